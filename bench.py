@@ -16,10 +16,20 @@
 Data parallel over N GPUs = N x the per-GPU batch per step (weak scaling), the gradient all-reduce through the
 C ABI's RCCL entry points (univer_hip.h: uocr_dp_*); torch.distributed (gloo) is the host-side control plane
 (rendezvous of the RCCL id, barriers, max-over-ranks of the elapsed time).  Rank 0 prints ONE JSON line with the
-whole-job images/s, the roofline of the dominant kernel (HIP events around each of its launches in the timed
-region + the same launch replayed alone), `roofline.secondary` (the wide 3x3 64->64 conv against the f32 MFMA
-peak and the pooling / activation / loss kernels against HBM, measured right after the timed loop) and the CPU
-baseline (oracle/ restatement of the reference timed on this box's host cores, same initial weights).
+whole-job images/s and `ms_per_step` of the timed steps.  A plain run does nothing else: set-up, warm-up, the
+--steps timed steps, the outputs (--dump-outputs), the line.
+
+--full adds what takes runs of its own: the roofline of the dominant kernel (HIP events around each of its launches
+in extra steps after the timed region + the same launch replayed alone), `roofline.secondary` (the wide 3x3 64->64
+conv against the f32 MFMA peak and the pooling / activation / loss kernels against HBM), the steady state over
+--steady-steps more steps, and the CPU baseline (oracle/ restatement of the reference timed on the host cores, same
+initial weights, first-step losses of the GPU path checked against it).
+
+--dump-outputs DIR: after the timed steps, what the last of them handed its caller, as DIR/<name>.npy (float32, losses
+float64): per net the prediction (`<net>_pred`; train: `<net>_losses` = output losses + L2 term, `<net>_weights` = the
+updated parameters, concatenated in Model.params() order).  An array of more than DUMP_SAMPLE elements is dumped as
+the same seeded sample of its flattened elements in every run.  Inputs and initial weights are seeded: the same
+arguments give the same inputs in every run.
 """
 import argparse
 import ctypes
@@ -34,6 +44,7 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level parameters)
 F32_PEAK_TFLOPS = 157.3        # dense f32 MFMA peak = f32 vector peak on gfx950 (same guide, peak table)
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: elements per array (4 MB); at most 3 arrays per net, 4 nets: < 64 MB
 
 CONFIGS = {
     'train-b32': dict(batch=32, height=256, width=512, dtype='float32', train=True,
@@ -235,6 +246,35 @@ def gpu_first_losses(cfg, args, weights, sample):
     return {name: float(l['output_losses'][0]) for name, l in losses.items()}
 
 
+def timed_outputs(trainer, context, losses, train):
+    """{name: host array} of what the last step handed its caller (see --dump-outputs); call after a device
+    synchronisation, before anything else runs on the trainer."""
+    import numpy as np
+
+    def sampled(a, dtype=np.float32):
+        a = np.asarray(a).astype(dtype)
+        if a.size <= DUMP_SAMPLE:
+            return a
+        idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+        return a.reshape(-1)[idx]
+    out = {}
+    for comp in trainer.model_system.components:
+        name = comp.name
+        pred = context[comp.selector.pred_label]
+        preds = pred if isinstance(pred, (list, tuple)) else [pred]
+        for i, p in enumerate(preds):
+            out[f'{name}_pred' + (f'{i}' if len(preds) > 1 else '')] = sampled(p.numpy())
+        if train:
+            l = losses[name]
+            out[f'{name}_losses'] = np.array([float(v) for v in l['output_losses']] + [float(l['regularization_loss'])],
+                                             dtype=np.float64)
+            out[f'{name}_weights'] = sampled(np.concatenate([p.value.numpy().reshape(-1).astype(np.float32)
+                                                             for p in trainer.models[name].params().values()]))
+    total = sum(a.nbytes for a in out.values())
+    assert total <= 64 << 20, f'--dump-outputs: {total} bytes'
+    return out
+
+
 def parse_xcds(spec):
     """'0-2,3-5,6-7' -> ((0, 1, 2), (3, 4, 5), (6, 7))"""
     groups = []
@@ -389,8 +429,13 @@ def main():
     ap.add_argument('--char-width', type=int, default=64)
     ap.add_argument('--optimizer', default='sgd', choices=['sgd', 'adam'])
     ap.add_argument('--lr', type=float, default=0.0015)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='skip roofline.secondary (the kernels measured after the loop)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the dominant-kernel roofline, roofline.secondary, the steady state and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-secondary', action='store_true',
+                    help='--full: skip roofline.secondary (the kernels measured after the loop)')
     ap.add_argument('--no-overlap', action='store_true')
     ap.add_argument('--no-pipeline', action='store_true',
                     help='end every step with the main stream waiting for all net streams (default: a net starts '
@@ -415,7 +460,7 @@ def main():
                     help='kernel selection knob of the C ABI, key=value (uocr_ctx_set_option: split_blocks, split_min, '
                          'gemm_bm, mfma, tiled, xcd_remap); experiments only')
     ap.add_argument('--steady-steps', type=int, default=300,
-                    help='N = 1: steps of the steady-state measurement after the timed region (0 = off)')
+                    help='--full, N = 1: steps of the steady-state measurement after the timed region (0 = off)')
     ap.add_argument('--step-timeout', type=float, default=300.0,
                     help='watchdog: exit with code 3 when no step / phase completes for this many seconds')
     args = ap.parse_args()
@@ -520,7 +565,7 @@ def main():
         key, value = opt.split('=')
         rt.set_option(key, int(value))          # (every lane)
     watchdog.beat('trainer built')
-    initial = flat_weights(trainer.models) if rank == 0 and not args.no_cpu_baseline and world == 1 else None
+    initial = flat_weights(trainer.models) if args.full and rank == 0 and not args.no_cpu_baseline and world == 1 else None
     first_gpu = None
     if initial is not None and train:
         # the production path on the CPU baseline's sample pages, before anything is timed (compared further down)
@@ -541,7 +586,7 @@ def main():
     n_convs = 3 if args.skip_input_grads else 4
     esize = 2 if cfg['dtype'] == 'float16' else 4
     if train:
-        probe = KernelProbe(rt, 'uocr_conv_pair_bwd', timer)
+        probed = 'uocr_conv_pair_bwd'
         # (the output Sigmoid' is applied by the Dice gradient kernel: the launch reads x and g = dLoss/d(conv_2 output) and
         # writes dx)
         dominant = {'kernel': 'uocr_conv_pair_bwd: fused backward of conv3x3(1->16)+LeakyReLU+conv3x3(16->1) (Monochrome; ' +
@@ -549,9 +594,10 @@ def main():
                                else 'pair_wave_bwd_h_kernel + pair_strip_finish, csrc/conv_pair_strip_h.hip)'),
                     'flops': 2.0 * 9 * 16 * n_convs * npix, 'bytes': float(esize) * npix * (n_convs - 1)}
     else:
-        probe = KernelProbe(rt, 'uocr_conv_pair_fwd', timer)
+        probed = 'uocr_conv_pair_fwd'
         dominant = {'kernel': 'uocr_conv_pair_fwd: fused forward of conv3x3(1->16)+LeakyReLU+conv3x3(16->1)+Sigmoid '
                               '(Monochrome)', 'flops': 2.0 * 9 * 16 * 2 * npix, 'bytes': float(esize) * npix * 2}
+    probe = KernelProbe(rt, probed, timer) if args.full else None
 
     def barrier():
         torch.cuda.synchronize()
@@ -605,10 +651,17 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     watchdog.beat('timed region done')
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, array in timed_outputs(trainer, context, losses, train).items():
+            np.save(os.path.join(args.dump_outputs, name + '.npy'), array)
+        watchdog.beat('outputs dumped')
     # The dominant launch inside the loop: events cannot be recorded into a captured graph on this ROCm, so the timed
     # region above replays ALL nets from graphs, and here the probed kernel's net runs eagerly for a few more steps
     # (same arithmetic) with a HIP-event pair around each launch of the entry point, the other lanes as before
-    if train:                                   # (every rank: the steps carry collectives)
+    dp_stats = None
+    if train and args.full:                     # (every rank: the steps carry collectives)
         probed_net = 'Monochrome'
         if graphs:
             trainer.set_eager_nets((probed_net,))
@@ -622,7 +675,6 @@ def main():
             one_step()
         barrier()
         probe.enabled = False
-        dp_stats = None
         if trainer.dp is not None:
             trainer.dp.profile = False
             dp_stats = trainer.dp.stats() or {}
@@ -638,7 +690,7 @@ def main():
     # steady state: the driver's run is short (20 steps = 17 ms), so the same loop once more over >= 300 steps in
     # chunks of 10 with a full synchronisation after each; the median chunk is robust against one slow chunk
     steady = None
-    if world == 1 and args.steady_steps > 0:
+    if args.full and world == 1 and args.steady_steps > 0:
         chunk, times = 10, []
         for c in range(max(1, args.steady_steps // chunk)):
             barrier()
@@ -663,32 +715,6 @@ def main():
     final = {n: [float(v) for v in l['output_losses']] for n, l in losses.items()} if losses else None
 
     if rank == 0:
-        kernel_us, launches = probe.mean_us()
-        solo_us = probe.solo_us()
-        watchdog.beat('solo replay done')
-
-        def priced(us):
-            if not us:
-                return None
-            if cfg['dtype'] == 'float16':
-                return dominant['bytes'] / us / 1e3          # GB/s
-            return dominant['flops'] / us / 1e6              # TFLOP/s
-        hbm_bound = cfg['dtype'] == 'float16'
-        peak = HBM_PEAK_GBS if hbm_bound else F32_PEAK_TFLOPS
-        in_loop, solo = priced(kernel_us), priced(solo_us)
-        # `achieved` / `frac`: the launch ALONE on the GPU (the kernel's own roofline; this is what the rocprofv3
-        # per-kernel average under profiles/ corresponds to).  In the timed region the nets run on three streams
-        # and share the machine: that figure is reported next to it.
-        headline = solo if solo else in_loop
-        traffic, traffic_source = None, None
-        tpath = os.path.join(ROOT, 'profiles', 'dominant_kernel_traffic.json')
-        if os.path.exists(tpath) and args.config == 'train-b32' and cfg['batch'] == 32 and not args.skip_input_grads:
-            with open(tpath) as f:
-                rec = json.load(f)
-            traffic = rec.get('hbm_bytes_per_launch')
-            traffic_source = ('NOT measured in this run: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this '
-                              'command, committed as profiles/dominant_kernel_traffic.json (' +
-                              str(rec.get('source', 'see profiles/README.md')) + ')')
         if dp_fallback:
             allreduce_desc = f'FALLBACK: gloo through the host, RCCL setup failed: {dp_fallback}'
         elif world > 1 and rehearsal:
@@ -728,18 +754,45 @@ def main():
                 'pipelined_lanes': not args.no_pipeline,
                 'hw_queues': os.environ.get('GPU_MAX_HW_QUEUES', 'default (4)'),
             },
-            'roofline': {'bound': 'hbm' if hbm_bound else 'mfma', 'kernel': dominant['kernel'],
-                         'achieved': None if headline is None else round(headline, 2),
-                         'peak': peak, 'unit': 'GB/s' if hbm_bound else 'TFLOP/s',
-                         'frac': None if headline is None else round(headline / peak, 4),
-                         'traffic': traffic, 'traffic_source': traffic_source,
-                         'solo_launch_us': None if solo_us is None else round(solo_us, 2),
-                         'in_loop_launch_us': round(kernel_us, 2) if launches else None, 'in_loop_achieved': None if in_loop is None else round(in_loop, 2),
-                         'launches_timed': launches,
-                         'algorithmic_flops_per_launch': dominant['flops'],
-                         'algorithmic_bytes_per_launch': dominant['bytes']},
         }
-        if world == 1 and not args.no_secondary:
+        if args.full:
+            kernel_us, launches = probe.mean_us()
+            solo_us = probe.solo_us()
+            watchdog.beat('solo replay done')
+
+            def priced(us):
+                if not us:
+                    return None
+                if cfg['dtype'] == 'float16':
+                    return dominant['bytes'] / us / 1e3          # GB/s
+                return dominant['flops'] / us / 1e6              # TFLOP/s
+            hbm_bound = cfg['dtype'] == 'float16'
+            peak = HBM_PEAK_GBS if hbm_bound else F32_PEAK_TFLOPS
+            in_loop, solo = priced(kernel_us), priced(solo_us)
+            # `achieved` / `frac`: the launch ALONE on the GPU (the kernel's own roofline; this is what the rocprofv3
+            # per-kernel average under profiles/ corresponds to).  In the timed region the nets run on three streams
+            # and share the machine: that figure is reported next to it.
+            headline = solo if solo else in_loop
+            traffic, traffic_source = None, None
+            tpath = os.path.join(ROOT, 'profiles', 'dominant_kernel_traffic.json')
+            if os.path.exists(tpath) and args.config == 'train-b32' and cfg['batch'] == 32 and not args.skip_input_grads:
+                with open(tpath) as f:
+                    rec = json.load(f)
+                traffic = rec.get('hbm_bytes_per_launch')
+                traffic_source = ('NOT measured in this run: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this '
+                                  'command, committed as profiles/dominant_kernel_traffic.json (' +
+                                  str(rec.get('source', 'see profiles/README.md')) + ')')
+            out['roofline'] = {'bound': 'hbm' if hbm_bound else 'mfma', 'kernel': dominant['kernel'],
+                               'achieved': None if headline is None else round(headline, 2),
+                               'peak': peak, 'unit': 'GB/s' if hbm_bound else 'TFLOP/s',
+                               'frac': None if headline is None else round(headline / peak, 4),
+                               'traffic': traffic, 'traffic_source': traffic_source,
+                               'solo_launch_us': None if solo_us is None else round(solo_us, 2),
+                               'in_loop_launch_us': round(kernel_us, 2) if launches else None, 'in_loop_achieved': None if in_loop is None else round(in_loop, 2),
+                               'launches_timed': launches,
+                               'algorithmic_flops_per_launch': dominant['flops'],
+                               'algorithmic_bytes_per_launch': dominant['bytes']}
+        if args.full and world == 1 and not args.no_secondary:
             del context, layers
             trainer.join()
             torch.cuda.synchronize()
@@ -752,7 +805,7 @@ def main():
             out['steady_state'] = steady
         if train and dp_stats is not None:
             out['dp'] = dp_stats       # (rank 0's view: per-collective device times of the probe steps)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             watchdog.limit = max(watchdog.limit, 600.0)      # host-only phase: no collective can hang here
             out['cpu_baseline'] = cpu_baseline(cfg, args, initial)
             if first_gpu is not None and out['cpu_baseline'].get('first_losses'):

@@ -95,6 +95,42 @@ def test_bench_two_rank_rehearsal_prints_one_valid_line():
     assert all(np.isfinite(v).all() for v in map(np.array, rec['config']['final_losses'].values()))
 
 
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain `bench.py` run prints the headline line only (nothing that takes runs of its own) and --dump-outputs
+    writes per net the prediction, the losses and the updated weights of the last timed step: the same in two runs
+    with the same arguments, the losses those of the line.  --full adds the dominant-kernel roofline, the steady
+    state and the CPU baseline."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    small = ['--steps', '3', '--warmup', '1', '--batch', '2', '--height', '64', '--width', '128']
+
+    def run(*extra):
+        out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', *small, *extra], cwd=root,
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [line for line in out.stdout.splitlines() if line.startswith('{')]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+    dumps = []
+    for i in range(2):
+        rec = run('--dump-outputs', str(tmp_path / f'run{i}'))
+        assert rec['steps'] == 3 and rec['ms_per_step'] > 0 and rec['value'] > 0
+        assert not {'roofline', 'steady_state', 'cpu_baseline'} & set(rec)
+        dumps.append({p.stem: np.load(p) for p in (tmp_path / f'run{i}').glob('*.npy')})
+    nets = ('Monochrome', 'Paragraph', 'Line', 'Char')
+    assert set(dumps[0]) == {f'{n}_{what}' for n in nets for what in ('pred', 'losses', 'weights')}
+    for name, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), name
+        np.testing.assert_allclose(dumps[1][name], a, rtol=1e-5, atol=1e-7, err_msg=name)
+    for n in nets:
+        np.testing.assert_allclose(dumps[1][f'{n}_losses'][:-1], rec['config']['final_losses'][n], rtol=1e-5)
+    rec = run('--full', '--no-secondary', '--steady-steps', '20')
+    assert rec['roofline']['launches_timed'] > 0 and rec['steady_state']['steps'] == 20
+    assert rec['cpu_baseline']['value'] > 0 and 'gpu_vs_cpu_first_loss_rel_diff' in rec['cpu_baseline']
+
+
 def test_page_feeder_into_static_graph_inputs():
     """The upload pipeline converting straight into the arrays the HIP graphs read
     (PageFeeder.context(into=PageTrainer.static_inputs())) trains exactly like make_context() on the same

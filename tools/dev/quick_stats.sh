@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/quick_$CFG
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT" --output-format csv -- \
-    python3 "$R/bench.py" --config $CFG --steps 20 --warmup 5 --steady-steps 0 --no-cpu-baseline --no-secondary > "$OUT/bench.json" 2> "$OUT/err.txt"
+    python3 "$R/bench.py" --full --config $CFG --steps 20 --warmup 5 --steady-steps 0 --no-cpu-baseline --no-secondary > "$OUT/bench.json" 2> "$OUT/err.txt"
 cd "$R"
 python3 - "$OUT" <<'PY'
 import csv, glob, sys

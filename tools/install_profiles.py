@@ -25,7 +25,7 @@ def part(name):
     return None
 
 
-def summarise(stats_dir, stem, marker, steps=46):      # 5 warm-up + 20 timed + 1 + 20 probe steps of bench.py --steps 20 --warmup 5
+def summarise(stats_dir, stem, marker, steps=46):      # 5 warm-up + 20 timed + 1 + 20 probe steps of bench.py --full --steps 20 --warmup 5
     """kernel stats of one profiled bench command -> profiles/<TAG>_<stem>_kernel_stats.csv + a per-step summary.
     (rocprofv3 also writes a file for the profiler's helper process: take the one that holds `marker`.)"""
     paths = [p for p in glob.glob(f'{R}/{stats_dir}/*/*_kernel_stats.csv') if marker in open(p).read()]

@@ -13,14 +13,14 @@ cd /tmp && export TMPDIR=/tmp
 case "$1" in
   stats)
     timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/stats" --output-format csv -- \
-        python3 "$R/bench.py" --steps 20 --warmup 5 --steady-steps 0 --no-cpu-baseline --no-secondary > "$OUT/bench_under_rocprofv3.json" 2> "$OUT/stats.err"
+        python3 "$R/bench.py" --full --steps 20 --warmup 5 --steady-steps 0 --no-cpu-baseline --no-secondary > "$OUT/bench_under_rocprofv3.json" 2> "$OUT/stats.err"
     timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/stats_hr" --output-format csv -- \
-        python3 "$R/bench.py" --config highres-fp16 --steps 20 --warmup 5 --steady-steps 0 --no-cpu-baseline --no-secondary > "$OUT/bench_hr_under_rocprofv3.json" 2> "$OUT/stats_hr.err"
+        python3 "$R/bench.py" --full --config highres-fp16 --steps 20 --warmup 5 --steady-steps 0 --no-cpu-baseline --no-secondary > "$OUT/bench_hr_under_rocprofv3.json" 2> "$OUT/stats_hr.err"
     cd "$R"
-    timeout -k 10 500 python3 bench.py > "$OUT/bench_n1.json" 2> "$OUT/bench.err"
-    timeout -k 10 500 python3 bench.py --config highres-fp16 > "$OUT/bench_hr_n1.json" 2> "$OUT/bench_hr.err"
-    timeout -k 10 500 python3 bench.py --config infer-b8 --no-secondary > "$OUT/bench_infer_n1.json" 2> "$OUT/bench_infer.err"
-    UOCR_BENCH_FORCE_DP=1 timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-secondary > "$OUT/bench_dp1_rehearsal.json" 2> "$OUT/bench_dp1.err"
+    timeout -k 10 500 python3 bench.py --full > "$OUT/bench_n1.json" 2> "$OUT/bench.err"
+    timeout -k 10 500 python3 bench.py --full --config highres-fp16 > "$OUT/bench_hr_n1.json" 2> "$OUT/bench_hr.err"
+    timeout -k 10 500 python3 bench.py --full --config infer-b8 --no-secondary > "$OUT/bench_infer_n1.json" 2> "$OUT/bench_infer.err"
+    UOCR_BENCH_FORCE_DP=1 timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-secondary > "$OUT/bench_dp1_rehearsal.json" 2> "$OUT/bench_dp1.err"
     timeout -k 10 400 python3 tools/bench_conv.py > "$OUT/conv_microbench.txt" 2>&1
     timeout -k 10 300 python3 tools/bench_membw.py > "$OUT/membw.txt" 2>&1
     timeout -k 10 300 python3 tools/bench_h16.py > "$OUT/bench_h16.txt" 2>&1
@@ -31,9 +31,9 @@ case "$1" in
     ;;
   pmc)
     timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_fetch" --output-format csv -- \
-        python3 "$R/bench.py" --steps 3 --warmup 1 --steady-steps 0 --no-cpu-baseline --no-secondary > "$OUT/pmc_fetch.json" 2> "$OUT/pmc_fetch.err"
+        python3 "$R/bench.py" --full --steps 3 --warmup 1 --steady-steps 0 --no-cpu-baseline --no-secondary > "$OUT/pmc_fetch.json" 2> "$OUT/pmc_fetch.err"
     timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_write" --output-format csv -- \
-        python3 "$R/bench.py" --steps 3 --warmup 1 --steady-steps 0 --no-cpu-baseline --no-secondary > "$OUT/pmc_write.json" 2> "$OUT/pmc_write.err"
+        python3 "$R/bench.py" --full --steps 3 --warmup 1 --steady-steps 0 --no-cpu-baseline --no-secondary > "$OUT/pmc_write.json" 2> "$OUT/pmc_write.err"
     cd "$R"
     bash tools/pmc_pair.sh refresh pair > "$OUT/pmc_pair_summary.txt" 2>&1
     ;;
