@@ -89,9 +89,14 @@ void* uocr_ctx_get_stream(uocr_ctx* ctx);
  * float32 Line output conv forward on error-compensated binary16 MFMAs); the Monochrome pair kernels:
  * "pair_band" (rows per band, 0 auto), "pair_g" (4 / 2 groups of 16 columns per wave), "pair_pf" (row prefetch form
  * of the forward kernels, -1 auto); "wgrad_bands" (row bands per tap / channel group of the direct weight-gradient
- * kernels, 0 = 64 or 512 by the kernel's accumulator count).  Results do not depend on any of them beyond float32
+ * kernels, 0 = 64 or 512 by the kernel's accumulator count); "max_blocks" (k > 0 lowers every block budget that is
+ * decided at run time -- persistent tile walks, rows or tiles per block -- to k, so that small shapes make blocks walk
+ * several tiles; it never raises one; 0 = the budgets as they are).  Results do not depend on any of them beyond float32
  * summation order ("h16": beyond the binary16 rounding of the weight operands; "h3": 22 significant bits). */
 int uocr_ctx_set_option(uocr_ctx* ctx, const char* key, int value);
+/* the block count and the number of work items (tiles, or strips x row bands x images) of the most recent launch on
+ * this ctx whose split was decided at run time (the sites "max_blocks" applies to); 0 / 0 before the first */
+int uocr_ctx_last_split(uocr_ctx* ctx, int* blocks, long long* items);
 int uocr_ctx_reserve_workspace(uocr_ctx* ctx, size_t bytes);   /* synchronises; not capturable */
 const char* uocr_last_error(uocr_ctx* ctx);
 int uocr_malloc(uocr_ctx* ctx, size_t bytes, void** out);                       /* cupy.zeros/asarray */

@@ -1177,9 +1177,11 @@ int launch_wgrad_s2(uocr_ctx* ctx, int dtype, const void* x, const void* dy, voi
     using C = S2Cfg<CIN, COUT>;
     const int tiles_x = (d.ow + C::TW - 1) / C::TW, tiles_y = (d.oh + C::TH - 1) / C::TH;
     int per_block = 1;                                      // ~1024 blocks: a few tiles of one column strip each
-    while (per_block < tiles_y && (size_t)tiles_x * ((tiles_y + per_block - 1) / per_block) * d.n > 1024) ++per_block;
+    while (per_block < tiles_y && (size_t)tiles_x * ((tiles_y + per_block - 1) / per_block) * d.n > (size_t)uocr_budget(ctx, 1024))
+        ++per_block;
     const dim3 grid(tiles_x, (tiles_y + per_block - 1) / per_block, d.n);
     const int nblocks = (int)(grid.x * grid.y * grid.z);
+    uocr_note_split(ctx, nblocks, (long long)tiles_x * tiles_y * d.n);
     int rc = UOCR_OK;
     float* partial = uocr_partial_buffer(ctx, (size_t)nblocks * 5 * C::NP * sizeof(float), &rc);
     if (rc) return rc;
@@ -1427,10 +1429,12 @@ int uocr_conv_wgrad_fast(uocr_ctx* ctx, int dtype, const void* x, const void* dy
     const bool f32 = UOCR_DTYPE_BASE(dtype) == UOCR_F32;
     if (f32 && is_c16_same(d, 16, 1) && pad_value == 0.0) {
         constexpr int NA = 3 * 3 * 4 + 1;
-        int rows = (d.n * d.h + 2047) / 2048;
+        const long budget = uocr_budget(ctx, 2048);
+        int rows = (int)((d.n * d.h + budget - 1) / budget);
         rows = ((rows + 3) / 4) * 4;
         if (rows > d.h) rows = ((d.h + 3) / 4) * 4;
         const int nbands = (d.h + rows - 1) / rows, nblocks = nbands * d.n;
+        uocr_note_split(ctx, nblocks, (long long)((d.h + 3) / 4) * d.n);     // (work items: bands of 4 rows)
         int rc = uocr_need_workspace(ctx, (size_t)nblocks * 4 * NA * sizeof(float));
         if (rc) return rc;
         float* partial = (float*)ctx->workspace;
@@ -1452,9 +1456,11 @@ int uocr_conv_wgrad_fast(uocr_ctx* ctx, int dtype, const void* x, const void* dy
         const int tiles_x = (d.w + t542::TW - 1) / t542::TW, tiles_y = (d.h + t542::TH - 1) / t542::TH;
         int per_block = 1;                                  // ~1024 blocks: a few tiles of one column strip each
         // (measured at 32 x 256 x 512: 512 blocks 58 us, 1024 57, 2048 65, 4096 74)
-        while (per_block < tiles_y && (size_t)tiles_x * ((tiles_y + per_block - 1) / per_block) * d.n > 1024) ++per_block;
+        while (per_block < tiles_y && (size_t)tiles_x * ((tiles_y + per_block - 1) / per_block) * d.n > (size_t)uocr_budget(ctx, 1024))
+            ++per_block;
         const dim3 grid(tiles_x, (tiles_y + per_block - 1) / per_block, d.n);
         const int nblocks = (int)(grid.x * grid.y * grid.z);
+        uocr_note_split(ctx, nblocks, (long long)tiles_x * tiles_y * d.n);
         int rc = UOCR_OK;
         float* partial = uocr_partial_buffer(ctx, (size_t)nblocks * 5 * t542::NACC * sizeof(float), &rc);
         if (rc) return rc;

@@ -387,8 +387,9 @@ int launch_h16(uocr_ctx* ctx, const void* in, const void* w, const void* bias, v
     // 4 x the resident blocks: when other lanes hold part of the CUs only some blocks of a launch are resident and
     // the rest start late -- with exactly one block per slot the late ones still own 1/grid of the tiles each (measured
     // in the three-lane step: 6.66 -> 6.75 k pages/s; alone the kernels do not care)
-    const long cap = (long)ctx->cu_count * resident * 4;
+    const long cap = uocr_budget(ctx, (long)ctx->cu_count * resident * 4);
     const int grid = (int)(ntiles < cap ? ntiles : cap);
+    uocr_note_split(ctx, grid, ntiles);
     hipLaunchKernelGGL(conv_h16_kernel<G>, dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)in, (const float*)w,
                        (const float*)bias, (_Float16*)out, (const _Float16*)mask_y, h_in, w_in, h_out, w_out, ph, pw,
                        tiles_x, tiles_y, (int)ntiles, pad, use_bias, act, alpha, mask_act, mask_alpha);

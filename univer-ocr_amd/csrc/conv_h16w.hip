@@ -816,9 +816,10 @@ int uocr_conv_wgrad_h16(uocr_ctx* ctx, int dtype, const void* x, const void* dy,
     const int tiles_x = (d.w + 4 + e42::BC - 1) / e42::BC, tiles_y = (d.h + br - 1) / br;   // (both: 64 columns)
     const long ntiles = (long)d.n * tiles_y * tiles_x;
     UOCR_REQUIRE(ctx, ntiles < (1l << 31));
-    const long cap = (long)ctx->cu_count * (one ? resident_blocks(ctx, wgrad_h16_e11_kernel, &cache11)
-                                                : resident_blocks(ctx, wgrad_h16_e42_kernel, &cache42));
+    const long cap = uocr_budget(ctx, (long)ctx->cu_count * (one ? resident_blocks(ctx, wgrad_h16_e11_kernel, &cache11)
+                                                                : resident_blocks(ctx, wgrad_h16_e42_kernel, &cache42)));
     const int grid = (int)(ntiles < cap ? ntiles : cap);
+    uocr_note_split(ctx, grid, ntiles);
     int rc = UOCR_OK;
     float* partial = uocr_partial_buffer(ctx, (size_t)grid * nv * sizeof(float), &rc);
     if (rc != UOCR_OK) return rc;
@@ -844,8 +845,9 @@ int uocr_upconv_wgrad_h16(uocr_ctx* ctx, const void* x_low, const void* dy, floa
         const int tiles_x = (wl + up1::BC - 1) / up1::BC, tiles_y = (hl + up1::BR - 1) / up1::BR;
         const long ntiles = (long)n * tiles_y * tiles_x;
         UOCR_REQUIRE(ctx, ntiles < (1l << 31) && (long)hl * wl * 4 < (1l << 31));
-        const long cap = (long)ctx->cu_count * resident_blocks(ctx, wgrad_h16_up1_kernel, &cache1);
+        const long cap = uocr_budget(ctx, (long)ctx->cu_count * resident_blocks(ctx, wgrad_h16_up1_kernel, &cache1));
         const int grid = (int)(ntiles < cap ? ntiles : cap);
+        uocr_note_split(ctx, grid, ntiles);
         UOCR_REQUIRE(ctx, (size_t)grid * UP1_NOUT <= partial_floats);
         hipLaunchKernelGGL(wgrad_h16_up1_kernel, dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)x_low,
                            (const _Float16*)dy, partial, hl, wl, tiles_x, tiles_y, (int)ntiles);
@@ -857,8 +859,9 @@ int uocr_upconv_wgrad_h16(uocr_ctx* ctx, const void* x_low, const void* dy, floa
     const int tiles_x = (wl + up::BC - 1) / up::BC, tiles_y = (hl + up::BR - 1) / up::BR;
     const long ntiles = (long)n * tiles_y * tiles_x;
     UOCR_REQUIRE(ctx, ntiles < (1l << 31) && (long)hl * wl * 16 < (1l << 31));
-    const long cap = (long)ctx->cu_count * resident_blocks(ctx, wgrad_h16_up_kernel, &cache);
+    const long cap = uocr_budget(ctx, (long)ctx->cu_count * resident_blocks(ctx, wgrad_h16_up_kernel, &cache));
     const int grid = (int)(ntiles < cap ? ntiles : cap);
+    uocr_note_split(ctx, grid, ntiles);
     UOCR_REQUIRE(ctx, (size_t)grid * UP4_NOUT <= partial_floats);
     hipLaunchKernelGGL(wgrad_h16_up_kernel, dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)x_low,
                        (const _Float16*)dy, partial, hl, wl, tiles_x, tiles_y, (int)ntiles);
@@ -884,8 +887,9 @@ int launch_s2(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw,
     const int tiles_x = (d.ow + 2 + G::BC - 1) / G::BC, tiles_y = (d.oh + G::BR - 1) / G::BR;   // Q runs over [-1, ow]
     const long ntiles = (long)d.n * tiles_y * tiles_x;
     UOCR_REQUIRE(ctx, ntiles < (1l << 31));
-    const long cap = (long)ctx->cu_count * resident_blocks(ctx, wgrad_h16_s2_kernel<CI, CO>, &cache);
+    const long cap = uocr_budget(ctx, (long)ctx->cu_count * resident_blocks(ctx, wgrad_h16_s2_kernel<CI, CO>, &cache));
     const int grid = (int)(ntiles < cap ? ntiles : cap);
+    uocr_note_split(ctx, grid, ntiles);
     int rc = UOCR_OK;
     float* partial = uocr_partial_buffer(ctx, (size_t)grid * G::NV * sizeof(float), &rc);
     if (rc != UOCR_OK) return rc;

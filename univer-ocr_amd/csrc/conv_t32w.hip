@@ -323,8 +323,9 @@ int launch_s2(uocr_ctx* ctx, const void* x, const void* dy, void* dw, void* db, 
     const int tiles_x = (d.ow + 2 + G::BC - 1) / G::BC, tiles_y = (d.oh + G::BR - 1) / G::BR;   // Q runs over [-1, ow]
     const long ntiles = (long)d.n * tiles_y * tiles_x;
     UOCR_REQUIRE(ctx, ntiles < (1l << 31));
-    const long cap = (long)ctx->cu_count * resident_blocks(wgrad_t32_s2_kernel<CI, CO>, &cache);
+    const long cap = uocr_budget(ctx, (long)ctx->cu_count * resident_blocks(wgrad_t32_s2_kernel<CI, CO>, &cache));
     const int grid = (int)(ntiles < cap ? ntiles : cap);
+    uocr_note_split(ctx, grid, ntiles);
     int rc = uocr_need_workspace(ctx, (size_t)grid * G::NV * sizeof(float));
     if (rc != UOCR_OK) return rc;
     float* partial = (float*)ctx->workspace;
@@ -345,8 +346,9 @@ int launch_e(uocr_ctx* ctx, const void* x, const void* dy, void* dw, void* db, c
     const int tiles_x = (d.w + 4 + G::BC - 1) / G::BC, tiles_y = (d.h + G::BR - 1) / G::BR;     // col runs over [-4, w)
     const long ntiles = (long)d.n * tiles_y * tiles_x;
     UOCR_REQUIRE(ctx, ntiles < (1l << 31));
-    const long cap = (long)ctx->cu_count * resident_blocks(wgrad_t32_e_kernel<CI, CO>, &cache);
+    const long cap = uocr_budget(ctx, (long)ctx->cu_count * resident_blocks(wgrad_t32_e_kernel<CI, CO>, &cache));
     const int grid = (int)(ntiles < cap ? ntiles : cap);
+    uocr_note_split(ctx, grid, ntiles);
     int rc = uocr_need_workspace(ctx, (size_t)grid * G::NV * sizeof(float));
     if (rc != UOCR_OK) return rc;
     float* partial = (float*)ctx->workspace;

@@ -555,7 +555,8 @@ extern "C" int uocr_upconv2x_fwd(uocr_ctx* ctx, int dtype, const void* x_low, co
     if (rc != UOCR_OK) return rc;
     if (uocr_upconv_h16_eligible(ctx, dtype, cin, cout) && uocr_aligned_act(x_low, dtype) && uocr_aligned_act(y, dtype))
         return uocr_upconv_fwd_h16(ctx, x_low, w, b, y, n, hl, wl, use_bias, act, act_alpha);
-    const int strips = (wl + RW - 1) / RW, rows = up_rows_per_block(strips, hl, n);
+    const int strips = (wl + RW - 1) / RW, rows = up_rows_per_block(strips, hl, n, (unsigned)uocr_budget(ctx, 2048));
+    if (cin != 1) uocr_note_split(ctx, (long long)strips * ((hl + rows - 1) / rows) * n, (long long)strips * ((hl + RH - 1) / RH) * n);
     UOCR_DISPATCH_TA(ctx, dtype, {
         if (cin == 1)
             hipLaunchKernelGGL((up1_fwd_kernel<TA>), dim3((wl + RW - 1) / RW, (hl + RH - 1) / RH, n), dim3(256), 0,
@@ -644,8 +645,9 @@ extern "C" int uocr_upconv2x_bwd_weight(uocr_ctx* ctx, int dtype, const void* x_
         return finish(partial, nblocks);
     }
     // fewer, longer blocks than the forward: every block ends with a reduction and a partial row for the finish kernel
-    const int strips = (wl + RW - 1) / RW, rows = up_rows_per_block(strips, hl, n, 1024u);
+    const int strips = (wl + RW - 1) / RW, rows = up_rows_per_block(strips, hl, n, (unsigned)uocr_budget(ctx, 1024));
     const int bands = (hl + rows - 1) / rows, nblocks = strips * bands * n;
+    uocr_note_split(ctx, nblocks, (long long)strips * ((hl + RH - 1) / RH) * n);       // (work items: bands of RH rows)
     float* partial = uocr_partial_buffer(ctx, (size_t)nblocks * ncols * sizeof(float), &rc);
     if (rc != UOCR_OK) return rc;
     UOCR_DISPATCH_TA(ctx, dtype, {

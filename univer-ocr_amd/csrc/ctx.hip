@@ -45,6 +45,9 @@ int uocr_ctx_create(int device, size_t workspace_bytes, uocr_ctx** out) {
     ctx->opt_pair_g = 4;
     ctx->opt_group_blocks = 0;
     ctx->opt_wgrad_bands = 0;
+    ctx->opt_max_blocks = 0;
+    ctx->split_blocks = 0;
+    ctx->split_items = 0;
     ctx->opt_h3 = 0;
 #ifdef UOCR_EXPERIMENTS
     if (const char* e = getenv("UOCR_H3")) ctx->opt_h3 = atoi(e);            // development override (tools/dev/h3_ab.sh)
@@ -145,6 +148,7 @@ int uocr_ctx_set_option(uocr_ctx* ctx, const char* key, int value) {
     else if (!strcmp(key, "pair_g")) ctx->opt_pair_g = value;
     else if (!strcmp(key, "group_blocks")) ctx->opt_group_blocks = value;
     else if (!strcmp(key, "wgrad_bands") && value >= 0) ctx->opt_wgrad_bands = value;
+    else if (!strcmp(key, "max_blocks") && value >= 0) ctx->opt_max_blocks = value;
     else if (!strcmp(key, "h3")) {
 #ifndef UOCR_EXPERIMENTS
         if (value) UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "option h3: this library was built without conv_h3 "
@@ -154,6 +158,14 @@ int uocr_ctx_set_option(uocr_ctx* ctx, const char* key, int value) {
     }
     else if (!strcmp(key, "pair_pf")) ctx->opt_pair_pf = value;
     else UOCR_FAIL(ctx, UOCR_ERR_ARG, "unknown option '%s'", key);
+    return UOCR_OK;
+}
+
+int uocr_ctx_last_split(uocr_ctx* ctx, int* blocks, long long* items) {
+    UOCR_CHECK_CTX(ctx);
+    UOCR_REQUIRE(ctx, blocks && items);
+    *blocks = ctx->split_blocks;
+    *items = ctx->split_items;
     return UOCR_OK;
 }
 

@@ -37,6 +37,9 @@ struct uocr_ctx {
     int opt_group_blocks; // blocks of a deferred weight-gradient group (0 = four per CU)
     int opt_wgrad_bands;  // row bands per tap / channel group of the direct weight-gradient kernels (0 = by accumulator count)
     int opt_pair_g;      // groups of 16 columns per wave of the strip kernels: 4 (8 waves per block) or 2 (16 waves)
+    int opt_max_blocks;  // k > 0 lowers every run-time block budget to k (tests: several tiles per block at small shapes)
+    int split_blocks;    // uocr_ctx_last_split: blocks and work items of the last launch with a run-time split
+    long long split_items;
     char err[512];
 };
 
@@ -128,6 +131,16 @@ static inline unsigned uocr_blocks_for(size_t items, unsigned per_block, unsigne
     if (b < 1) b = 1;
     if (b > cap) b = cap;
     return (unsigned)b;
+}
+
+// a block budget of a launch that sizes its work at run time, lowered to the "max_blocks" option when that is set and
+// smaller (never raised: some partial buffers are sized by the budget); the launch then reports its split
+static inline long uocr_budget(const uocr_ctx* ctx, long budget) {
+    return ctx->opt_max_blocks > 0 && ctx->opt_max_blocks < budget ? ctx->opt_max_blocks : budget;
+}
+static inline void uocr_note_split(uocr_ctx* ctx, long long blocks, long long items) {
+    ctx->split_blocks = (int)blocks;
+    ctx->split_items = items;
 }
 
 // grid cap for grid-stride HBM-bound kernels: 256 CUs x 8 blocks of 256 threads

@@ -51,6 +51,7 @@ _PROTOS = {
     'uocr_ctx_set_stream': [_ctx, _vp],
     'uocr_ctx_reserve_workspace': [_ctx, _sz],
     'uocr_ctx_set_option': [_ctx, C.c_char_p, _i],
+    'uocr_ctx_last_split': [_ctx, C.POINTER(_i), C.POINTER(C.c_longlong)],
     'uocr_malloc': [_ctx, _sz, C.POINTER(_vp)],
     'uocr_free': [_ctx, _vp],
     'uocr_memset_zero': [_ctx, _vp, _sz],

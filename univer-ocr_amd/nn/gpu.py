@@ -130,6 +130,14 @@ class Runtime:
         self._options = getattr(self, '_options', {})
         self._options[key] = int(value)              # (replayed on contexts made later: side streams)
 
+    def last_split(self):
+        """(blocks, work items) of the most recent launch on the current lane whose split was decided at run time
+        (persistent tile walks, rows or tiles per block: the launches the 'max_blocks' option lowers)."""
+        import ctypes as C
+        blocks, items = C.c_int(), C.c_longlong()
+        self.call('uocr_ctx_last_split', C.byref(blocks), C.byref(items))
+        return blocks.value, items.value
+
     def set_loss_snapshot(self, arena):
         """From now on the fused optimizer tails launched on the CURRENT lane end by copying `arena`'s slots into the next
         row of its ring (LossArena.arm); None switches it off."""
