@@ -97,6 +97,13 @@ int uocr_ctx_set_option(uocr_ctx* ctx, const char* key, int value);
 /* the block count and the number of work items (tiles, or strips x row bands x images) of the most recent launch on
  * this ctx whose split was decided at run time (the sites "max_blocks" applies to); 0 / 0 before the first */
 int uocr_ctx_last_split(uocr_ctx* ctx, int* blocks, long long* items);
+/* the most recent float32 MFMA GEMM launched on this ctx (gemm_mfma.hip; "mfma", "gemm_bm", "split_blocks", "split_min",
+ * "xcd_remap" steer it): its row tile (64 / 128), its grid of output tiles (gm row tiles x gn 64-column tiles) and its
+ * depth slabs (1 = unsplit).  A deferred weight-gradient group flush reports bm = 64, gm = gn = 0 and nsplit = the
+ * largest split of its problems; uocr_ctx_last_gemm_group gives the number of problems of that flush and how many of
+ * them were split.  All 0 before the first. */
+int uocr_ctx_last_gemm(uocr_ctx* ctx, int* bm, int* gm, int* gn, int* nsplit);
+int uocr_ctx_last_gemm_group(uocr_ctx* ctx, int* problems, int* split_problems);
 int uocr_ctx_reserve_workspace(uocr_ctx* ctx, size_t bytes);   /* synchronises; not capturable */
 const char* uocr_last_error(uocr_ctx* ctx);
 int uocr_malloc(uocr_ctx* ctx, size_t bytes, void** out);                       /* cupy.zeros/asarray */
@@ -140,7 +147,10 @@ int uocr_ctx_set_loss_snapshot(uocr_ctx* ctx, const double* slots, int count, do
  * and flush runs all of them as ONE grid and one reduction; every other call is unaffected.  Operands named in
  * recorded calls must stay valid and unchanged until the flush.  keep_open != 0: flush what is recorded and keep
  * recording (a gradient bucket must be complete now).  Same sums as the separate launches up to float32 summation
- * order (the depth splits are chosen for the group). */
+ * order (the depth splits are chosen for the group).  The problems of one group run concurrently, so a call whose dw
+ * or db overlaps the dw or db of a call already recorded first flushes what is recorded, then records: calls that
+ * accumulate into one gradient still add up as they would one after the other.  A group holds at most 8 problems
+ * and 4 of each kind (conv / dense); a call beyond that is launched at once, outside the group. */
 int uocr_wgrad_defer_begin(uocr_ctx* ctx);
 int uocr_wgrad_defer_flush(uocr_ctx* ctx, int keep_open);
 /* name, CU count, HBM bytes of the ctx's device (train.py:70-90 prints the numba equivalents) */

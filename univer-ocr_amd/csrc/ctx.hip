@@ -48,6 +48,8 @@ int uocr_ctx_create(int device, size_t workspace_bytes, uocr_ctx** out) {
     ctx->opt_max_blocks = 0;
     ctx->split_blocks = 0;
     ctx->split_items = 0;
+    ctx->gemm_bm = ctx->gemm_gm = ctx->gemm_gn = ctx->gemm_nsplit = 0;
+    ctx->gemm_group_count = ctx->gemm_group_split = 0;
     ctx->opt_h3 = 0;
 #ifdef UOCR_EXPERIMENTS
     if (const char* e = getenv("UOCR_H3")) ctx->opt_h3 = atoi(e);            // development override (tools/dev/h3_ab.sh)
@@ -166,6 +168,24 @@ int uocr_ctx_last_split(uocr_ctx* ctx, int* blocks, long long* items) {
     UOCR_REQUIRE(ctx, blocks && items);
     *blocks = ctx->split_blocks;
     *items = ctx->split_items;
+    return UOCR_OK;
+}
+
+int uocr_ctx_last_gemm(uocr_ctx* ctx, int* bm, int* gm, int* gn, int* nsplit) {
+    UOCR_CHECK_CTX(ctx);
+    UOCR_REQUIRE(ctx, bm && gm && gn && nsplit);
+    *bm = ctx->gemm_bm;
+    *gm = ctx->gemm_gm;
+    *gn = ctx->gemm_gn;
+    *nsplit = ctx->gemm_nsplit;
+    return UOCR_OK;
+}
+
+int uocr_ctx_last_gemm_group(uocr_ctx* ctx, int* problems, int* split_problems) {
+    UOCR_CHECK_CTX(ctx);
+    UOCR_REQUIRE(ctx, problems && split_problems);
+    *problems = ctx->gemm_group_count;
+    *split_problems = ctx->gemm_group_split;
     return UOCR_OK;
 }
 

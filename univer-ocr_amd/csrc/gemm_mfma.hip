@@ -752,6 +752,10 @@ int launch_mfma(uocr_ctx* ctx, const ALoader& A, const BLoader& B, const Epilogu
     const int tps = (ntiles + nsplit - 1) / nsplit;
     nsplit = (ntiles + tps - 1) / tps;
     float* slabs = nsplit > 1 ? ws_slabs(ctx) : nullptr;
+    ctx->gemm_bm = bm;
+    ctx->gemm_gm = gm;
+    ctx->gemm_gn = gn;
+    ctx->gemm_nsplit = nsplit;
     const dim3 grid(gm, gn, nsplit), block(256);
     if (bm == 128)
         hipLaunchKernelGGL((mfma_gemm_kernel<128, ALoader, BLoader>), grid, block, 0, ctx->stream, A, B, ep, M, N, ntiles, tps,
@@ -852,16 +856,46 @@ struct GemmDefer {
 
 inline GemmDefer* defer_of(uocr_ctx* ctx) { return (GemmDefer*)ctx->gemm_defer; }
 
+int defer_flush(uocr_ctx* ctx);
+
+// the bytes an epilogue writes: rows [0, split_row or M) of c, and N floats of c2 (conv dw: db, which the caller also
+// zeroes when there is no bias row)
+struct ByteRange {
+    uintptr_t lo, hi;
+};
+inline bool overlaps(ByteRange a, ByteRange b) { return a.lo < b.hi && b.lo < a.hi; }
+inline ByteRange c_range(const Epilogue& ep, int M, int N) {
+    const int rows = ep.split_row >= 0 ? ep.split_row : M;
+    const uintptr_t lo = (uintptr_t)ep.c;
+    return ByteRange{lo, rows > 0 ? lo + ((size_t)(rows - 1) * ep.ldc + N) * sizeof(float) : lo};
+}
+inline ByteRange c2_range(const Epilogue& ep, int N) {
+    const uintptr_t lo = (uintptr_t)ep.c2;
+    return ByteRange{lo, ep.c2 ? lo + (size_t)N * sizeof(float) : lo};
+}
+
 // true: recorded (the caller returns UOCR_OK without launching)
 template <typename ALoader>
 bool defer_record(uocr_ctx* ctx, const ALoader& A, const BRowMajor& B, const Epilogue& ep, int M, int N, int depth) {
     GemmDefer* d = defer_of(ctx);
-    if (!d || !d->on || d->count >= GROUP_MAX) return false;
-    constexpr bool conv = std::is_same<ALoader, AConvWgrad>::value;
-    if ((conv ? d->nconv : d->ncol) >= GROUP_MAX_TYPE) return false;
+    if (!d || !d->on) return false;
     // only the small problems (64-row tiles, few of them) gain from sharing a launch
     const long tiles = (long)((M + 63) / 64) * ((N + BN - 1) / BN);
     if (tiles >= 2L * ctx->cu_count || (size_t)M * N * sizeof(float) * 2 > ws_half(ctx)) return false;
+    // the problems of a group run at the same time, and an epilogue's `*dst = *dst + v` is no atomic: a problem that
+    // writes where a recorded one writes (two calls accumulating into one dw) waits for those to be flushed
+    const ByteRange mc = c_range(ep, M, N), mc2 = c2_range(ep, N);
+    for (int q = 0; q < d->count; ++q) {
+        const GroupShape& o = d->args.shape[q];
+        const ByteRange oc = c_range(o.ep, o.M, o.N), oc2 = c2_range(o.ep, o.N);
+        if (overlaps(mc, oc) || overlaps(mc, oc2) || overlaps(mc2, oc) || overlaps(mc2, oc2)) {
+            if (defer_flush(ctx) != UOCR_OK) return false;
+            break;
+        }
+    }
+    if (d->count >= GROUP_MAX) return false;
+    constexpr bool conv = std::is_same<ALoader, AConvWgrad>::value;
+    if ((conv ? d->nconv : d->ncol) >= GROUP_MAX_TYPE) return false;
     const int p = d->count++;
     GroupArgs& g = d->args;
     g.type[p] = conv ? 0 : 1;
@@ -926,6 +960,13 @@ int defer_flush(uocr_ctx* ctx) {
             r.ep[q] = sh.ep;
         }
     }
+    int max_split = 1;
+    for (int p = 0; p < g.count; ++p) max_split = std::max(max_split, g.shape[p].gz);
+    ctx->gemm_bm = 64;
+    ctx->gemm_gm = ctx->gemm_gn = 0;
+    ctx->gemm_nsplit = max_split;
+    ctx->gemm_group_count = g.count;
+    ctx->gemm_group_split = r.count;
     hipLaunchKernelGGL(mfma_gemm_group_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, g);
     UOCR_LAUNCH_CHECK(ctx);
     if (r.count > 0) {

@@ -40,6 +40,8 @@ struct uocr_ctx {
     int opt_max_blocks;  // k > 0 lowers every run-time block budget to k (tests: several tiles per block at small shapes)
     int split_blocks;    // uocr_ctx_last_split: blocks and work items of the last launch with a run-time split
     long long split_items;
+    int gemm_bm, gemm_gm, gemm_gn, gemm_nsplit;   // uocr_ctx_last_gemm: row tile, output-tile grid, slabs of the last MFMA GEMM
+    int gemm_group_count, gemm_group_split;      // uocr_ctx_last_gemm_group: problems / split problems of the last group flush
     char err[512];
 };
 

@@ -52,6 +52,8 @@ _PROTOS = {
     'uocr_ctx_reserve_workspace': [_ctx, _sz],
     'uocr_ctx_set_option': [_ctx, C.c_char_p, _i],
     'uocr_ctx_last_split': [_ctx, C.POINTER(_i), C.POINTER(C.c_longlong)],
+    'uocr_ctx_last_gemm': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
+    'uocr_ctx_last_gemm_group': [_ctx, C.POINTER(_i), C.POINTER(_i)],
     'uocr_malloc': [_ctx, _sz, C.POINTER(_vp)],
     'uocr_free': [_ctx, _vp],
     'uocr_memset_zero': [_ctx, _vp, _sz],

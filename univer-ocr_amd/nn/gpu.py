@@ -138,6 +138,21 @@ class Runtime:
         self.call('uocr_ctx_last_split', C.byref(blocks), C.byref(items))
         return blocks.value, items.value
 
+    def last_gemm(self):
+        """(row tile, row tiles, column tiles, depth slabs) of the most recent float32 MFMA GEMM on the current lane
+        (uocr_ctx_last_gemm); a deferred weight-gradient group flush reports (64, 0, 0, its largest split)."""
+        import ctypes as C
+        v = [C.c_int() for _ in range(4)]
+        self.call('uocr_ctx_last_gemm', *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
+    def last_gemm_group(self):
+        """(problems, split problems) of the most recent deferred weight-gradient group flush on the current lane."""
+        import ctypes as C
+        problems, split = C.c_int(), C.c_int()
+        self.call('uocr_ctx_last_gemm_group', C.byref(problems), C.byref(split))
+        return problems.value, split.value
+
     def set_loss_snapshot(self, arena):
         """From now on the fused optimizer tails launched on the CURRENT lane end by copying `arena`'s slots into the next
         row of its ring (LossArena.arm); None switches it off."""
