@@ -35,6 +35,16 @@ struct MapArgs {
     const TS* in[NIN];
 };
 
+// conversion of a functor's result to the storage type.  A functor that multiplies by a 0 / 1 mask says so
+// (`mask_multiply`): for binary16 storage its result is made opaque first -- hipcc otherwise fuses the multiply with
+// the conversion into v_fma_mixlo_f16 x, m, +0, and (-0) + (+0) = +0: the Relu of a negative binary16 value came out
+// as +0.0 where x * mask is -0.0 (NumPy, and the float32 / float64 kernels)
+template <typename TS, typename T, typename Op>
+__device__ __forceinline__ TS map_store(T v) {
+    if constexpr (!std::is_same<TS, T>::value && requires { Op::mask_multiply; }) asm volatile("" : "+v"(v));
+    return (TS)v;
+}
+
 template <typename TS, typename T, int NIN, int V, typename Op>
 __global__ __launch_bounds__(256) void map_kernel(MapArgs<TS, NIN> a, size_t n, Op op) {
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -50,7 +60,7 @@ __global__ __launch_bounds__(256) void map_kernel(MapArgs<TS, NIN> a, size_t n, 
             T args[NIN];
 #pragma unroll
             for (int k = 0; k < NIN; ++k) args[k] = (T)x[k].v[j];
-            r.v[j] = (TS)op(args);
+            r.v[j] = map_store<TS, T, Op>(op(args));
         }
         *reinterpret_cast<Pack<TS, V>*>(a.out + i * V) = r;
     }
@@ -58,7 +68,7 @@ __global__ __launch_bounds__(256) void map_kernel(MapArgs<TS, NIN> a, size_t n, 
         T args[NIN];
 #pragma unroll
         for (int k = 0; k < NIN; ++k) args[k] = (T)a.in[k][i];
-        a.out[i] = (TS)op(args);
+        a.out[i] = map_store<TS, T, Op>(op(args));
     }
 }
 
@@ -89,10 +99,12 @@ __device__ __forceinline__ double dev_exp<double>(double x) { return exp(x); }
 // mask = (x >= 0) [+ alpha * (x < 0)], y = x * mask: NaN and -0.0 behave as in NumPy.
 template <typename T>
 struct ReluFwd {
+    static constexpr bool mask_multiply = true;
     __device__ T operator()(const T* a) const { return a[0] * (a[0] >= T(0) ? T(1) : T(0)); }
 };
 template <typename T>
 struct LeakyFwd {
+    static constexpr bool mask_multiply = true;
     T alpha;
     __device__ T operator()(const T* a) const {
         const T m = (a[0] >= T(0) ? T(1) : T(0)) + alpha * (a[0] < T(0) ? T(1) : T(0));
@@ -106,10 +118,12 @@ struct SigmoidFwd {
 // backward: args = {x (stashed input), dy}
 template <typename T>
 struct ReluBwd {
+    static constexpr bool mask_multiply = true;
     __device__ T operator()(const T* a) const { return a[1] * (a[0] >= T(0) ? T(1) : T(0)); }
 };
 template <typename T>
 struct LeakyBwd {
+    static constexpr bool mask_multiply = true;
     T alpha;
     __device__ T operator()(const T* a) const {
         const T m = (a[0] >= T(0) ? T(1) : T(0)) + alpha * (a[0] < T(0) ? T(1) : T(0));
@@ -354,6 +368,12 @@ __device__ __forceinline__ void loss_snapshot(const LossSnapshot& s) {
     for (int i = 0; i < s.count; ++i) s.ring[(size_t)k * s.count + i] = s.src[i];
 }
 
+// With regulariser ranges the last block to arrive adds the partial rows of all blocks, OPT_FUSED_SUM_TRIPS rows per
+// thread: the launcher's block cap for that case must stay within what 256 threads cover.
+constexpr unsigned OPT_FUSED_REG_GRID = 256;
+constexpr int OPT_FUSED_SUM_TRIPS = 4;
+static_assert(OPT_FUSED_REG_GRID <= 256u * OPT_FUSED_SUM_TRIPS, "the last block of opt_fused_kernel would skip partial rows");
+
 template <typename T, int OPT, int VEC>
 __global__ __launch_bounds__(256) void opt_fused_kernel(T* __restrict__ w, T* __restrict__ g, T* __restrict__ s1,
                                                         T* __restrict__ s2, size_t n, T p0, T p1, T p2, T p3,
@@ -439,16 +459,16 @@ __global__ __launch_bounds__(256) void opt_fused_kernel(T* __restrict__ w, T* __
     __shared__ double red[16];
     double a[4] = {0.0, 0.0, 0.0, 0.0};
     {
-        double t[4][4];
+        double t[OPT_FUSED_SUM_TRIPS][4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
+        for (int k = 0; k < OPT_FUSED_SUM_TRIPS; ++k)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int i = threadIdx.x + 256 * k;
                 t[k][r] = (i < (int)gridDim.x && r < rr.n) ? pub_load(partial + (size_t)i * 4 + r) : 0.0;
             }
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
+        for (int k = 0; k < OPT_FUSED_SUM_TRIPS; ++k)
 #pragma unroll
             for (int r = 0; r < 4; ++r) a[r] += t[k][r];
     }
@@ -733,7 +753,7 @@ static int launch_opt_fused(uocr_ctx* ctx, int dtype, int opt, void* w, void* g,
     // with regulariser sums every block ends in a ticket on ONE counter (same-address atomics are served one after the other)
     // and the last one adds all partials: a block per CU (802 k parameters, 3 ranges: 35.9 us at 784 blocks, 32.5 at 512,
     // 30.2 at 256, 29.9 at 128 -- of which ~18 us are the benchmark's own loss-slot launches)
-    const unsigned grid = uocr_blocks_for(vec ? (count + 3) / 4 : count, 256, nranges > 0 ? 256u : 1024u);
+    const unsigned grid = uocr_blocks_for(vec ? (count + 3) / 4 : count, 256, nranges > 0 ? OPT_FUSED_REG_GRID : 1024u);
     int rc = uocr_need_workspace(ctx, (size_t)grid * 4 * sizeof(double));
     if (rc) return rc;
     double* partial = (double*)ctx->workspace;
