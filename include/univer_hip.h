@@ -87,8 +87,11 @@ void* uocr_ctx_get_stream(uocr_ctx* ctx);
  * stride-2 5x5 convolutions -- the default library contains bit 2 only, the others need a library built with
  * UOCR_BUILD_EXPERIMENTS=1 ./build.sh and are refused with UOCR_ERR_UNSUPPORTED otherwise; likewise "h3" = 1, the
  * float32 Line output conv forward on error-compensated binary16 MFMAs); the Monochrome pair kernels:
- * "pair_band" (rows per band, 0 auto), "pair_g" (4 / 2 groups of 16 columns per wave), "pair_pf" (row prefetch form
- * of the forward kernels, -1 auto); "wgrad_bands" (row bands per tap / channel group of the direct weight-gradient
+ * "pair_band" (rows per band, 0 auto; every pair entry point), "pair_g" (4 / 2 groups of 16 columns per wave: honoured
+ * by the float32 backward and by the binary16 backward of pages wider than 512 columns; both forwards and the binary16
+ * backward up to 512 columns always run 4), "pair_pf" (row prefetch form of the two forward kernels, ignored by the
+ * backward kernels: 0 / 1 / 2, -1 auto = form 1 in float32 and form 2 in binary16; any other value is taken as auto);
+ * "wgrad_bands" (row bands per tap / channel group of the direct weight-gradient
  * kernels, 0 = 64 or 512 by the kernel's accumulator count); "max_blocks" (k > 0 lowers every block budget that is
  * decided at run time -- persistent tile walks, rows or tiles per block -- to k, so that small shapes make blocks walk
  * several tiles; it never raises one; 0 = the budgets as they are).  Results do not depend on any of them beyond float32
@@ -104,6 +107,16 @@ int uocr_ctx_last_split(uocr_ctx* ctx, int* blocks, long long* items);
  * them were split.  All 0 before the first. */
 int uocr_ctx_last_gemm(uocr_ctx* ctx, int* bm, int* gm, int* gn, int* nsplit);
 int uocr_ctx_last_gemm_group(uocr_ctx* ctx, int* problems, int* split_problems);
+/* the most recent Monochrome pair launch accepted on this ctx (uocr_conv_pair_fwd / uocr_conv_pair_bwd on the strip
+ * kernels; "pair_band", "pair_g", "pair_pf" steer it).  kernel: 1 float32 forward, 2 float32 backward, 3 binary16 forward,
+ * 4 binary16 backward as one cooperative block per band (pages up to 512 columns), 5 binary16 backward on independent
+ * waves; g: groups of 16 columns per wave that ran (4 / 2); mode: the masking form the host chose (0 = no position is
+ * ever masked, 1 = per-position selects; 0 for kernels 3 and 5, which decide per wave); pf: the prefetch form that ran
+ * (0 for the backward kernels); nw: waves per block; blocks_x x bands: the grid per image (column blocks, or blocks of
+ * up to four strips, by row bands); band_h: rows per band.  A call that is refused leaves them as they were.  All 0
+ * before the first. */
+int uocr_ctx_last_pair(uocr_ctx* ctx, int* kernel, int* g, int* mode, int* pf, int* nw, int* blocks_x, int* bands,
+                       int* band_h);
 int uocr_ctx_reserve_workspace(uocr_ctx* ctx, size_t bytes);   /* synchronises; not capturable */
 const char* uocr_last_error(uocr_ctx* ctx);
 int uocr_malloc(uocr_ctx* ctx, size_t bytes, void** out);                       /* cupy.zeros/asarray */

@@ -651,6 +651,7 @@ int strip_bwd_launch(uocr_ctx* ctx, const float* x, const float* y, const float*
         return UOCR_OK;
     };
     const bool plain = nbx == 1 && w == bwc && pad1 == 0.f;      // MODE 0: no position is ever masked
+    uocr_note_pair(ctx, 2, G, plain ? 0 : 1, 0, nw, nbx, bands, band_h);
     auto pick = [&](auto dxtag, auto sigtag) -> int {
         constexpr bool D = decltype(dxtag)::value, S = decltype(sigtag)::value;
         return plain ? launch(pair_strip_bwd_kernel<G, D, S, 0>) : launch(pair_strip_bwd_kernel<G, D, S, 1>);
@@ -690,6 +691,8 @@ int uocr_pair_strip_fwd_f32(uocr_ctx* ctx, const float* x, const float* w1, cons
     UOCR_REQUIRE(ctx, bands <= 65535 && n <= 65535);
     const size_t lds = sizeof(float) * NSLOT * NPLANE * (bwc + 16);
     const bool plain = nbx == 1 && w == bwc && pad1 == 0.f;
+    uocr_note_pair(ctx, 1, G, plain ? 0 : 1, ctx->opt_pair_pf == 0 ? 0 : ctx->opt_pair_pf == 2 ? 2 : 1, nw, nbx, bands,
+                   band_h);
     auto go = [&](auto mode, auto pf) {
         hipLaunchKernelGGL((pair_strip_fwd_kernel<G, decltype(mode)::value, decltype(pf)::value>), dim3(nbx, bands, n),
                            dim3(nw * 64), lds, ctx->stream, x, w1, b1, w2, b2, y, h, w, band_h, pad1, use_b1, use_b2, alpha,

@@ -954,6 +954,7 @@ int uocr_pair_strip_fwd_f16(uocr_ctx* ctx, const void* x, const float* w1, const
     bands = (h + band_h - 1) / band_h;
     UOCR_REQUIRE(ctx, bands <= 65535 && n <= 65535);
     const size_t lds = sizeof(float) * nw * 3 * NPLANE * (COLS + 2);
+    uocr_note_pair(ctx, 3, G, 0, ctx->opt_pair_pf == 0 ? 0 : ctx->opt_pair_pf == 1 ? 1 : 2, nw, blocks_x, bands, band_h);
     auto go = [&](auto pf) {
         hipLaunchKernelGGL((pair_wave_fwd_h_kernel<G, decltype(pf)::value>), dim3(blocks_x, bands, n), dim3(nw * 64), lds,
                            ctx->stream, (const _Float16*)x, w1, b1, w2, b2, (_Float16*)y, h, w, band_h, pad1, use_b1,
@@ -1000,6 +1001,7 @@ int wave_bwd_launch(uocr_ctx* ctx, const void* x, const void* y, const void* dy,
     int rc = UOCR_OK;
     float* partial = uocr_partial_buffer(ctx, nblocks * PAIR_NPART * sizeof(float), &rc);
     if (rc != UOCR_OK) return rc;
+    uocr_note_pair(ctx, 5, G, 0, 0, nw, blocks_x, bands, band_h);
     auto run = [&](auto dxtag, auto sigtag) -> int {
         constexpr bool D = decltype(dxtag)::value, S = decltype(sigtag)::value;
         static bool attr_set = false;
@@ -1065,6 +1067,7 @@ int uocr_pair_strip_bwd_f16(uocr_ctx* ctx, const void* x, const void* y, const v
         return UOCR_OK;
     };
     const bool plain = w == bwc && pad1 == 0.f;
+    uocr_note_pair(ctx, 4, G, plain ? 0 : 1, 0, nw, 1, bands, band_h);
     auto run = [&](auto dxtag, auto sigtag) -> int {
         constexpr bool D = decltype(dxtag)::value, S = decltype(sigtag)::value;
         return plain ? launch(pair_strip_bwd_h_kernel<G, D, S, 0>) : launch(pair_strip_bwd_h_kernel<G, D, S, 1>);

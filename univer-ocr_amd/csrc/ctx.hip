@@ -50,6 +50,7 @@ int uocr_ctx_create(int device, size_t workspace_bytes, uocr_ctx** out) {
     ctx->split_items = 0;
     ctx->gemm_bm = ctx->gemm_gm = ctx->gemm_gn = ctx->gemm_nsplit = 0;
     ctx->gemm_group_count = ctx->gemm_group_split = 0;
+    uocr_note_pair(ctx, 0, 0, 0, 0, 0, 0, 0, 0);
     ctx->opt_h3 = 0;
 #ifdef UOCR_EXPERIMENTS
     if (const char* e = getenv("UOCR_H3")) ctx->opt_h3 = atoi(e);            // development override (tools/dev/h3_ab.sh)
@@ -186,6 +187,21 @@ int uocr_ctx_last_gemm_group(uocr_ctx* ctx, int* problems, int* split_problems) 
     UOCR_REQUIRE(ctx, problems && split_problems);
     *problems = ctx->gemm_group_count;
     *split_problems = ctx->gemm_group_split;
+    return UOCR_OK;
+}
+
+int uocr_ctx_last_pair(uocr_ctx* ctx, int* kernel, int* g, int* mode, int* pf, int* nw, int* blocks_x, int* bands,
+                       int* band_h) {
+    UOCR_CHECK_CTX(ctx);
+    UOCR_REQUIRE(ctx, kernel && g && mode && pf && nw && blocks_x && bands && band_h);
+    *kernel = ctx->pair_kernel;
+    *g = ctx->pair_g;
+    *mode = ctx->pair_mode;
+    *pf = ctx->pair_pf;
+    *nw = ctx->pair_nw;
+    *blocks_x = ctx->pair_blocks_x;
+    *bands = ctx->pair_bands;
+    *band_h = ctx->pair_band_h;
     return UOCR_OK;
 }
 

@@ -42,6 +42,8 @@ struct uocr_ctx {
     long long split_items;
     int gemm_bm, gemm_gm, gemm_gn, gemm_nsplit;   // uocr_ctx_last_gemm: row tile, output-tile grid, slabs of the last MFMA GEMM
     int gemm_group_count, gemm_group_split;      // uocr_ctx_last_gemm_group: problems / split problems of the last group flush
+    int pair_kernel, pair_g, pair_mode, pair_pf;  // uocr_ctx_last_pair: the form of the last Monochrome pair launch ...
+    int pair_nw, pair_blocks_x, pair_bands, pair_band_h;   // ... and its geometry (waves per block, grid x, grid y, rows per band)
     char err[512];
 };
 
@@ -143,6 +145,13 @@ static inline long uocr_budget(const uocr_ctx* ctx, long budget) {
 static inline void uocr_note_split(uocr_ctx* ctx, long long blocks, long long items) {
     ctx->split_blocks = (int)blocks;
     ctx->split_items = items;
+}
+
+// what a pair launch chose (uocr_ctx_last_pair; kernel 1-5 as in univer_hip.h), noted once the launch was accepted
+static inline void uocr_note_pair(uocr_ctx* ctx, int kernel, int g, int mode, int pf, int nw, int blocks_x, int bands,
+                                  int band_h) {
+    ctx->pair_kernel = kernel, ctx->pair_g = g, ctx->pair_mode = mode, ctx->pair_pf = pf;
+    ctx->pair_nw = nw, ctx->pair_blocks_x = blocks_x, ctx->pair_bands = bands, ctx->pair_band_h = band_h;
 }
 
 // grid cap for grid-stride HBM-bound kernels: 256 CUs x 8 blocks of 256 threads

@@ -54,6 +54,7 @@ _PROTOS = {
     'uocr_ctx_last_split': [_ctx, C.POINTER(_i), C.POINTER(C.c_longlong)],
     'uocr_ctx_last_gemm': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     'uocr_ctx_last_gemm_group': [_ctx, C.POINTER(_i), C.POINTER(_i)],
+    'uocr_ctx_last_pair': [_ctx] + [C.POINTER(_i)] * 8,
     'uocr_malloc': [_ctx, _sz, C.POINTER(_vp)],
     'uocr_free': [_ctx, _vp],
     'uocr_memset_zero': [_ctx, _vp, _sz],

@@ -153,6 +153,15 @@ class Runtime:
         self.call('uocr_ctx_last_gemm_group', C.byref(problems), C.byref(split))
         return problems.value, split.value
 
+    def last_pair(self):
+        """(kernel, g, mode, pf, waves per block, blocks_x, bands, band_h) of the most recent Monochrome pair launch
+        accepted on the current lane (uocr_ctx_last_pair): kernel 1 / 2 = float32 forward / backward, 3 = binary16
+        forward, 4 / 5 = binary16 backward as one cooperative block / on independent waves; all 0 before the first."""
+        import ctypes as C
+        v = [C.c_int() for _ in range(8)]
+        self.call('uocr_ctx_last_pair', *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
     def set_loss_snapshot(self, arena):
         """From now on the fused optimizer tails launched on the CURRENT lane end by copying `arena`'s slots into the next
         row of its ring (LossArena.arm); None switches it off."""
