@@ -117,6 +117,33 @@ int uocr_ctx_last_gemm_group(uocr_ctx* ctx, int* problems, int* split_problems);
  * before the first. */
 int uocr_ctx_last_pair(uocr_ctx* ctx, int* kernel, int* g, int* mode, int* pf, int* nw, int* blocks_x, int* bands,
                        int* band_h);
+/* the kernel family that took the most recent uocr_conv2d_* call accepted on this ctx ("fast_paths", "mfma", "tiled",
+ * "t32", "h16", "h3" and the alignment of the pointers steer the choice).  entry: 0 uocr_conv2d_fwd, 1 _bwd_data,
+ * 2 _bwd_weight; kernel: one of UOCR_CONV_* below.  A call that is refused leaves them as they were; a weight gradient
+ * recorded into a deferred group (uocr_wgrad_defer_begin) still notes its kernel.  Both 0 before the first. */
+enum {
+    UOCR_CONV_NONE = 0,
+    UOCR_CONV_GENERIC = 1,          /* conv.hip: any shape, any dtype */
+    UOCR_CONV_MFMA = 2,             /* gemm_mfma.hip: float32 implicit GEMM */
+    UOCR_CONV_H16 = 3,              /* conv_h16.hip: binary16-MFMA forward / backward-data */
+    UOCR_CONV_H16_WGRAD = 4,        /* conv_h16w.hip: ... weight gradient of the stride-1 5x5 convs */
+    UOCR_CONV_H16_WGRAD_S2 = 5,     /* conv_h16w.hip: ... of the stride-2 5x5 convs */
+    UOCR_CONV_T32 = 6,              /* conv_t32.hip: float32 vertical-Toeplitz MFMA forward / backward-data */
+    UOCR_CONV_T32_WGRAD = 7,        /* conv_t32w.hip: ... weight gradients */
+    UOCR_CONV_H3 = 8,               /* conv_h3.hip: float32 4 -> 2 forward on error-compensated binary16 MFMAs */
+    UOCR_CONV_TILED = 9,            /* conv_tiled.hip: LDS-tiled forward of the stride-1 4-channel 5x5 convs */
+    UOCR_CONV_C16_EXPAND = 10,      /* conv_fast.hip, quad-lane 3x3 kernels: 1 -> 16 forward, 16 -> 1 backward-data */
+    UOCR_CONV_C16_REDUCE = 11,      /* ... 16 -> 1 forward, 1 -> 16 backward-data */
+    UOCR_CONV_C16_WGRAD = 12,       /* ... weight gradient of the 16 -> 1 conv */
+    UOCR_CONV_DGRAD_S2 = 13,        /* conv_fast.hip: backward-data of the 5x5 / stride 2 / padding 2 convs */
+    UOCR_CONV_DGRAD_C64S2 = 14,     /* conv_fast.hip: backward-data of the 5x3 / stride (2,1) / padding (0,1) 1 -> 64 conv */
+    UOCR_CONV_WGRAD_T542 = 15,      /* conv_fast.hip: LDS-tiled weight gradient of the 5x5 4 -> 2 conv */
+    UOCR_CONV_WGRAD_S2_TILED = 16,  /* conv_fast.hip: LDS-tiled weight gradient of the 5x5 / stride 2 1 -> 4 conv */
+    UOCR_CONV_TABLE_FAST = 17,      /* conv_fast.hip, the nine table configurations: conv_fwd_fast / conv_dgrad_fast /
+                                     * conv_wgrad_fast */
+    UOCR_CONV_TABLE_PX = 18         /* ... their row-loop forms conv_fwd_px / conv_dgrad_px */
+};
+int uocr_ctx_last_conv(uocr_ctx* ctx, int* entry, int* kernel);
 int uocr_ctx_reserve_workspace(uocr_ctx* ctx, size_t bytes);   /* synchronises; not capturable */
 const char* uocr_last_error(uocr_ctx* ctx);
 int uocr_malloc(uocr_ctx* ctx, size_t bytes, void** out);                       /* cupy.zeros/asarray */
@@ -173,7 +200,9 @@ int uocr_device_info(uocr_ctx* ctx, char* name_out, size_t name_cap, int* cu_cou
 /* y[b,oy,ox,:] = sum_{ky,kx,ic} x~[b,oy*sh-ph+ky,ox*sw-pw+kx,ic] * w[ky,kx,ic,:] (+ b if use_bias),
  * x~ = x inside, pad_value outside (convolutional.py:62-99; GPU kernel :153-195).  OH/OW follow
  * convolutional.py:290-301 and are passed explicitly.  `act` fuses a following activation layer
- * (UOCR_ACT_NONE = plain conv). */
+ * (UOCR_ACT_NONE = plain conv).  The shape-specialised kernels of conv_fast.hip's table are selected by kernel size,
+ * channels and stride only: padding and pad_value are unrestricted for them (the kernels that shadow them at the nets'
+ * own padding are not chosen at any other; uocr_ctx_last_conv tells which one ran). */
 int uocr_conv2d_fwd(uocr_ctx* ctx, int dtype, const void* x, const void* w, const void* b, void* y,
                     int n, int h, int wd, int cin, int cout, int kh, int kw, int sh, int sw,
                     int ph, int pw, int oh, int ow, double pad_value, int use_bias,

@@ -30,18 +30,24 @@ int uocr_conv2d_fwd(uocr_ctx* ctx, int dtype, const void* x, const void* w, cons
     UOCR_REQUIRE(ctx, x && w && y && (b || !use_bias));
     UOCR_REQUIRE(ctx, act >= UOCR_ACT_NONE && act <= UOCR_ACT_SIGMOID);
     if (uocr_conv_h16_eligible(ctx, dtype, d, 0) && uocr_aligned_act(x, dtype) && uocr_aligned_act(y, dtype))
-        return uocr_conv_fwd_h16(ctx, x, w, b, y, d, pad_value, use_bias, act, act_alpha);
+        return uocr_noted_conv(ctx, 0, UOCR_CONV_H16,
+                               uocr_conv_fwd_h16(ctx, x, w, b, y, d, pad_value, use_bias, act, act_alpha));
     if (uocr_conv_t32_eligible(ctx, dtype, d, 0) && aligned16(x) && aligned16(y))
-        return uocr_conv_fwd_t32(ctx, x, w, b, y, d, pad_value, use_bias, act, act_alpha);
+        return uocr_noted_conv(ctx, 0, UOCR_CONV_T32,
+                               uocr_conv_fwd_t32(ctx, x, w, b, y, d, pad_value, use_bias, act, act_alpha));
     if (uocr_conv_h3_eligible(ctx, dtype, d) && aligned16(x) && aligned16(y))
-        return uocr_conv_fwd_h3(ctx, x, w, b, y, d, pad_value, use_bias, act, act_alpha);
+        return uocr_noted_conv(ctx, 0, UOCR_CONV_H3,
+                               uocr_conv_fwd_h3(ctx, x, w, b, y, d, pad_value, use_bias, act, act_alpha));
     if (uocr_conv_tiled_eligible(ctx, dtype, d) && uocr_aligned_act(x, dtype) && uocr_aligned_act(y, dtype))
-        return uocr_conv_fwd_tiled(ctx, dtype, x, w, b, y, d, pad_value, use_bias, act, act_alpha);
+        return uocr_noted_conv(ctx, 0, UOCR_CONV_TILED,
+                               uocr_conv_fwd_tiled(ctx, dtype, x, w, b, y, d, pad_value, use_bias, act, act_alpha));
     if (uocr_conv_fast_eligible(ctx, dtype, d, x, y, w))
         return uocr_conv_fwd_fast(ctx, dtype, x, w, b, y, d, pad_value, use_bias, act, act_alpha);
     if (uocr_conv_mfma_eligible(ctx, dtype, d, 0))
-        return uocr_conv_fwd_mfma(ctx, x, w, b, y, d, pad_value, use_bias, act, act_alpha);
-    return uocr_conv_fwd_generic(ctx, dtype, x, w, b, y, d, pad_value, use_bias, act, act_alpha);
+        return uocr_noted_conv(ctx, 0, UOCR_CONV_MFMA,
+                               uocr_conv_fwd_mfma(ctx, x, w, b, y, d, pad_value, use_bias, act, act_alpha));
+    return uocr_noted_conv(ctx, 0, UOCR_CONV_GENERIC,
+                           uocr_conv_fwd_generic(ctx, dtype, x, w, b, y, d, pad_value, use_bias, act, act_alpha));
 }
 
 int uocr_conv2d_bwd_data(uocr_ctx* ctx, int dtype, const void* dy, const void* w, void* dx, int n, int h, int wd,
@@ -56,12 +62,13 @@ int uocr_conv2d_bwd_data(uocr_ctx* ctx, int dtype, const void* dy, const void* w
     const ActMask mask{act == UOCR_ACT_NONE ? nullptr : x_act, act, act_alpha};
     if (uocr_conv_h16_eligible(ctx, dtype, d, 1) && uocr_aligned_act(dy, dtype) && uocr_aligned_act(dx, dtype) &&
         (!mask.y || uocr_aligned_act(mask.y, dtype)))
-        return uocr_conv_dgrad_h16(ctx, dy, w, dx, d, mask);
+        return uocr_noted_conv(ctx, 1, UOCR_CONV_H16, uocr_conv_dgrad_h16(ctx, dy, w, dx, d, mask));
     if (uocr_conv_t32_eligible(ctx, dtype, d, 1) && aligned16(dy) && aligned16(dx) && (!mask.y || aligned16(mask.y)))
-        return uocr_conv_dgrad_t32(ctx, dy, w, dx, d, mask);
+        return uocr_noted_conv(ctx, 1, UOCR_CONV_T32, uocr_conv_dgrad_t32(ctx, dy, w, dx, d, mask));
     if (uocr_conv_fast_eligible(ctx, dtype, d, dy, dx, w)) return uocr_conv_dgrad_fast(ctx, dtype, dy, w, dx, d, mask);
-    if (uocr_conv_mfma_eligible(ctx, dtype, d, 1)) return uocr_conv_dgrad_mfma(ctx, dy, w, dx, d, mask);
-    return uocr_conv_dgrad_generic(ctx, dtype, dy, w, dx, d, mask);
+    if (uocr_conv_mfma_eligible(ctx, dtype, d, 1))
+        return uocr_noted_conv(ctx, 1, UOCR_CONV_MFMA, uocr_conv_dgrad_mfma(ctx, dy, w, dx, d, mask));
+    return uocr_noted_conv(ctx, 1, UOCR_CONV_GENERIC, uocr_conv_dgrad_generic(ctx, dtype, dy, w, dx, d, mask));
 }
 
 int uocr_conv2d_bwd_weight(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw, void* db, int n, int h,
@@ -73,16 +80,21 @@ int uocr_conv2d_bwd_weight(uocr_ctx* ctx, int dtype, const void* x, const void* 
     if (rc) return rc;
     UOCR_REQUIRE(ctx, x && dy && dw && db);
     if (uocr_conv_wgrad_h16_eligible(ctx, dtype, d) && uocr_aligned_act(x, dtype) && uocr_aligned_act(dy, dtype))
-        return uocr_conv_wgrad_h16(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate);
+        return uocr_noted_conv(ctx, 2, UOCR_CONV_H16_WGRAD,
+                               uocr_conv_wgrad_h16(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate));
     if (uocr_conv_wgrad_t32_eligible(ctx, dtype, d) && aligned16(x) && aligned16(dy))
-        return uocr_conv_wgrad_t32(ctx, x, dy, dw, db, d, pad_value, use_bias, accumulate);
+        return uocr_noted_conv(ctx, 2, UOCR_CONV_T32_WGRAD,
+                               uocr_conv_wgrad_t32(ctx, x, dy, dw, db, d, pad_value, use_bias, accumulate));
     if (uocr_conv_wgrad_s2_h16_eligible(ctx, dtype, d) && uocr_aligned_act(x, dtype) && uocr_aligned_act(dy, dtype))
-        return uocr_conv_wgrad_s2_h16(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate);
+        return uocr_noted_conv(ctx, 2, UOCR_CONV_H16_WGRAD_S2,
+                               uocr_conv_wgrad_s2_h16(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate));
     if (uocr_conv_fast_eligible(ctx, dtype, d, x, dy, dw))
         return uocr_conv_wgrad_fast(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate);
     if (uocr_conv_mfma_eligible(ctx, dtype, d, 2))
-        return uocr_conv_wgrad_mfma(ctx, x, dy, dw, db, d, pad_value, use_bias, accumulate);
-    return uocr_conv_wgrad_generic(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate);
+        return uocr_noted_conv(ctx, 2, UOCR_CONV_MFMA,
+                               uocr_conv_wgrad_mfma(ctx, x, dy, dw, db, d, pad_value, use_bias, accumulate));
+    return uocr_noted_conv(ctx, 2, UOCR_CONV_GENERIC,
+                           uocr_conv_wgrad_generic(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate));
 }
 
 }  // extern "C"

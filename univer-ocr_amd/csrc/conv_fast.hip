@@ -1351,6 +1351,7 @@ int uocr_conv_fwd_fast(uocr_ctx* ctx, int dtype, const void* x, const void* w, c
                            (const float*)w, (const float*)b, (float*)y, d.n, d.h, d.w, d.ph, d.pw, (float)pad_value,
                            use_bias, act, (float)act_alpha, (const float*)nullptr, (int)UOCR_ACT_NONE, 0.f);
         UOCR_LAUNCH_CHECK(ctx);
+        uocr_note_conv(ctx, 0, UOCR_CONV_C16_EXPAND);
         return UOCR_OK;
     }
     if (f32 && is_c16_same(d, 16, 1)) {
@@ -1360,12 +1361,14 @@ int uocr_conv_fwd_fast(uocr_ctx* ctx, int dtype, const void* x, const void* w, c
                            (const float*)w, (const float*)b, (float*)y, d.n, d.h, d.w, d.ph, d.pw, (float)pad_value,
                            use_bias, act, (float)act_alpha, (const float*)nullptr, (int)UOCR_ACT_NONE, 0.f);
         UOCR_LAUNCH_CHECK(ctx);
+        uocr_note_conv(ctx, 0, UOCR_CONV_C16_REDUCE);
         return UOCR_OK;
     }
 #define X(KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX)                        \
     if (FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::match(d))      \
-        return FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::fwd(ctx, dtype, x, w, b, y, d, pad_value, use_bias, act, \
-                                                                        act_alpha);
+        return uocr_noted_conv(ctx, 0, FPX > 0 ? UOCR_CONV_TABLE_PX : UOCR_CONV_TABLE_FAST,                                       \
+                               FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::fwd(                  \
+                                   ctx, dtype, x, w, b, y, d, pad_value, use_bias, act, act_alpha));
     UOCR_FAST_CONVS(X)
 #undef X
     UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "no fast conv kernel for this shape");
@@ -1381,6 +1384,7 @@ int uocr_conv_dgrad_fast(uocr_ctx* ctx, int dtype, const void* dy, const void* w
                            (const float*)w, (const float*)nullptr, (float*)dx, d.n, d.h, d.w, d.ph, d.pw, 0.f, 0,
                            (int)UOCR_ACT_NONE, 0.f, (const float*)mask.y, mask.act, (float)mask.alpha);
         UOCR_LAUNCH_CHECK(ctx);
+        uocr_note_conv(ctx, 1, UOCR_CONV_C16_EXPAND);
         return UOCR_OK;
     }
     if (f32 && is_c16_same(d, 1, 16)) {
@@ -1390,6 +1394,7 @@ int uocr_conv_dgrad_fast(uocr_ctx* ctx, int dtype, const void* dy, const void* w
                            (const float*)w, (const float*)nullptr, (float*)dx, d.n, d.h, d.w, d.ph, d.pw, 0.f, 0,
                            (int)UOCR_ACT_NONE, 0.f, (const float*)mask.y, mask.act, (float)mask.alpha);
         UOCR_LAUNCH_CHECK(ctx);
+        uocr_note_conv(ctx, 1, UOCR_CONV_C16_REDUCE);
         return UOCR_OK;
     }
     if (f32 && d.kh == 5 && d.kw == 3 && d.sh == 2 && d.sw == 1 && d.ph == 0 && d.pw == 1 && d.cin == 1 && d.cout == 64 &&
@@ -1398,6 +1403,7 @@ int uocr_conv_dgrad_fast(uocr_ctx* ctx, int dtype, const void* dy, const void* w
                            (const float*)dy, (const float*)w, (float*)dx, d.n, d.h, d.w, d.oh, d.ow,
                            (const float*)mask.y, mask.act, (float)mask.alpha);
         UOCR_LAUNCH_CHECK(ctx);
+        uocr_note_conv(ctx, 1, UOCR_CONV_DGRAD_C64S2);
         return UOCR_OK;
     }
     if (d.kh == 5 && d.kw == 5 && d.sh == 2 && d.sw == 2 && d.ph == 2 && d.pw == 2 &&
@@ -1414,11 +1420,14 @@ int uocr_conv_dgrad_fast(uocr_ctx* ctx, int dtype, const void* dy, const void* w
             else launch(conv_dgrad_s2<1, 4, TA>);
         });
         UOCR_LAUNCH_CHECK(ctx);
+        uocr_note_conv(ctx, 1, UOCR_CONV_DGRAD_S2);
         return UOCR_OK;
     }
 #define X(KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX)                   \
     if (FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::match(d)) \
-        return FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::dgrad(ctx, dtype, dy, w, dx, d, mask);
+        return uocr_noted_conv(ctx, 1, DPX > 0 ? UOCR_CONV_TABLE_PX : UOCR_CONV_TABLE_FAST,     \
+                               FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::dgrad( \
+                                   ctx, dtype, dy, w, dx, d, mask));
     UOCR_FAST_CONVS(X)
 #undef X
     UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "no fast conv kernel for this shape");
@@ -1444,13 +1453,15 @@ int uocr_conv_wgrad_fast(uocr_ctx* ctx, int dtype, const void* x, const void* dy
         hipLaunchKernelGGL((conv_c16_wgrad_finish<3, 3>), dim3(NA, 4), dim3(256), 0, ctx->stream,
                            (const float*)partial, (float*)dw, (float*)db, nblocks, use_bias, accumulate);
         UOCR_LAUNCH_CHECK(ctx);
+        uocr_note_conv(ctx, 2, UOCR_CONV_C16_WGRAD);
         return UOCR_OK;
     }
     if (d.kh == 5 && d.kw == 5 && d.sh == 2 && d.sw == 2 && d.ph == 2 && d.pw == 2 && ctx->opt_tiled == 1) {
         // (measured against conv_wgrad_fast on one box: 1 -> 4 20 vs 25 us; 1 -> 1 17 vs 15 and 4 -> 4 34 vs 29 us
         // lose -- too little work per staged tile -- and stay on the register kernels)
         if (d.cin == 1 && d.cout == 4)
-            return launch_wgrad_s2<1, 4>(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate);
+            return uocr_noted_conv(ctx, 2, UOCR_CONV_WGRAD_S2_TILED,
+                                   launch_wgrad_s2<1, 4>(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate));
     }
     if (d.kh == 5 && d.kw == 5 && d.cin == 4 && d.cout == 2 && d.sh == 1 && d.sw == 1 && d.ph == 2 && d.pw == 2) {
         const int tiles_x = (d.w + t542::TW - 1) / t542::TW, tiles_y = (d.h + t542::TH - 1) / t542::TH;
@@ -1479,16 +1490,18 @@ int uocr_conv_wgrad_fast(uocr_ctx* ctx, int dtype, const void* x, const void* dy
         fd.use_bias = use_bias, fd.accumulate = accumulate;
         fd.unscale = (float)uocr_grad_unscale(dtype);
         fd.p[0] = t542::NACC, fd.p[1] = 40, fd.p[2] = 2;
-        if (uocr_finish_defer(ctx, fd)) return UOCR_OK;
+        if (uocr_finish_defer(ctx, fd)) return uocr_noted_conv(ctx, 2, UOCR_CONV_WGRAD_T542, UOCR_OK);
         hipLaunchKernelGGL(conv_wgrad_t542_finish, dim3(202), dim3(256), 0, ctx->stream, (const float*)partial,
                            (float*)dw, (float*)db, nblocks, use_bias, accumulate, (float)uocr_grad_unscale(dtype));
         UOCR_LAUNCH_CHECK(ctx);
+        uocr_note_conv(ctx, 2, UOCR_CONV_WGRAD_T542);
         return UOCR_OK;
     }
 #define X(KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX)                   \
     if (FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::match(d)) \
-        return FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::wgrad(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, \
-                                                                          accumulate);
+        return uocr_noted_conv(ctx, 2, UOCR_CONV_TABLE_FAST,                                    \
+                               FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::wgrad( \
+                                   ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate));
     UOCR_FAST_CONVS(X)
 #undef X
     UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "no fast conv kernel for this shape");

@@ -51,6 +51,7 @@ int uocr_ctx_create(int device, size_t workspace_bytes, uocr_ctx** out) {
     ctx->gemm_bm = ctx->gemm_gm = ctx->gemm_gn = ctx->gemm_nsplit = 0;
     ctx->gemm_group_count = ctx->gemm_group_split = 0;
     uocr_note_pair(ctx, 0, 0, 0, 0, 0, 0, 0, 0);
+    uocr_note_conv(ctx, 0, UOCR_CONV_NONE);
     ctx->opt_h3 = 0;
 #ifdef UOCR_EXPERIMENTS
     if (const char* e = getenv("UOCR_H3")) ctx->opt_h3 = atoi(e);            // development override (tools/dev/h3_ab.sh)
@@ -202,6 +203,14 @@ int uocr_ctx_last_pair(uocr_ctx* ctx, int* kernel, int* g, int* mode, int* pf, i
     *blocks_x = ctx->pair_blocks_x;
     *bands = ctx->pair_bands;
     *band_h = ctx->pair_band_h;
+    return UOCR_OK;
+}
+
+int uocr_ctx_last_conv(uocr_ctx* ctx, int* entry, int* kernel) {
+    UOCR_CHECK_CTX(ctx);
+    UOCR_REQUIRE(ctx, entry && kernel);
+    *entry = ctx->conv_entry;
+    *kernel = ctx->conv_kernel;
     return UOCR_OK;
 }
 

@@ -44,6 +44,7 @@ struct uocr_ctx {
     int gemm_group_count, gemm_group_split;      // uocr_ctx_last_gemm_group: problems / split problems of the last group flush
     int pair_kernel, pair_g, pair_mode, pair_pf;  // uocr_ctx_last_pair: the form of the last Monochrome pair launch ...
     int pair_nw, pair_blocks_x, pair_bands, pair_band_h;   // ... and its geometry (waves per block, grid x, grid y, rows per band)
+    int conv_entry, conv_kernel;                  // uocr_ctx_last_conv: entry point and kernel family of the last accepted conv call
     char err[512];
 };
 
@@ -152,6 +153,16 @@ static inline void uocr_note_pair(uocr_ctx* ctx, int kernel, int g, int mode, in
                                   int band_h) {
     ctx->pair_kernel = kernel, ctx->pair_g = g, ctx->pair_mode = mode, ctx->pair_pf = pf;
     ctx->pair_nw = nw, ctx->pair_blocks_x = blocks_x, ctx->pair_bands = bands, ctx->pair_band_h = band_h;
+}
+
+// which kernel family took a uocr_conv2d_* call (uocr_ctx_last_conv; entry 0 fwd / 1 bwd_data / 2 bwd_weight, kernel =
+// UOCR_CONV_* of univer_hip.h), noted once the call was accepted: uocr_noted_conv passes a launcher's code through
+static inline void uocr_note_conv(uocr_ctx* ctx, int entry, int kernel) {
+    ctx->conv_entry = entry, ctx->conv_kernel = kernel;
+}
+static inline int uocr_noted_conv(uocr_ctx* ctx, int entry, int kernel, int rc) {
+    if (rc == UOCR_OK) uocr_note_conv(ctx, entry, kernel);
+    return rc;
 }
 
 // grid cap for grid-stride HBM-bound kernels: 256 CUs x 8 blocks of 256 threads

@@ -18,6 +18,10 @@ def f16_scaled(k):
     return F16 | (int(k) << 8)
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3
 LOSS_DICE, LOSS_JACCARD = 0, 1
+# UOCR_CONV_*: the kernel family uocr_ctx_last_conv reports (index = value)
+CONV_KERNELS = ('none', 'generic', 'mfma', 'h16', 'h16_wgrad', 'h16_wgrad_s2', 't32', 't32_wgrad', 'h3', 'tiled',
+                'c16_expand', 'c16_reduce', 'c16_wgrad', 'dgrad_s2', 'dgrad_c64s2', 'wgrad_t542', 'wgrad_s2_tiled',
+                'table_fast', 'table_px')
 
 
 class HipError(RuntimeError):
@@ -55,6 +59,7 @@ _PROTOS = {
     'uocr_ctx_last_gemm': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     'uocr_ctx_last_gemm_group': [_ctx, C.POINTER(_i), C.POINTER(_i)],
     'uocr_ctx_last_pair': [_ctx] + [C.POINTER(_i)] * 8,
+    'uocr_ctx_last_conv': [_ctx, C.POINTER(_i), C.POINTER(_i)],
     'uocr_malloc': [_ctx, _sz, C.POINTER(_vp)],
     'uocr_free': [_ctx, _vp],
     'uocr_memset_zero': [_ctx, _vp, _sz],

@@ -162,6 +162,15 @@ class Runtime:
         self.call('uocr_ctx_last_pair', *[C.byref(x) for x in v])
         return tuple(x.value for x in v)
 
+    def last_conv(self):
+        """(entry, kernel) of the most recent uocr_conv2d_* call accepted on the current lane (uocr_ctx_last_conv): entry
+        0 / 1 / 2 = forward / backward-data / backward-weight, kernel = a UOCR_CONV_* value (hip.lib.CONV_KERNELS names
+        them); (0, 0) before the first."""
+        import ctypes as C
+        entry, kernel = C.c_int(), C.c_int()
+        self.call('uocr_ctx_last_conv', C.byref(entry), C.byref(kernel))
+        return entry.value, kernel.value
+
     def set_loss_snapshot(self, arena):
         """From now on the fused optimizer tails launched on the CURRENT lane end by copying `arena`'s slots into the next
         row of its ring (LossArena.arm); None switches it off."""
