@@ -369,6 +369,36 @@ int uocr_rmsprop_step(uocr_ctx* ctx, int dtype, void* w, const void* g, void* a,
 /* *flag_out (int32, device) = 1 if any element is NaN else 0  (nan_weights, layers.py:139-140) */
 int uocr_has_nan(uocr_ctx* ctx, int dtype, const void* x, size_t count, int32_t* flag_out);
 
+/* ---- connected components and masked crops (interpreter/interpreter.py: the ParagraphCrop stage) ---------
+ * uocr_label_components replaces label_layer (interpreter.py:16-21: ndimage.label(layer > np.mean(layer))), the
+ * thresholds of :437-438 and :549 (0.5 * (mean + max)) and ndimage.find_objects / center_of_mass (:303, :36-39).
+ * x: (n, h, w, 1) in `dtype`; foreground is x > t with t chosen by thresh_mode (mean and max are float64 reductions over
+ * the WHOLE tensor; thresh_value is read for UOCR_THRESH_VALUE only).  Connectivity is scipy's default structure (four
+ * edge neighbours in the h-w plane).  Every image is labelled on its own: for n = 1 exactly the reference's result (its
+ * 4-D call would also join equal pixels of neighbouring images; its data path only has n = 1, datasets.py:18,39).
+ * labels: int32 (n, h, w), 0 = background, the components of image i numbered 1..count[i] in the order of their first
+ * pixel in row-major order (scipy's numbering).  table: int64 [n][max_components][8], entry k-1 of image i =
+ * {linear index of the component's first pixel, area, y0, y1, x0, x1, sum of y, sum of x} with half-open boxes equal to
+ * find_objects' slices (centre of mass = sums / area); entries past count[i] are zero.  count[i] is the true number of
+ * components even when it exceeds max_components: the table then holds the first max_components, the labels stay
+ * complete.  Scratch (one int32 per pixel and a little more) comes from the ctx workspace (UOCR_ERR_WORKSPACE).
+ * Integer atomics only: results are bit-identical run to run.  Asynchronous and capturable. */
+enum { UOCR_THRESH_MEAN = 0, UOCR_THRESH_MEAN_MAX = 1, UOCR_THRESH_VALUE = 2 };
+int uocr_label_components(uocr_ctx* ctx, int dtype, const void* x, int n, int h, int w, int thresh_mode,
+                          double thresh_value, int* labels, long long* table, int max_components, int* count);
+/* (image * mask)[:, ry, rx, :] of interpreter.py:304-308 followed by make_divisible_by's zero frame (my_model/model.py:
+ * 26-34) in one pass.  image: (n, h, w, c) in `dtype`, labels as written by uocr_label_components; the box [y0, y0 + ch)
+ * x [x0, x0 + cw) of image `image_index` is copied where labels == label_id and zeroed elsewhere, and placed in out
+ * (1, out_h, out_w, c) at row (out_h - ch) / 2, column (out_w - cw) / 2 -- where make_divisible_by puts it when out_h =
+ * ch + 16 - ch % 16; at (0, 0) when out has the box's size.  Every element of out is written (zero outside the box).
+ * UOCR_ERR_ARG for a box outside the image, out smaller than the box, image_index outside [0, n) or label_id < 1;
+ * nothing is written then. */
+int uocr_masked_crop(uocr_ctx* ctx, int dtype, const void* image, const int* labels, int n, int h, int w, int c,
+                     int image_index, int label_id, int y0, int x0, int ch, int cw, void* out, int out_h, int out_w);
+/* the tile (rows, columns) of the last uocr_label_components call on this ctx and the kernels it launched (all 0 before the
+ * first): tests size their images from it so that components cross tile borders */
+int uocr_ctx_last_label(uocr_ctx* ctx, int* tile_h, int* tile_w, int* launches);
+
 /* ---- data parallel over the GPUs of one node: RCCL over xGMI ------------------------------------
  * The reference has no multi-GPU path; BASELINE.json adds one to the step loop my_model/trainer.py:213-233
  * -> nn/model_system.py:104-118 -> nn/models.py:250-254: between compute_loss_and_gradients and update_grads

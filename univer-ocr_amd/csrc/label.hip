@@ -1,0 +1,536 @@
+// Connected-component labelling, component table and masked crop: the device form of the reference's ParagraphCrop
+// stage (interpreter/interpreter.py:16-21 label_layer, :303 ndimage.find_objects, :304-308 the masked crop) and of the
+// labelling every later stage starts with (:437-438, :549).
+//
+// Foreground is x > t; connectivity is scipy's default structure (the four edge neighbours in the H-W plane).  EVERY
+// IMAGE OF THE BATCH IS LABELLED ON ITS OWN: for N = 1 that is exactly what the reference computes; its 4-D
+// ndimage.label call would also join equal pixels of neighbouring images, but its data path only ever has N = 1
+// (my_model/datasets.py:18,39).  The components of an image are numbered 1..count in the order of their first pixel in
+// row-major order, which is scipy's numbering: the representative of a component is its minimum linear index and its
+// number is the rank of that root among the roots of its image.
+//
+// Launches of one uocr_label_components call, all on the context's stream (no grid barrier, nobody waits for another
+// block; every exchange between blocks inside a launch is an integer atomic on a word that only ever decreases):
+//   1. label_stats     float64 sum and max of x, the last block to arrive stores the threshold (not for THRESH_VALUE)
+//   2. label_local     union-find of one LTH x LTW tile in LDS (a pixel starts at the head of its row run, unions only
+//                      with the row above and once per pair of runs); writes the tile root's image-linear index, -1 =
+//                      background
+//   3. label_merge     unions across tile borders, one per pair of border runs: lock-free atomicMin retries on the plane
+//   4. label_flatten   root of every pixel into the second plane (workspace) + roots per chunk of LCHUNK pixels
+//   5. label_scan      one block per image: exclusive scan of the chunk counts, count[n]
+//   6. label_rank      number of every root (written at the root's own pixel), its table entry initialised
+//   7. label_relabel   final labels; box / area / coordinate sums: runs of equal label inside a wave are combined (a
+//                      segmented reduction along the row), full-width runs of consecutive rows too, one atomic per
+//                      field and flush -- never one per pixel
+#include "uocr_common.h"
+
+// float64 forms of the activation accessors of uocr_common.h (8 / 16 bytes per access)
+__device__ __forceinline__ double ld1(const double* p) { return *p; }
+__device__ __forceinline__ double2 ld2(const double* p) { return *reinterpret_cast<const double2*>(p); }
+__device__ __forceinline__ void st1(double* p, double v) { *p = v; }
+__device__ __forceinline__ void st2(double* p, double2 v) { *reinterpret_cast<double2*>(p) = v; }
+
+namespace {
+
+constexpr int LTH = 16, LTW = 64;          // tile of label_local / label_merge
+constexpr int LNT = 256;                   // threads per block of every kernel here
+constexpr int LCHUNK = 1024;               // pixels per block of label_flatten / label_rank
+constexpr int LROWS = 16;                  // rows per wave of label_relabel
+constexpr unsigned LSYNC = 4;              // word of ctx->sync the statistics launch counts its blocks in
+
+__device__ __forceinline__ int g_load(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int g_min(int* p, int v) {
+    return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ int l_load(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ int l_min(int* p, int v) {
+    return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// Union-find whose links always point to a smaller index of the same component.  A link is only ever lowered
+// (atomicMin), so a reader that sees an older value still walks inside the component and every loop ends; whoever
+// replaces a link a -> old by a -> b goes on to unite old and b, so no connection is lost.  GLOBAL = the image plane in
+// HBM (relaxed agent-scope atomics: the L2s are per XCD), else a tile in LDS.
+template <bool GLOBAL>
+__device__ __forceinline__ int uf_load(int* L, int i) { return GLOBAL ? g_load(L + i) : l_load(L + i); }
+template <bool GLOBAL>
+__device__ __forceinline__ int uf_min(int* L, int i, int v) { return GLOBAL ? g_min(L + i, v) : l_min(L + i, v); }
+
+template <bool GLOBAL>
+__device__ __forceinline__ int uf_find(int* L, int x) {
+    int at = x, p;
+    while ((p = uf_load<GLOBAL>(L, x)) != x) x = p;
+    if (GLOBAL)                                                // shorten the chain for whoever walks it next (still only lowering)
+        while (at > x) {                                       // (links go strictly downwards: this ends at or below x)
+            p = uf_load<true>(L, at);
+            if (p > x) uf_min<true>(L, at, x);
+            at = p;
+        }
+    return x;
+}
+
+template <bool GLOBAL>
+__device__ __forceinline__ void uf_unite(int* L, int a, int b) {
+    for (;;) {
+        a = uf_find<GLOBAL>(L, a);
+        b = uf_find<GLOBAL>(L, b);
+        if (a == b) return;
+        if (a < b) {
+            const int t = a;
+            a = b;
+            b = t;
+        }
+        const int old = uf_min<GLOBAL>(L, a, b);
+        if (old == a) return;                                  // a was a root and now hangs below b
+        a = old;                                               // a had a parent already: that one and b remain to be united
+    }
+}
+
+// ---- 1. threshold statistics ------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(LNT) void label_stats(const T* __restrict__ x, size_t count, int mode, unsigned* counter,
+                                                   double* partial /* [2 * grid] */, double* thr) {
+    __shared__ double smem[17];
+    __shared__ double smax[5];
+    double sum = 0.0, mx = -INFINITY;
+    for (size_t i = (size_t)blockIdx.x * LNT + threadIdx.x; i < count; i += (size_t)gridDim.x * LNT) {
+        const double v = (double)x[i];
+        sum += v;
+        mx = v > mx ? v : mx;
+    }
+    sum = block_reduce_sum(sum, smem);
+    mx = wave_reduce_max(mx);
+    if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < LNT / 64; ++k) mx = smax[k] > mx ? smax[k] : mx;
+        pub_store(partial + 2 * blockIdx.x, sum);
+        pub_store(partial + 2 * blockIdx.x + 1, mx);
+        const unsigned t = sync_arrive(counter);
+        smax[4] = t == gridDim.x - 1 ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    if (smax[4] == 0.0) return;                                // block-uniform: only the last block to arrive goes on
+    sum = 0.0, mx = -INFINITY;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += LNT) {  // fixed order: the same bits run to run
+        sum += pub_load(partial + 2 * i);
+        const double m = pub_load(partial + 2 * i + 1);
+        mx = m > mx ? m : mx;
+    }
+    sum = block_reduce_sum(sum, smem);
+    mx = wave_reduce_max(mx);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < LNT / 64; ++k) mx = smax[k] > mx ? smax[k] : mx;
+        const double mean = sum / (double)count;
+        *thr = mode == UOCR_THRESH_MEAN ? mean : 0.5 * (mean + mx);
+        sync_clear(counter);
+    }
+}
+
+// ---- 2. tile-local union-find -------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(LNT) void label_local(const T* __restrict__ x, int h, int w, int tiles_x, int tiles_y,
+                                                   const double* thr_dev, double thr_value, int* __restrict__ plane) {
+    __shared__ int L[LTH * LTW];
+    const double thr = thr_dev ? *thr_dev : thr_value;
+    const int tile = blockIdx.x;
+    const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, img = tile / (tiles_x * tiles_y);
+    const size_t base = (size_t)img * h * w;
+    const int lx = threadIdx.x & (LTW - 1), gx = tx * LTW + lx;
+    constexpr int RSTEP = LNT / LTW, PER = LTH / RSTEP;
+    static_assert(LTW == 64, "a wave is one row of the tile: its ballot is the row's foreground");
+    bool fg[PER];
+    int run[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int ly = (threadIdx.x / LTW) + k * RSTEP, gy = ty * LTH + ly;
+        fg[k] = gy < h && gx < w && (double)x[base + (size_t)gy * w + gx] > thr;
+        // every pixel starts at the first pixel of its horizontal run: no union along a row is needed
+        const unsigned long long gaps_below = ~__ballot(fg[k]) & ((1ull << lx) - 1ull);
+        run[k] = gaps_below ? 64 - __clzll((long long)gaps_below) : 0;
+        L[ly * LTW + lx] = fg[k] ? ly * LTW + run[k] : -1;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int ly = (threadIdx.x / LTW) + k * RSTEP, i = ly * LTW + lx;
+        // with the row above: not where the left neighbour and the one above it are foreground too -- those two are in
+        // this pixel's and the upper pixel's runs, and the union is made further left (at the run's start at the latest)
+        if (fg[k] && ly > 0 && l_load(L + i - LTW) >= 0 && (lx == run[k] || l_load(L + i - LTW - 1) < 0))
+            uf_unite<false>(L, i, i - LTW);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int ly = (threadIdx.x / LTW) + k * RSTEP, gy = ty * LTH + ly;
+        if (gy < h && gx < w) {
+            int out = -1;
+            if (fg[k]) {
+                const int r = uf_find<false>(L, ly * LTW + lx);
+                out = (ty * LTH + r / LTW) * w + tx * LTW + (r % LTW);
+            }
+            plane[base + (size_t)gy * w + gx] = out;
+        }
+    }
+}
+
+// ---- 3. unions across tile borders ----------------------------------------------------------------------------------
+__global__ __launch_bounds__(LNT) void label_merge(int h, int w, int tiles_x, int tiles_y, int* plane) {
+    const int tile = blockIdx.x;
+    const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, img = tile / (tiles_x * tiles_y);
+    int* L = plane + (size_t)img * h * w;
+    for (int e = threadIdx.x; e < LTW + LTH; e += LNT) {
+        int gy, gx, other;
+        if (e < LTW) {                       // top row of the tile against the row above
+            gy = ty * LTH, gx = tx * LTW + e;
+            if (ty == 0 || gx >= w) continue;
+            other = (gy - 1) * w + gx;
+        } else {                             // left column against the column to its left
+            gy = ty * LTH + (e - LTW), gx = tx * LTW;
+            if (tx == 0 || gy >= h) continue;
+            other = gy * w + gx - 1;
+        }
+        const int i = gy * w + gx;
+        if (g_load(L + i) < 0 || g_load(L + other) < 0) continue;
+        // the previous pixel along the border and its partner, when both are foreground, are joined to this pair inside
+        // their tiles already and make the union themselves (or the pair before them does)
+        const int back = e < LTW ? 1 : w;
+        if (e != 0 && e != LTW && g_load(L + i - back) >= 0 && g_load(L + other - back) >= 0) continue;
+        uf_unite<true>(L, i, other);
+    }
+}
+
+// exclusive scan of one int per thread over the block (LNT threads); *total = the block's sum.  Contains barriers.
+__device__ __forceinline__ int block_exscan(int v, int* total, int* smem /* >= LNT / 64 + 1 */) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += o;
+    }
+    __syncthreads();
+    if (lane == 63) smem[wid] = inc;
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int k = 0; k < LNT / 64; ++k) {
+        before += k < wid ? smem[k] : 0;
+        all += smem[k];
+    }
+    *total = all;
+    return before + inc - v;
+}
+
+// ---- 4. flatten + roots per chunk ----------------------------------------------------------------------------------
+__global__ __launch_bounds__(LNT) void label_flatten(int hw, int chunks, int* __restrict__ plane, int* __restrict__ root,
+                                                     int* __restrict__ chunk_count) {
+    __shared__ int smem[LNT / 64 + 1];
+    const int img = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
+    int* L = plane + (size_t)img * hw;
+    int* R = root + (size_t)img * hw;
+    int mine = 0;
+#pragma unroll
+    for (int j = 0; j < LCHUNK / LNT; ++j) {
+        const int i = chunk * LCHUNK + j * LNT + threadIdx.x;
+        if (i < hw) {
+            int r = L[i];                      // (no block writes the plane in this launch)
+            if (r >= 0) {
+                int p = r;
+                r = i;
+                while (p != r) {
+                    r = p;
+                    p = L[r];
+                }
+                mine += r == i;
+            }
+            R[i] = r;
+        }
+    }
+    int total;
+    block_exscan(mine, &total, smem);
+    if (threadIdx.x == 0) chunk_count[blockIdx.x] = total;
+}
+
+// ---- 5. scan of the chunk counts, one block per image ----------------------------------------------------------------
+__global__ __launch_bounds__(LNT) void label_scan(int chunks, int* __restrict__ chunk_count, int* __restrict__ count) {
+    __shared__ int smem[LNT / 64 + 1];
+    int* c = chunk_count + (size_t)blockIdx.x * chunks;
+    int running = 0;
+    for (int first = 0; first < chunks; first += LNT) {
+        const int i = first + threadIdx.x;
+        const int v = i < chunks ? c[i] : 0;
+        int total;
+        const int ex = block_exscan(v, &total, smem);
+        if (i < chunks) c[i] = running + ex;
+        running += total;
+    }
+    if (threadIdx.x == 0) count[blockIdx.x] = running;
+}
+
+// ---- 6. rank of every root ----------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(LNT) void label_rank(int hw, int chunks, const int* __restrict__ root,
+                                                  const int* __restrict__ chunk_offset, int* __restrict__ plane,
+                                                  long long* __restrict__ table, int max_components) {
+    __shared__ int smem[LNT / 64 + 1];
+    const int img = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
+    const int* R = root + (size_t)img * hw;
+    int running = chunk_offset[blockIdx.x];
+    for (int j = 0; j < LCHUNK / LNT; ++j) {
+        const int i = chunk * LCHUNK + j * LNT + threadIdx.x;
+        const int is_root = i < hw && R[i] == i;
+        int total;
+        const int ex = block_exscan(is_root, &total, smem);
+        if (is_root) {
+            const int k = running + ex + 1;
+            plane[(size_t)img * hw + i] = k;
+            if (k <= max_components) {
+                long long* e = table + ((size_t)img * max_components + (k - 1)) * 8;
+                e[0] = i, e[1] = 0, e[2] = INT32_MAX, e[3] = 0, e[4] = INT32_MAX, e[5] = 0, e[6] = 0, e[7] = 0;
+            }
+        }
+        running += total;
+    }
+}
+
+// ---- 7. final labels + table -----------------------------------------------------------------------------------------
+struct RunAcc {
+    int k;
+    long long area, y0, y1, x0, x1, sy, sx;
+};
+__device__ __forceinline__ void table_flush(long long* table_img, int max_components, const RunAcc& a) {
+    if (a.k <= 0 || a.k > max_components) return;
+    unsigned long long* e = reinterpret_cast<unsigned long long*>(table_img + (size_t)(a.k - 1) * 8);
+    atomicAdd(e + 1, (unsigned long long)a.area);
+    atomicMin(e + 2, (unsigned long long)a.y0);
+    atomicMax(e + 3, (unsigned long long)a.y1);
+    atomicMin(e + 4, (unsigned long long)a.x0);
+    atomicMax(e + 5, (unsigned long long)a.x1);
+    atomicAdd(e + 6, (unsigned long long)a.sy);
+    atomicAdd(e + 7, (unsigned long long)a.sx);
+}
+
+// One wave owns a strip of 64 columns x LROWS rows.  Per row: the heads of runs of equal label come from one ballot; a
+// run that fills the strip's whole width and continues the label of the rows above is kept in (wave-uniform) registers
+// and flushed once, by lane 0, when the label changes or the strip ends.
+__global__ __launch_bounds__(LNT) void label_relabel(int h, int w, int strips_x, int strips_y,
+                                                     const int* __restrict__ root, int* __restrict__ plane,
+                                                     long long* __restrict__ table, int max_components, int n) {
+    const int lane = threadIdx.x & 63;
+    const long long wave = (long long)blockIdx.x * (LNT / 64) + (threadIdx.x >> 6);
+    const int sx_ = (int)(wave % strips_x), sy_ = (int)((wave / strips_x) % strips_y);
+    const long long img = wave / ((long long)strips_x * strips_y);
+    if (img >= n) return;                                           // (the grid is rounded up to whole blocks)
+    const size_t hw = (size_t)h * w;
+    const int* R = root + img * hw;
+    int* P = plane + img * hw;
+    long long* T = table + (size_t)img * max_components * 8;
+    const int gx = sx_ * 64 + lane;
+    const int valid_n = min(64, w - sx_ * 64);                      // lanes of this strip inside the image
+    const bool valid = lane < valid_n;
+    RunAcc acc;
+    acc.k = 0;
+    const int y_end = min(h, (sy_ + 1) * LROWS);
+    for (int gy = sy_ * LROWS; gy < y_end; ++gy) {
+        int k = 0;
+        if (valid) {
+            const int r = R[(size_t)gy * w + gx];
+            if (r >= 0) k = P[r];                                   // the root's pixel holds the number (label_rank) ...
+            if (r != gy * w + gx) P[(size_t)gy * w + gx] = k;       // ... and is the one pixel this launch only reads
+        }
+        const int prev = __shfl_up(k, 1, 64);
+        const bool head = valid && (lane == 0 || k != prev);
+        const unsigned long long heads = __ballot(head);
+        const int k0 = __shfl(k, 0, 64);
+        if (heads == 1ull) {                                        // one run over the whole width: wave-uniform
+            if (k0 != acc.k) {
+                if (lane == 0) table_flush(T, max_components, acc);
+                acc.k = k0, acc.area = 0, acc.sy = 0, acc.sx = 0;
+                acc.y0 = gy, acc.x0 = sx_ * 64, acc.x1 = sx_ * 64 + valid_n;
+            }
+            if (k0 > 0) {
+                acc.area += valid_n;
+                acc.y1 = gy + 1;
+                acc.sy += (long long)gy * valid_n;
+                acc.sx += (long long)valid_n * (sx_ * 64) + (long long)valid_n * (valid_n - 1) / 2;
+            }
+            continue;
+        }
+        if (lane == 0) table_flush(T, max_components, acc);
+        acc.k = 0;
+        if (head && k > 0) {
+            const unsigned long long later = lane == 63 ? 0ull : (heads >> (lane + 1)) << (lane + 1);
+            const int end = later ? __ffsll((long long)later) - 1 : valid_n;
+            const long long len = end - lane;
+            RunAcc run;
+            run.k = k, run.area = len, run.y0 = gy, run.y1 = gy + 1, run.x0 = gx, run.x1 = gx + len;
+            run.sy = (long long)gy * len, run.sx = len * gx + len * (len - 1) / 2;
+            table_flush(T, max_components, run);
+        }
+    }
+    if (lane == 0) table_flush(T, max_components, acc);
+}
+
+// ---- masked crop ----------------------------------------------------------------------------------------------------------
+// one thread per output pixel; C = 1 / 2 / 4 channels move as one 4- / 8- / 16-byte access of float (2 / 4 / 8 of
+// binary16; float64 as 8 / 16 / 2 x 16), C = 0 is the generic loop over `c` channels
+template <typename T, int C>
+__global__ __launch_bounds__(LNT) void masked_crop(const T* __restrict__ image, const int* __restrict__ labels, int w, int c,
+                                                   int label_id, int y0, int x0, int ch, int cw, int py, int px,
+                                                   T* __restrict__ out, int out_h, int out_w) {
+    const size_t o = (size_t)blockIdx.x * LNT + threadIdx.x;
+    if (o >= (size_t)out_h * out_w) return;
+    const int oy = (int)(o / out_w), ox = (int)(o % out_w);
+    const int sy = oy - py, sx = ox - px;
+    bool take = sy >= 0 && sy < ch && sx >= 0 && sx < cw;
+    size_t src = 0;
+    if (take) {
+        src = (size_t)(y0 + sy) * w + (x0 + sx);
+        take = labels[src] == label_id;
+    }
+    if constexpr (C == 0) {
+        for (int i = 0; i < c; ++i) out[o * c + i] = take ? image[src * c + i] : T(0);
+    } else if constexpr (C == 1) {
+        decltype(ld1(image)) v = 0;
+        if (take) v = ld1(image + src);
+        st1(out + o, v);
+    } else if constexpr (C == 2) {
+        decltype(ld2(image)) v = {0, 0};
+        if (take) v = ld2(image + src * 2);
+        st2(out + o * 2, v);
+    } else if constexpr (sizeof(T) == 8) {
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            double2 v = {0, 0};
+            if (take) v = ld2(image + src * 4 + 2 * half);
+            st2(out + o * 4 + 2 * half, v);
+        }
+    } else {
+        decltype(ld4(image)) v = {0, 0, 0, 0};
+        if (take) v = ld4(image + src * 4);
+        st4(out + o * 4, v);
+    }
+}
+
+}  // namespace
+
+#define UOCR_CROP(C)                                                                                                   \
+    hipLaunchKernelGGL((masked_crop<T, C>), dim3((unsigned)blocks), dim3(LNT), 0, ctx->stream, img, lab, w, c, label_id, \
+                       y0, x0, ch, cw, py, px, (T*)out, out_h, out_w)
+
+extern "C" {
+
+int uocr_label_components(uocr_ctx* ctx, int dtype, const void* x, int n, int h, int w, int thresh_mode,
+                          double thresh_value, int* labels, long long* table, int max_components, int* count) {
+    UOCR_CHECK_CTX(ctx);
+    UOCR_REQUIRE(ctx, x && labels && table && count);
+    UOCR_REQUIRE(ctx, n >= 0 && h >= 0 && w >= 0 && max_components >= 0);
+    UOCR_REQUIRE(ctx, thresh_mode == UOCR_THRESH_MEAN || thresh_mode == UOCR_THRESH_MEAN_MAX ||
+                          thresh_mode == UOCR_THRESH_VALUE);
+    const int base = UOCR_DTYPE_BASE(dtype);
+    if (base != UOCR_F32 && base != UOCR_F64 && base != UOCR_F16) UOCR_FAIL(ctx, UOCR_ERR_DTYPE, "unknown dtype %d", dtype);
+    if ((long long)h * w > (long long)INT32_MAX - LCHUNK)
+        UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "image of %d x %d pixels: linear indices must fit int32", h, w);
+    if (n == 0 || h == 0 || w == 0) return UOCR_OK;
+    const int hw = h * w;
+    const size_t pixels = (size_t)n * hw;
+    const int tiles_x = (w + LTW - 1) / LTW, tiles_y = (h + LTH - 1) / LTH;
+    const int chunks = (hw + LCHUNK - 1) / LCHUNK;
+    const int strips_x = (w + 63) / 64, strips_y = (h + LROWS - 1) / LROWS;
+    const long long tiles = (long long)n * tiles_x * tiles_y, nchunks = (long long)n * chunks;
+    const long long relabel_blocks = ((long long)n * strips_x * strips_y + LNT / 64 - 1) / (LNT / 64);
+    if (tiles > INT32_MAX || nchunks > INT32_MAX || relabel_blocks > INT32_MAX)
+        UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "batch of %d images of %d x %d: too many blocks for one grid", n, h, w);
+    const unsigned stat_blocks = uocr_blocks_for(pixels, 4 * LNT, UOCR_MAX_GRID);
+    // workspace: root plane | chunk counts | statistics partials (sum, max per block) | threshold
+    const size_t off_counts = (pixels * sizeof(int) + 15) & ~(size_t)15;
+    const size_t off_partial = (off_counts + (size_t)nchunks * sizeof(int) + 15) & ~(size_t)15;
+    const size_t off_thr = off_partial + 2 * (size_t)stat_blocks * sizeof(double);
+    if (int rc = uocr_need_workspace(ctx, off_thr + sizeof(double))) return rc;
+    char* ws = (char*)ctx->workspace;
+    int* root = (int*)ws;
+    int* chunk_count = (int*)(ws + off_counts);
+    double* partial = (double*)(ws + off_partial);
+    double* thr = (double*)(ws + off_thr);
+    int launches = 0;
+    UOCR_DISPATCH_STORAGE(ctx, dtype, {
+        if (thresh_mode != UOCR_THRESH_VALUE) {
+            hipLaunchKernelGGL(label_stats<T>, dim3(stat_blocks), dim3(LNT), 0, ctx->stream, (const T*)x, pixels, thresh_mode,
+                               ctx->sync + LSYNC, partial, thr);
+            UOCR_LAUNCH_CHECK(ctx);
+            ++launches;
+        }
+        hipLaunchKernelGGL(label_local<T>, dim3((unsigned)tiles), dim3(LNT), 0, ctx->stream, (const T*)x, h, w, tiles_x,
+                           tiles_y, thresh_mode == UOCR_THRESH_VALUE ? (const double*)nullptr : (const double*)thr,
+                           thresh_value, labels);
+        UOCR_LAUNCH_CHECK(ctx);
+        ++launches;
+    });
+    if (tiles_x > 1 || tiles_y > 1) {
+        hipLaunchKernelGGL(label_merge, dim3((unsigned)tiles), dim3(LNT), 0, ctx->stream, h, w, tiles_x, tiles_y, labels);
+        UOCR_LAUNCH_CHECK(ctx);
+        ++launches;
+    }
+    hipLaunchKernelGGL(label_flatten, dim3((unsigned)nchunks), dim3(LNT), 0, ctx->stream, hw, chunks, labels, root,
+                       chunk_count);
+    UOCR_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(label_scan, dim3(n), dim3(LNT), 0, ctx->stream, chunks, chunk_count, count);
+    UOCR_LAUNCH_CHECK(ctx);
+    if (max_components > 0)   // entries past an image's count read zero
+        UOCR_HIP(ctx, hipMemsetAsync(table, 0, (size_t)n * max_components * 8 * sizeof(long long), ctx->stream));
+    hipLaunchKernelGGL(label_rank, dim3((unsigned)nchunks), dim3(LNT), 0, ctx->stream, hw, chunks, (const int*)root,
+                       (const int*)chunk_count, labels, table, max_components);
+    UOCR_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(label_relabel, dim3((unsigned)relabel_blocks), dim3(LNT), 0, ctx->stream, h, w, strips_x, strips_y,
+                       (const int*)root, labels, table, max_components, n);
+    UOCR_LAUNCH_CHECK(ctx);
+    launches += 4;
+    ctx->label_th = LTH, ctx->label_tw = LTW, ctx->label_launches = launches;
+    return UOCR_OK;
+}
+
+int uocr_masked_crop(uocr_ctx* ctx, int dtype, const void* image, const int* labels, int n, int h, int w, int c,
+                     int image_index, int label_id, int y0, int x0, int ch, int cw, void* out, int out_h, int out_w) {
+    UOCR_CHECK_CTX(ctx);
+    UOCR_REQUIRE(ctx, image && labels && out);
+    UOCR_REQUIRE(ctx, n >= 0 && h >= 0 && w >= 0 && c >= 0 && ch >= 0 && cw >= 0 && out_h >= 0 && out_w >= 0);
+    UOCR_REQUIRE(ctx, image_index >= 0 && image_index < n && label_id >= 1);
+    UOCR_REQUIRE(ctx, y0 >= 0 && x0 >= 0 && ch <= h - y0 && cw <= w - x0);
+    UOCR_REQUIRE(ctx, out_h >= ch && out_w >= cw);
+    const int base = UOCR_DTYPE_BASE(dtype);
+    if (base != UOCR_F32 && base != UOCR_F64 && base != UOCR_F16) UOCR_FAIL(ctx, UOCR_ERR_DTYPE, "unknown dtype %d", dtype);
+    const size_t out_pixels = (size_t)out_h * out_w;
+    if (out_pixels == 0 || c == 0) return UOCR_OK;
+    const size_t blocks = (out_pixels + LNT - 1) / LNT;
+    if (blocks > INT32_MAX) UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "crop of %d x %d pixels: too many blocks", out_h, out_w);
+    const int py = (out_h - ch) / 2, px = (out_w - cw) / 2;
+    const size_t hw = (size_t)h * w;
+    const int* lab = labels + (size_t)image_index * hw;
+    UOCR_DISPATCH_STORAGE(ctx, dtype, {
+        const T* img = (const T*)image + (size_t)image_index * hw * c;
+        const size_t pixel_bytes = sizeof(T) * (size_t)c;
+        const size_t align = pixel_bytes > 16 ? 16 : pixel_bytes;
+        const bool vec = (c == 1 || c == 2 || c == 4) &&
+                         ((reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(out)) & (align - 1)) == 0;
+        if (vec && c == 1) UOCR_CROP(1);
+        else if (vec && c == 2) UOCR_CROP(2);
+        else if (vec && c == 4) UOCR_CROP(4);
+        else UOCR_CROP(0);
+        UOCR_LAUNCH_CHECK(ctx);
+    });
+    return UOCR_OK;
+}
+
+int uocr_ctx_last_label(uocr_ctx* ctx, int* tile_h, int* tile_w, int* launches) {
+    UOCR_CHECK_CTX(ctx);
+    UOCR_REQUIRE(ctx, tile_h && tile_w && launches);
+    *tile_h = ctx->label_th;
+    *tile_w = ctx->label_tw;
+    *launches = ctx->label_launches;
+    return UOCR_OK;
+}
+
+}  // extern "C"

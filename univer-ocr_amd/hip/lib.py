@@ -18,6 +18,7 @@ def f16_scaled(k):
     return F16 | (int(k) << 8)
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3
 LOSS_DICE, LOSS_JACCARD = 0, 1
+THRESH_MEAN, THRESH_MEAN_MAX, THRESH_VALUE = 0, 1, 2
 # UOCR_CONV_*: the kernel family uocr_ctx_last_conv reports (index = value)
 CONV_KERNELS = ('none', 'generic', 'mfma', 'h16', 'h16_wgrad', 'h16_wgrad_s2', 't32', 't32_wgrad', 'h3', 'tiled',
                 'c16_expand', 'c16_reduce', 'c16_wgrad', 'dgrad_s2', 'dgrad_c64s2', 'wgrad_t542', 'wgrad_s2_tiled',
@@ -122,6 +123,9 @@ _PROTOS = {
                              C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_double), _vp, _i, _vp],
     'uocr_rmsprop_step': [_ctx, _i, _vp, _vp, _vp, _sz, _d, _d, _d],
     'uocr_has_nan': [_ctx, _i, _vp, _sz, _vp],
+    'uocr_label_components': [_ctx, _i, _vp, _i, _i, _i, _i, _d, _vp, _vp, _i, _vp],
+    'uocr_masked_crop': [_ctx, _i, _vp, _vp] + [_i] * 10 + [_vp, _i, _i],
+    'uocr_ctx_last_label': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     'uocr_dp_init': [_ctx, _i, _i, _vp],
     'uocr_dp_info': [_ctx, C.POINTER(_i), C.POINTER(_i)],
     'uocr_dp_allreduce_sum': [_ctx, _vp, _sz, _i],

@@ -8,9 +8,10 @@ channel counts, kernel sizes and losses, so `model_weights.json` files are inter
   Char        3 x conv(5x3, stride (2,1), pad (0,1), 64 ch) LeakyReLU, fixed-width(8) windows,
               dense 512->1024->128->162, softmax cross-entropy                     (:250-304)
 
-Every conv carries L2(0.01) (model.py:36-39).  The crop / rotate stages that sit between the nets
-in the reference's model system are host code (interpreter/) and out of this backend's scope;
-`make_model_system` builds the modes whose data path stays on the device.
+Every conv carries L2(0.01) (model.py:36-39).  Of the stages that sit between the nets in the
+reference's model system (host code, interpreter/), ParagraphCrop without the rotation search runs on
+the device (my_model/crop.py), which is what TRAIN_LINE needs; LineCrop, CharLabel and PredToText have
+no device form yet, and `make_model_system` says so for the modes that need them.
 """
 from enum import Enum
 
@@ -22,9 +23,10 @@ from ..nn.layers import (
     Concat, Conv2DToBatchedFixedWidthed, Convolutional2D, Flatten, FullyConnected, LeakyRelu, Sigmoid,
     Upsample2D)
 from ..nn.losses import SegmentationDice2D, SoftmaxCrossEntropy
-from ..nn.model_system import ModelComponent, ModelSystem, StringSelector
+from ..nn.model_system import IterableSelector, ModelComponent, ModelSystem, RawFunctionComponent, StringSelector
 from ..nn.models import Model
 from ..nn.optimizers import Adam
+from ..nn.progress_tracker import track_function
 from ..nn.regularizations import L2
 
 CHAR_INPUT_HEIGHT = 32
@@ -159,6 +161,104 @@ def make_char(input_shape, optimizer=None):
 NET_MAKERS = {'Monochrome': make_monochrome, 'Paragraph': make_paragraph, 'Line': make_line, 'Char': make_char}
 
 
+def _map_nested(func, value):
+    """`func` on every array of a (possibly nested) list / dict structure."""
+    if isinstance(value, list):
+        return [_map_nested(func, item) for item in value]
+    if isinstance(value, dict):
+        return {key: _map_nested(func, item) for key, item in value.items()}
+    return func(value)
+
+
+def _make_move_component(func, labels):
+    def move(context):
+        for source, target in labels:
+            context[target] = _map_nested(func, context[source])
+    return RawFunctionComponent(move)
+
+
+def make_move_from_gpu_component(labels):
+    """model.py:307-320: context[new] = host copy of context[old] for every (old, new) pair; lists and dicts are walked."""
+    return _make_move_component(CP.asnumpy, labels)
+
+
+def make_move_to_gpu_component(labels):
+    """model.py:323-334: the other direction."""
+    return _make_move_component(CP.copy, labels)
+
+
+class LineSelector(IterableSelector):
+    """One sample per paragraph (model.py:353-373): context[X_label][p], context[y_label][p]; the prediction of
+    paragraph p is filed at context[pred_label][p].  The position starts over with every bind."""
+
+    def __init__(self, X_label, y_label, pred_label):
+        IterableSelector.__init__(self, X_label, y_label, pred_label)
+        self.paragraph_id = 0
+
+    def __call__(self, context):
+        IterableSelector.__call__(self, context)
+        self.paragraph_id = 0
+
+    def get(self):
+        Xs, ys = self.context[self.X_label], self.context[self.y_label]
+        for self.paragraph_id in range(len(Xs)):
+            yield Xs[self.paragraph_id], ys[self.paragraph_id]
+
+    def get_X(self):
+        Xs = self.context[self.X_label]
+        for self.paragraph_id in range(len(Xs)):
+            yield Xs[self.paragraph_id]
+
+    @staticmethod
+    def _grown(store, index):
+        """`store`, with empty entries appended until position `index` exists (a paragraph without lines leaves a gap)"""
+        while index >= len(store):
+            store.append([])
+        return store
+
+    def put(self, pred):
+        per_paragraph = self.context.setdefault(self.pred_label, [])
+        self._grown(per_paragraph, self.paragraph_id)[self.paragraph_id] = pred
+
+
+class CharSelector(LineSelector):
+    """One sample per line of every paragraph (model.py:376-400): context[X_label][p][l]; predictions are filed at
+    context[pred_label][p][l].  Paragraphs may hold different numbers of lines."""
+
+    def __init__(self, X_label, y_label, pred_label):
+        LineSelector.__init__(self, X_label, y_label, pred_label)
+        self.line_id = 0
+
+    def __call__(self, context):
+        LineSelector.__call__(self, context)
+        self.line_id = 0
+
+    def get(self):
+        Xs, ys = self.context[self.X_label], self.context[self.y_label]
+        for self.paragraph_id in range(len(Xs)):
+            for self.line_id in range(len(Xs[self.paragraph_id])):
+                yield Xs[self.paragraph_id][self.line_id], ys[self.paragraph_id][self.line_id]
+
+    def get_X(self):
+        Xs = self.context[self.X_label]
+        for self.paragraph_id in range(len(Xs)):
+            for self.line_id in range(len(Xs[self.paragraph_id])):
+                yield Xs[self.paragraph_id][self.line_id]
+
+    def put(self, pred):
+        per_paragraph = self.context.setdefault(self.pred_label, [])
+        per_line = self._grown(per_paragraph, self.paragraph_id)[self.paragraph_id]
+        self._grown(per_line, self.line_id)[self.line_id] = pred
+
+
+# what the modes that still raise are waiting for (the reference's component order, model.py:489-500)
+_MISSING_STAGE = {
+    'TRAIN_CHAR': 'LineCrop (interpreter.py CropRotateAndZoomLines: ndimage.rotate / zoom of every line) and CharLabel',
+    'TRAIN_ALL': 'LineCrop (interpreter.py CropRotateAndZoomLines: ndimage.rotate / zoom of every line) and CharLabel',
+    'PREDICT': 'the rotation search of ParagraphCrop (find_rotation=True), LineCrop and PredToText',
+}
+
+
 class Modes(Enum):
     TRAIN_MONOCHROME = 0
     TRAIN_PARAGRAPH = 1
@@ -181,12 +281,14 @@ def make_context_maker(mode=Modes.PREDICT):
                            'paragraph_X': 'monochrome', 'paragraph_y': 'paragraph',
                            'line_X': 'monochrome', 'line_y': 'line',
                            'char_X': 'char_lines', 'char_y': 'char_labels'},
+        # model.py:438-447 keeps these three on the host (`*_cpu`) for its host crop stage; here the crop runs on the device
+        Modes.TRAIN_LINE: {'monochrome_pred': 'monochrome', 'paragraph_pred': 'paragraph', 'line': 'line'},
         Modes.PREDICT: {'monochrome_X': 'image'},
     }
     if mode not in wanted:
         raise NotImplementedError(
-            f'{mode.name} needs the host crop/rotate stages of the reference (interpreter/), '
-            f'which are outside the MI355X backend (SURVEY.md section 2, component 18)')
+            f'{mode.name} needs a stage that has no device form yet: {_MISSING_STAGE[mode.name]} '
+            f'(the device stages are in my_model/crop.py)')
     mapping = wanted[mode]
 
     def make_context(dataset_get_func, args=(), kwargs={}):
@@ -198,7 +300,16 @@ def make_context_maker(mode=Modes.PREDICT):
 
 def make_model_system(input_shape, optimizer=None, progress_tracker=None, weights=None, mode=Modes.PREDICT,
                       char_input_shape=None):
-    """model.py:486-717 for the device-resident modes.  Returns (model_system, models, names)."""
+    """model.py:486-717 for the device-resident modes.  Returns (model_system, models, names).
+
+    TRAIN_LINE is the system [ParagraphCrop, Line] (names ['ParagraphCrop', 'Line']): the crop stage labels
+    context['paragraph_pred'], cuts context['monochrome_pred'] and context['line'] to every paragraph, pads the crops to
+    multiples of 16 (make_divisible_by) and files them as context['cropped_monochrome'] / ['cropped_line']; the Line net
+    then takes one step per paragraph through a LineSelector and files line_pred[paragraph].  That equals the reference's
+    TRAIN_LINE system (model.py:585-593) built with find_rotation=False, minus its move_to_gpu component: no array
+    visits the host between the stages (the crop stage reads back the component table only)."""
+    if mode is Modes.TRAIN_LINE:
+        return _make_train_line_system(input_shape, optimizer, progress_tracker, weights)
     plan = {
         Modes.TRAIN_MONOCHROME: ['Monochrome'],
         Modes.TRAIN_PARAGRAPH: ['Paragraph'],
@@ -206,8 +317,8 @@ def make_model_system(input_shape, optimizer=None, progress_tracker=None, weight
     }
     if mode not in plan:
         raise NotImplementedError(
-            f'{mode.name} chains the nets through host crop/rotate stages (interpreter/), which are '
-            f'outside the MI355X backend; use TRAIN_MONOCHROME / TRAIN_PARAGRAPH / TRAIN_PAGE')
+            f'{mode.name} needs a stage that has no device form yet: {_MISSING_STAGE[mode.name]}; '
+            f'use TRAIN_MONOCHROME / TRAIN_PARAGRAPH / TRAIN_LINE / TRAIN_PAGE')
     components, models = [], {}
     for name in plan[mode]:
         shape = input_shape
@@ -223,3 +334,23 @@ def make_model_system(input_shape, optimizer=None, progress_tracker=None, weight
                                          delist_result=True))
         models[name] = model
     return ModelSystem(components), models, list(plan[mode])
+
+
+def _make_train_line_system(input_shape, optimizer, progress_tracker, weights):
+    from .crop import CropParagraphs
+    crop_paragraphs = CropParagraphs(find_rotation=False)
+
+    @track_function('ParagraphCrop', 'forward', progress_tracker)
+    def paragraph_crop(context):
+        crops = crop_paragraphs(context['paragraph_pred'], [context['monochrome_pred'], context['line']],
+                                divisible_by=(16, 16))
+        context['cropped_monochrome'], context['cropped_line'] = crops
+
+    model = make_line(input_shape, optimizer)
+    if progress_tracker is not None:
+        model.init_progress_tracker(progress_tracker, 'Line')
+    if weights is not None:
+        model.set_weights(weights)
+    line = ModelComponent('Line', model, LineSelector('cropped_monochrome', 'cropped_line', 'line_pred'),
+                          delist_result=True)
+    return ModelSystem([RawFunctionComponent(paragraph_crop), line]), {'Line': model}, ['ParagraphCrop', 'Line']

@@ -27,7 +27,7 @@ from ..hip.lib import HipError
 
 _TORCH_DT = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64,
              np.dtype(np.float16): torch.float16,
-             np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32}
+             np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64}
 _CODE = {torch.float32: hiplib.F32, torch.float64: hiplib.F64, torch.float16: hiplib.F16}
 _NP_DT = {v: k for k, v in _TORCH_DT.items()}
 
@@ -170,6 +170,14 @@ class Runtime:
         entry, kernel = C.c_int(), C.c_int()
         self.call('uocr_ctx_last_conv', C.byref(entry), C.byref(kernel))
         return entry.value, kernel.value
+
+    def last_label(self):
+        """(tile rows, tile columns, kernel launches) of the most recent uocr_label_components call on the current lane
+        (uocr_ctx_last_label); all 0 before the first."""
+        import ctypes as C
+        v = [C.c_int() for _ in range(3)]
+        self.call('uocr_ctx_last_label', *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
 
     def set_loss_snapshot(self, arena):
         """From now on the fused optimizer tails launched on the CURRENT lane end by copying `arena`'s slots into the next

@@ -509,6 +509,93 @@ def has_nan(x):
     return bool(flag.t.item())
 
 
+# ---- connected components / masked crops (interpreter/interpreter.py: ParagraphCrop) ---------------------------------
+class Components:
+    """Result of label_components.  `.labels` stays on the device; `.count`, `.boxes`, `.area` and `.center_of_mass`
+    (one entry per image) come from ONE device-to-host copy of the component table and the counts, made at the first
+    access.  boxes[n] is (count, 4) = y0, y1, x0, x1, half-open as scipy's find_objects slices; center_of_mass[n] is
+    (count, 2) = (y, x) as ndimage.center_of_mass of each component's boolean mask."""
+
+    def __init__(self, labels, table, count, max_components):
+        self.labels = labels
+        self.max_components = max_components
+        self._table_dev, self._count_dev = table, count
+        self._host = None
+
+    def _fetch(self):
+        if self._host is None:
+            count = self._count_dev.numpy().copy()
+            table = self._table_dev.numpy()
+            if count.size and int(count.max()) > self.max_components:
+                raise HipError(f'label_components: an image has {int(count.max())} components, more than '
+                               f'max_components = {self.max_components}')
+            self._host = count, [table[n, :int(c)].copy() for n, c in enumerate(count)]
+        return self._host
+
+    @property
+    def count(self):
+        return self._fetch()[0]
+
+    @property
+    def table(self):
+        """per image: int64 (count, 8) = first pixel, area, y0, y1, x0, x1, sum of y, sum of x"""
+        return self._fetch()[1]
+
+    @property
+    def boxes(self):
+        return [t[:, 2:6] for t in self.table]
+
+    @property
+    def area(self):
+        return [t[:, 1] for t in self.table]
+
+    @property
+    def center_of_mass(self):
+        return [t[:, 6:8] / np.maximum(t[:, 1:2], 1) for t in self.table]
+
+
+def label_components(x, threshold='mean', max_components=4096):
+    """Connected components of x > t, x of shape (N, H, W, 1): interpreter.py:16-21 with threshold='mean' (t = mean of
+    x), :437-438 / :549 with 'mean_max' (t = (mean + max) / 2), or a number.  Every image is labelled on its own."""
+    if x.ndim != 4 or x.shape[3] != 1:
+        raise ValueError(f'label_components: expected (N, H, W, 1), got {x.shape}')
+    n, h, w, _ = x.shape
+    if isinstance(threshold, str):
+        if threshold not in ('mean', 'mean_max'):
+            raise ValueError(f"label_components: threshold must be 'mean', 'mean_max' or a number, got {threshold!r}")
+        mode, value = (hiplib.THRESH_MEAN if threshold == 'mean' else hiplib.THRESH_MEAN_MAX), 0.0
+    else:
+        mode, value = hiplib.THRESH_VALUE, float(threshold)
+    max_components = int(max_components)
+    labels = CP.empty((n, h, w), np.int32)
+    table = CP.empty((n, max_components, 8), np.int64)
+    count = CP.zeros((n,), np.int32)
+    _rt().call('uocr_label_components', x.code & 0xff, x.ptr, n, h, w, mode, value, labels.ptr, table.ptr,
+               max_components, count.ptr)
+    return Components(labels, table, count, max_components)
+
+
+def masked_crop(array, components, image_index, k, divisible_by=None):
+    """Component k (1-based) of image `image_index`: array * (labels == k) cut to the component's box
+    (interpreter.py:304-308), as a new (1, h, w, C) DeviceArray.  divisible_by=(y, x) also adds make_divisible_by's zero
+    frame (my_model/model.py:26-34: at least one row and column, the crop centred) in the same pass."""
+    n, h, w, c = array.shape
+    if components.labels.shape != (n, h, w):
+        raise ValueError(f'masked_crop: labels {components.labels.shape} do not belong to an array of shape {array.shape}')
+    boxes = components.boxes[image_index]
+    if not 1 <= k <= len(boxes):
+        raise ValueError(f'masked_crop: image {image_index} has components 1..{len(boxes)}, not {k}')
+    y0, y1, x0, x1 = (int(v) for v in boxes[k - 1])
+    ch, cw = y1 - y0, x1 - x0
+    out_h, out_w = ch, cw
+    if divisible_by is not None:
+        out_h, out_w = ch + divisible_by[0] - ch % divisible_by[0], cw + divisible_by[1] - cw % divisible_by[1]
+    out = CP.empty((1, out_h, out_w, c), array.dtype)
+    _rt().call('uocr_masked_crop', array.code & 0xff, array.ptr, components.labels.ptr, n, h, w, c, int(image_index), int(k),
+               y0, x0, ch, cw, out.ptr, out_h, out_w)
+    return out
+
+
 class _Ops:
     add = staticmethod(add)
 
