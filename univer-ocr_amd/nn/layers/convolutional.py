@@ -103,7 +103,7 @@ class Convolutional2D(BaseLayerGPU):
         self.clear_memory()
         return [dx]
 
-    # Upsample2D(2) + this conv evaluated on the low-res tensor (Model._find_ups; csrc/conv_up.hip)
+    # Upsample2D(2) + this conv evaluated on the low-res tensor (nn/plan.py find_ups; csrc/conv_up.hip)
     @track_method('forward')
     def forward_up(self, x_low, activation=None):
         x_low = ops.as_device(x_low)
@@ -142,7 +142,7 @@ class Convolutional2D(BaseLayerGPU):
         return dx
 
     # this conv as the SECOND of conv3x3(1->16)+LeakyReLU+conv3x3(16->1)[+Sigmoid]: one kernel each way
-    # (Model._find_pairs; csrc/conv_pair.hip); `first` is the 1->16 conv whose output is never stored
+    # (nn/plan.py find_pairs; csrc/conv_pair.hip); `first` is the 1->16 conv whose output is never stored
     @track_method('forward')
     def forward_pair(self, X, first, activation, out_activation):
         X = ops.as_device(X)

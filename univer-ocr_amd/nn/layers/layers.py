@@ -398,7 +398,7 @@ class FullyConnected(BaseLayer):
         return dx
 
     # this layer fed by Conv2DToBatchedFixedWidthed + Flatten: one implicit GEMM on the conv feature map
-    # (Model._find_windows; ops.windows_dense_fwd)
+    # (nn/plan.py find_windows; ops.windows_dense_fwd)
     @track_method('forward')
     def forward_windows(self, x, width, activation=None):
         x = ops.as_device(x)

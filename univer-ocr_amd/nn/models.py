@@ -2,11 +2,13 @@
 `Sequential(list)` with forward / backward / compute_loss_and_gradients / train / test / predict /
 params / get_weights / set_weights, nested models flattened to 'parent/child' layer names.
 
-The reference walks the DAG with memoised recursion on every call.  This executor compiles the DAG
-once (`initialize`) into a topologically ordered plan, so forward is a flat loop of asynchronous
-kernel launches on one HIP stream; parameters of the whole model are packed into one flat buffer
-(layers.ParamPack), which turns `clear_grads`, `regularize`, `update_grads`, `nan_weights` and the
-data-parallel gradient all-reduce into one launch each.
+The reference walks the DAG with memoised recursion on every call.  This executor orders the DAG
+once (`initialize`: `_plan`, the topologically ordered node names) and compiles it once, fusions
+included, into a list of steps (nn/plan.py, at the first forward after the graph or its fusion
+flags changed); forward is one loop over that list and backward one loop over it in reverse, each
+a sequence of asynchronous kernel launches on one HIP stream.  Parameters of the whole model are
+packed into one flat buffer (layers.ParamPack), which turns `clear_grads`, `regularize`,
+`update_grads`, `nan_weights` and the data-parallel gradient all-reduce into one launch each.
 
 Semantics kept from the reference:
   * gradients are cleared when the forward pass starts (models.py:188) and again after the
@@ -17,7 +19,7 @@ Semantics kept from the reference:
 """
 import numpy as np
 
-from . import ops
+from . import ops, plan
 from .gpu import CP, DeviceScalar
 from .help_func import make_list_if_not
 from .layers import BaseLayer, ParamPack
@@ -104,6 +106,8 @@ class Model(BaseModel):
         self.layers_outputs = {}
         self.input_grads = {}
         self._skipped_input_grads = False
+        self.fuse_activations, self.fuse_pairs, self.fuse_windows = False, True, True     # enable_fusion
+        self._shapes, self._steps = {}, None          # per-node output shapes; the compiled step list (_compiled)
         self.relations_backward = {}
         self.is_initialized = False
         self._plan = None
@@ -174,7 +178,7 @@ class Model(BaseModel):
         never = [n for n in self.layers if n not in shapes]
         if never:
             print(f'These layers have never been visited: {never}')
-        self._plan = order
+        self._plan, self._shapes = order, shapes
         self._build_pack()
         self.is_initialized = True
 
@@ -183,12 +187,25 @@ class Model(BaseModel):
         dtypes = {p.value.dtype for p in params}
         self._pack = ParamPack(params) if params and len(dtypes) == 1 else None
         self._reg_ranges = None
+        self._steps = None
 
     @property
     def pack(self):
         return self._pack
 
     # -- forward / backward ----------------------------------------------------------------------------
+    def _compiled(self):
+        """The step list (nn/plan.py): built at the first use after initialize / _build_pack / enable_fusion /
+        skip_input_grads, each of which drops it.  It needs an initialised model; a backward runs the list as it is
+        then, so a forward comes between a change of the fusion flags and the next backward (as everywhere here)."""
+        if self._steps is None:
+            def shape_of(src):
+                return self.input_shapes[src] if isinstance(src, int) else self._shapes[src]
+            self._steps = plan.compile_steps(self.layers, self.relations, self.relations_backward, self._plan, shape_of,
+                                             self.outputs_count, self.fuse_activations, self.fuse_pairs,
+                                             self.fuse_windows)
+        return self._steps
+
     @track_method('forward')
     def forward(self, inputs):
         inputs = [ops.as_device(x) for x in make_list_if_not(inputs)]
@@ -196,85 +213,50 @@ class Model(BaseModel):
             self.initialize_from_X(inputs)
         self.clear_param_grads()                      # models.py:188 (per layer there, once here)
         outputs = {}
-        fused_conv, fused_act = self._fusion_maps()
-        pairs = self._active_pairs(inputs)
-        pair_first = {first: second for second, (first, _, _) in pairs.items()}
-        ups = self._active_ups()
-        up_nodes = {up for up, _ in ups.values()}
-        wins = self._active_windows()
-        win_nodes = {n for fw, flat, _ in wins.values() for n in (fw, flat)}
-        for node in self._plan:
-            if node in pair_first or node in up_nodes or node in win_nodes:   # computed inside the kernel of its consumer
-                outputs[node] = None
-                continue
-            if node in wins:                          # windows + flatten + dense on the conv feature map
-                fw = wins[node][0]
-                src = self.relations[fw][0]
-                x = inputs[src] if isinstance(src, int) else outputs[src]
-                if x.shape[3] % 32 == 0:
-                    act = self.layers[fused_conv[node]] if node in fused_conv else None
-                    outputs[node] = self.layers[node].forward_windows(x, self.layers[fw].width, act)
-                    continue
-                for part in (fw, wins[node][1]):      # channel count the implicit GEMM does not take
-                    out = self.layers[part].forward([x])
-                    x = outputs[part] = out[0] if isinstance(out, list) else out
-                wins = {k: v for k, v in wins.items() if k != node}
-            if node in ups:                           # upsample + conv on the low-res tensor
-                src = self.relations[ups[node][0]][0]
-                x_low = inputs[src] if isinstance(src, int) else outputs[src]
-                act = self.layers[fused_conv[node]] if node in fused_conv else None
-                outputs[node] = self.layers[node].forward_up(x_low, act)
-                continue
-            if node in fused_act:                     # activation absorbed into its producing conv
-                outputs[node] = outputs[fused_act[node]]
-                continue
-            if node in pairs:
-                first, act_a, act_b = pairs[node]
-                src = self.relations[first][0]
-                x = inputs[src] if isinstance(src, int) else outputs[src]
-                outputs[node] = self.layers[node].forward_pair(
-                    x, self.layers[first], self.layers[act_a], None if act_b is None else self.layers[act_b])
-                continue
-            args = [inputs[s] if isinstance(s, int) else outputs[s] for s in self.relations[node]]
-            if node in fused_conv:
-                out = self.layers[node].forward_fused(args, self.layers[fused_conv[node]])
-            else:
-                out = self.layers[node].forward(args)
-            outputs[node] = out[0] if isinstance(out, list) else out
+        for step in self._compiled().steps:
+            kind, layer = step.kind, step.layer
+            args = [inputs[s] if isinstance(s, int) else outputs[s] for s in step.sources]
+            if kind == plan.PLAIN:
+                out = layer.forward(args)
+            elif kind == plan.FUSED:                  # activation in the epilogue and / or folded into dx
+                out = layer.forward_fused(args, step.act) if step.act is not None else layer.forward(args)
+            elif kind == plan.ALIAS:                  # activation absorbed into its producing conv
+                out = outputs[step.alias_of]
+            elif kind == plan.PAIR:
+                out = layer.forward_pair(args[0], step.first, step.first_act, step.act)
+            elif kind == plan.UP:                     # upsample + conv on the low-res tensor
+                out = layer.forward_up(args[0], step.act)
+            elif kind == plan.WINDOWS:                # windows + flatten + dense on the conv feature map
+                out = layer.forward_windows(args[0], step.width, step.act)
+            else:                                     # ABSORBED: computed inside the kernel of its consumer
+                out = None
+            outputs[step.node] = out[0] if isinstance(out, list) else out
         for k in range(self.outputs_count):
             src = self.relations[k][0]
             outputs[k] = inputs[src] if isinstance(src, int) else outputs[src]
         self.layers_outputs = outputs
-        self._pairs_used = pairs
-        self._ups_used = ups
-        self._wins_used = wins
         return [outputs[k] for k in range(self.outputs_count)]
 
-    def _active_pairs(self, inputs):
-        """The pair kernels exist in float32 only; other dtypes run the layers one by one."""
-        pairs = getattr(self, '_pairs', {})
-        if pairs and all(self.layers[n].w.value.dtype == np.float32 for n in pairs):
-            return pairs
-        return {}
-
     @track_method('backward')
-    def backward(self, grads):
+    def backward(self, grads, loss_folded=()):
+        """loss_folded: the output activations whose derivative the loss kernel already applied (nodes of
+        StepList.output_sigmoid; _forward_loss_backward passes them)."""
         if self.group_wgrad and CP.has_device():
             with CP.runtime().defer_wgrad():
-                return self._backward_pass(grads)
+                return self._backward_pass(grads, loss_folded)
         rt = CP.runtime() if self.side_wgrad and CP.has_device() else None
         if rt is None:
-            return self._backward_pass(grads)
+            return self._backward_pass(grads, loss_folded)
         # weight gradients go to the side stream of this lane: the chain of dX kernels does not wait for them;
         # they are back before anything reads a parameter gradient (here, and in front of a bucket hook)
         rt.side_on = True
         try:
-            return self._backward_pass(grads)
+            return self._backward_pass(grads, loss_folded)
         finally:
             rt.side_on = False
             rt.join_side()
 
-    def _backward_pass(self, grads):
+    def _backward_pass(self, grads, loss_folded=()):
         grads = [ops.as_device(g) for g in make_list_if_not(grads)]
         grads_mem = {}
 
@@ -287,60 +269,30 @@ class Model(BaseModel):
                 total = ops.add(total, extra)         # models.py:218
             return total
 
-        fused_conv, fused_act = self._fusion_maps()
-        pairs = getattr(self, '_pairs_used', {})
-        pair_first = {first: second for second, (first, _, _) in pairs.items()}
-        ups = getattr(self, '_ups_used', {})
-        up_nodes = {up for up, _ in ups.values()}
-        wins = getattr(self, '_wins_used', {})
-        win_nodes = {n for fw, flat, _ in wins.values() for n in (fw, flat)}
-        for node in reversed(self._plan):
-            if node not in self.relations_backward:
-                continue
-            if node in wins:                          # dW and dX w.r.t. the conv feature map in one go
-                fw, flat, act_in = wins[node]
-                act = self.layers[fused_conv[node]] if node in fused_conv else None
-                dx = self.layers[node].backward_windows(
-                    incoming(node), self.layers[fw].width, act,
-                    act_grad_applied=act is not None and self._act_folded(fused_conv[node]),
-                    input_activation=None if act_in is None else self.layers[act_in])
-                grads_mem[node] = [None]
-                grads_mem[flat] = [None]
-                grads_mem[fw] = [dx]
-            elif node in win_nodes:
-                grads_mem.setdefault(node, [None])
-            elif node in ups:                           # dW, and dX w.r.t. the LOW-RES input, in one go
-                up_node, act_in = ups[node]
-                act = self.layers[fused_conv[node]] if node in fused_conv else None
-                dx_low = self.layers[node].backward_up(
-                    incoming(node), act, act_grad_applied=act is not None and self._act_folded(fused_conv[node]),
-                    input_activation=None if act_in is None else self.layers[act_in])
-                grads_mem[node] = [None]
-                grads_mem[up_node] = [dx_low]
-            elif node in up_nodes:
-                grads_mem.setdefault(node, [None])
-            elif node in pairs:                         # dW of both convs and dX of the first in one kernel
-                first, act_a, act_b = pairs[node]
-                folded = act_b is None or act_b in getattr(self, '_loss_folded', ())    # Sigmoid' already in the loss gradient
-                dx = self.layers[node].backward_pair(
-                    incoming(node), self.layers[first], self.layers[act_a], None if folded else self.layers[act_b])
-                grads_mem[node] = [None]
-                grads_mem[first] = [dx]
-            elif node in pair_first or (node in fused_act and fused_act[node] in pair_first):
-                grads_mem.setdefault(node, [None])
-            elif node in fused_act:                   # its gradient is applied inside a conv's backward
-                grads_mem[node] = [incoming(node)]
-            elif node in fused_conv or node in self._fusion[2]:
-                act = self.layers[fused_conv[node]] if node in fused_conv else None
-                folded = node in fused_conv and self._act_folded(fused_conv[node])
-                in_act = self._fusion[2].get(node)
-                grads_mem[node] = make_list_if_not(self.layers[node].backward_fused(
-                    incoming(node), act, act_grad_applied=folded,
-                    input_activation=None if in_act is None else self.layers[in_act]))
-            else:
-                grads_mem[node] = make_list_if_not(self.layers[node].backward(incoming(node)))
+        for step in reversed(self._compiled().steps):
+            kind, layer = step.kind, step.layer
+            if kind == plan.PLAIN:
+                dx = layer.backward(incoming(step.node))
+            elif kind == plan.ALIAS:                  # its gradient is applied inside a conv's backward
+                dx = incoming(step.node)
+            elif kind == plan.PAIR:                   # dW of both convs and dX of the first in one kernel; only the
+                act = None if step.act_node in loss_folded else step.act     # loss kernel can take its Sigmoid over
+                dx = layer.backward_pair(incoming(step.node), step.first, step.first_act, act)
+            elif kind != plan.ABSORBED:               # (an absorbed node's gradient never exists)
+                grad, act = incoming(step.node), step.act
+                # the epilogue activation's derivative: here, unless a consumer's dx kernel or the loss kernel applies it
+                applied = act is not None and (step.act_folded or step.act_node in loss_folded)
+                folds = {'act_grad_applied': applied, 'input_activation': step.in_act}
+                if kind == plan.FUSED:
+                    dx = layer.backward_fused(grad, act, **folds)
+                elif kind == plan.UP:                 # dW, and dX w.r.t. the LOW-RES input, in one go
+                    dx = layer.backward_up(grad, act, **folds)
+                else:                                 # WINDOWS: dW and dX w.r.t. the conv feature map in one go
+                    dx = layer.backward_windows(grad, step.width, act, **folds)
+            if kind != plan.ABSORBED:
+                grads_mem[step.grad_node] = make_list_if_not(dx)
             if self.bucket_hook is not None:          # data parallel: part of the gradient may be final now
-                self.bucket_hook(self, node)
+                self.bucket_hook(self, step.node)
         if self._skipped_input_grads:
             self.input_grads = {}
             return []
@@ -359,9 +311,10 @@ class Model(BaseModel):
         for n in firsts:
             self.layers[n].needs_input_grad = not on
         self._skipped_input_grads = bool(on)
+        self._steps = None
         return self
 
-    # -- conv + activation fusion (graph level; reference: none -- every layer is its own pass) -----
+    # -- graph-level fusion (nn/plan.py; reference: none -- every layer is its own pass) ------------
     def enable_fusion(self, on=True, pairs=True, windows=True):
         """Run every Convolutional2D whose ONLY consumer is a LeakyRelu(alpha > 0) / Sigmoid as one
         kernel with the activation in the epilogue.  Results are the same tensors the unfused graph
@@ -370,172 +323,17 @@ class Model(BaseModel):
         self.fuse_activations = bool(on)
         self.fuse_pairs = bool(pairs)        # also run conv(1->16)+LeakyReLU+conv(16->1) blocks as one kernel
         self.fuse_windows = bool(windows)    # and windows + flatten + dense as one implicit GEMM
-        self._fusion = None
+        self._steps = None
         return self
 
+    # read-only views of the compiled steps, by node name (plan.StepList; the find_* functions there give the values)
     def _fusion_maps(self):
-        if not getattr(self, 'fuse_activations', False):
-            self._fusion = ({}, {}, {}, set())
-            self._pairs = {}
-            self._ups = {}
-            self._wins = {}
-            return {}, {}
-        if self._fusion is None:
-            from .layers import Convolutional2D, FullyConnected, LeakyRelu, Sigmoid
-            fused_conv, fused_act = {}, {}           # ("conv": Convolutional2D or FullyConnected)
-            for node in self._plan:
-                layer = self.layers[node]
-                consumers = self.relations_backward.get(node, {})
-                if not isinstance(layer, (Convolutional2D, FullyConnected)) or len(consumers) != 1:
-                    continue
-                (dst, _), = consumers.items()
-                if isinstance(dst, int) or self.relations[dst] != [node]:
-                    continue
-                act = self.layers[dst]
-                ok = isinstance(act, Sigmoid) or (isinstance(act, LeakyRelu) and act.alpha > 0)
-                if ok and type(act) in (Sigmoid, LeakyRelu):
-                    fused_conv[node] = dst
-                    fused_act[dst] = node
-            # a fused activation whose ONLY consumer is a conv: that conv's dx kernel multiplies by the
-            # activation's derivative in its epilogue (input_of[conv] = act), and the producing conv
-            # skips its own activation-gradient pass (folded)
-            input_of, folded = {}, set()
-            for act_node in fused_act:
-                consumers = self.relations_backward.get(act_node, {})
-                if len(consumers) != 1:
-                    continue
-                (dst, _), = consumers.items()
-                if not isinstance(dst, int) and isinstance(self.layers[dst], (Convolutional2D, FullyConnected)) and \
-                        self.relations[dst] == [act_node]:
-                    input_of[dst] = act_node
-                    folded.add(act_node)
-            self._fusion = (fused_conv, fused_act, input_of, folded)
-            self._pairs = self._find_pairs(fused_conv, input_of) if getattr(self, 'fuse_pairs', True) else {}
-            self._ups = self._find_ups(fused_act) if getattr(self, 'fuse_pairs', True) else {}
-            self._wins = self._find_windows(fused_act) if getattr(self, 'fuse_windows', True) else {}
-        return self._fusion[0], self._fusion[1]
+        """({conv or dense: its fused activation}, {fused activation: its producer})"""
+        return self._compiled().fused_conv, self._compiled().fused_act
 
-    def _find_windows(self, fused_act):
-        """Conv2DToBatchedFixedWidthed feeding only a Flatten feeding only a FullyConnected -- the bridge
-        between the conv block and the dense block of the Char net (my_model/model.py:250-304) -- runs as one
-        implicit GEMM on the conv feature map (ops.windows_dense_fwd): the 8x larger windows tensor and its
-        gradient are never built.  Returns {dense: (windows node, flatten node, fused activation that feeds only
-        the windows layer, or None)}; that activation's backward is folded into the dx epilogue."""
-        from .layers import Conv2DToBatchedFixedWidthed, Flatten, FullyConnected
-
-        def only_consumer(node, kind):
-            consumers = self.relations_backward.get(node, {})
-            if len(consumers) != 1:
-                return None
-            (dst, _), = consumers.items()
-            if isinstance(dst, int) or self.relations[dst] != [node] or not isinstance(self.layers[dst], kind):
-                return None
-            return dst
-
-        wins = {}
-        for node in self._plan:
-            if not isinstance(self.layers[node], Conv2DToBatchedFixedWidthed):
-                continue
-            flat = only_consumer(node, Flatten)
-            dense = only_consumer(flat, FullyConnected) if flat is not None else None
-            if dense is None:
-                continue
-            src = self.relations[node]
-            act_in = None
-            if len(src) == 1 and src[0] in fused_act and len(self.relations_backward.get(src[0], {})) == 1:
-                act_in = src[0]
-            wins[dense] = (node, flat, act_in)
-        return wins
-
-    def _active_windows(self):
-        """float32 with channel counts the MFMA implicit GEMM takes (the generic conv kernels would be slower
-        than the three separate layers)."""
-        wins = getattr(self, '_wins', {})
-        out = {}
-        for dense, v in wins.items():
-            layer = self.layers[dense]
-            if layer.is_initialized and layer.w.value.dtype == np.float32 and layer.n_output % 32 == 0 and \
-                    layer.n_input % (32 * self.layers[v[0]].width) == 0:
-                out[dense] = v
-        return out
-
-    def _find_ups(self, fused_act):
-        """Upsample2D(2) feeding only a 5x5 / stride 1 / padding 2 Convolutional2D with 4->4 or 1->1 channels -- the
-        decoder blocks of the Line and Paragraph nets (my_model/model.py:138-247) -- runs as one op on the low-res tensor (csrc/conv_up.hip);
-        the upsampled tensor is never built.  Returns {conv: (upsample node, fused activation that feeds only
-        this upsample, or None)}; that activation's backward is folded into the op's dx epilogue."""
-        from .layers import Convolutional2D, Upsample2D
-        ups = {}
-        for node in self._plan:
-            layer = self.layers[node]
-            consumers = self.relations_backward.get(node, {})
-            if not isinstance(layer, Upsample2D) or tuple(layer.scale_factor) != (2, 2) or len(consumers) != 1:
-                continue
-            (dst, _), = consumers.items()
-            if isinstance(dst, int) or self.relations[dst] != [node]:
-                continue
-            conv = self.layers[dst]
-            if not (isinstance(conv, Convolutional2D) and conv.kernel_size == (5, 5) and conv.stride == (1, 1)
-                    and conv.padding == (2, 2) and conv.padding_value == 0
-                    and (conv.in_channels, conv.out_channels) in ((4, 4), (1, 1))):
-                continue
-            src = self.relations[node]
-            act_in = None
-            if len(src) == 1 and src[0] in fused_act and len(self.relations_backward.get(src[0], {})) == 1:
-                act_in = src[0]
-            ups[dst] = (node, act_in)
-        return ups
-
-    def _active_ups(self):
-        """float32 only, like the pair kernels."""
-        ups = getattr(self, '_ups', {})
-        return {conv: v for conv, v in ups.items() if self.layers[conv].w.value.dtype == np.float32}
-
-    def _act_folded(self, act_node):
-        """Is the backward of this fused activation applied by its consumer (a conv's dx kernel, or the
-        loss kernel for an output Sigmoid)?"""
-        return act_node in self._fusion[3] or act_node in getattr(self, '_loss_folded', ()) or \
-            any(a == act_node for _, a in getattr(self, '_ups_used', {}).values()) or \
-            any(a == act_node for _, _, a in getattr(self, '_wins_used', {}).values())
-
-    def _foldable_output_sigmoid(self, key):
-        """Model output `key` = a Sigmoid fused into its conv (or into a pair kernel) and consumed by nothing else: its
-        backward can move into the loss-gradient kernel (an elementwise, HBM-bound kernel that reads the prediction
-        anyway; the pair backward is bound by vector issue and saves the loads of y and three instructions per
-        position: 181 -> 167 us at 8 x 1024 x 2048 in float16)."""
-        from .layers import Sigmoid
-        node = self.relations[key][0]
-        fused_act = self._fusion[1] if self._fusion else {}
-        if isinstance(node, int) or node not in fused_act or not isinstance(self.layers[node], Sigmoid):
-            return None
-        if len(self.relations_backward.get(node, {})) != 1:
-            return None
-        return node
-
-    def _find_pairs(self, fused_conv, input_of):
-        """conv3x3(1->16, pad 1) + LeakyReLU feeding only conv3x3(16->1, pad 1) [+ Sigmoid] -- the
-        Monochrome block (my_model/model.py:108-135) -- runs as ONE forward and ONE backward kernel
-        (csrc/conv_pair.hip) that never writes the 16-channel activation or its gradient to HBM.
-        Returns {second conv: (first conv, its LeakyReLU, the second conv's fused activation or None)}."""
-        from .layers import LeakyRelu, Sigmoid
-        pairs = {}
-        from .layers import Convolutional2D
-        for conv_b, act_a in input_of.items():
-            conv_a = self._fusion[1][act_a]
-            a, b, act = self.layers[conv_a], self.layers[conv_b], self.layers[act_a]
-            if not isinstance(act, LeakyRelu) or not (isinstance(a, Convolutional2D) and isinstance(b, Convolutional2D)):
-                continue
-            if not 0.0 <= act.alpha <= 1.0:               # the fused kernels take LeakyReLU as max(z, alpha z)
-                continue
-            same = all(l.kernel_size == (3, 3) and l.stride == (1, 1) and l.padding == (1, 1) for l in (a, b))
-            if not (same and (a.in_channels, a.out_channels, b.in_channels, b.out_channels) == (1, 16, 16, 1)
-                    and b.padding_value == 0):
-                continue
-            act_b = fused_conv.get(conv_b)
-            if act_b is not None and not isinstance(self.layers[act_b], Sigmoid):
-                continue
-            pairs[conv_b] = (conv_a, act_a, act_b)
-        return pairs
+    _pairs_used = property(lambda self: self._compiled().pairs)    # {second conv: (first conv, LeakyReLU, Sigmoid / None)}
+    _ups_used = property(lambda self: self._compiled().ups)        # {conv: (upsample, activation folded into dx / None)}
+    _wins_used = property(lambda self: self._compiled().wins)      # {dense: (windows, flatten, the same / None)}
 
     def _loss_func(self, key):
         return self.loss[key] if isinstance(self.loss, list) else self.loss
@@ -543,20 +341,20 @@ class Model(BaseModel):
     def _forward_loss_backward(self, X, y):
         predicted = self.forward(make_list_if_not(X))
         y = make_list_if_not(y)
-        losses, gradients = [], []
-        self._loss_folded = set()
-        for key in range(self.outputs_count):
-            func, act_node = self._loss_func(key), self._foldable_output_sigmoid(key)
+        losses, gradients, loss_folded = [], [], set()
+        for key, act_node in enumerate(self._compiled().output_sigmoid):
+            func = self._loss_func(key)
             if act_node is not None and getattr(func, 'folds_sigmoid', False):
-                # the loss kernel writes the gradient w.r.t. the INPUT of the fused output Sigmoid
+                # the loss kernel (elementwise, HBM-bound, reads the prediction anyway) writes the gradient w.r.t. the
+                # INPUT of the fused output Sigmoid; the pair backward, bound by vector issue, saves the loads of y and
+                # three instructions per position (181 -> 167 us at 8 x 1024 x 2048 in float16)
                 loss, grad = func(predicted[key], ops.as_device(y[key]), out_act='sigmoid')
-                self._loss_folded.add(act_node)
+                loss_folded.add(act_node)
             else:
                 loss, grad = func(predicted[key], ops.as_device(y[key]))
             losses.append(loss)
             gradients.append(grad)
-        self.backward(gradients)
-        self._loss_folded = set()
+        self.backward(gradients, loss_folded)
         if self.grad_sync is not None:
             self.grad_sync(self)                      # data parallel: RCCL all-reduce of pack.grad
         return losses
@@ -596,10 +394,10 @@ class Model(BaseModel):
         """The three calls that end a train step (models.py:252-254: regularize via compute_loss_and_gradients,
         update_grads, clear_grads) as ONE kernel over the flat pack when the whole model is trained by one
         Momentum or Adam optimizer and has at most 4 L1/L2 ranges; None = not applicable, run them one by one."""
-        plan = self._fused_tail_plan()
-        if plan is None:
+        tail = self._fused_tail_plan()
+        if tail is None:
             return None
-        optimizer, pack, ranges = plan
+        optimizer, pack, ranges = tail
         return optimizer.update_pack_fused(pack, ranges)
 
     def _fused_tail_plan(self):
