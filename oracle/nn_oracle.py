@@ -521,6 +521,101 @@ class Net:
         return {'output_losses': [loss]}, pred
 
 
+# ----------------------------------------------------------------------------
+# graphs: Model.compute_loss_and_gradients / train of models.py:187-254 for a DAG of layers
+# ----------------------------------------------------------------------------
+class Graph:
+    """`layers` {name: (kind, cfg)} and `relations` {name or output number: source or [sources]} as Model takes them
+    (a source is a model input number or a layer name; models.py:7-53).  kind / cfg as in Net, plus 'concat'
+    (cfg: axis) and an `l1` strength beside `l2`.  `loss`: one name of LOSSES, or one per output.  A node consumed by
+    several nodes or outputs gets the sum of their gradients (models.py:218).  Every node is evaluated by the
+    functions above, through a one-layer Net that shares `params`."""
+
+    def __init__(self, layers, relations, loss):
+        self.layers = dict(layers)
+        self.relations = {dst: list(src) if isinstance(src, (list, tuple)) else [src] for dst, src in relations.items()}
+        self.outputs = sorted(k for k in self.relations if isinstance(k, int))
+        self.loss = loss if isinstance(loss, (list, tuple)) else [loss] * len(self.outputs)
+        self.n_inputs = 1 + max(s for srcs in self.relations.values() for s in srcs if isinstance(s, int))
+        self.params, self.grads = {}, {}
+        self.order = []
+        for out in self.outputs:
+            self._visit(out)
+        self._nets = {n: Net([(n, *self.layers[n])], None) for n in self.order if self.layers[n][0] != 'concat'}
+
+    def _visit(self, node):
+        for src in self.relations[node]:
+            if not isinstance(src, int) and src not in self.order:
+                self._visit(src)
+        if not isinstance(node, int) and node not in self.order:
+            self.order.append(node)
+
+    def param_names(self):
+        return sorted(self.params.keys())
+
+    def forward(self, Xs, keep=False):
+        """Returns the model outputs; keep=True: also every node's output and what its backward needs."""
+        values, stash = {}, {}
+        for node in self.order:
+            ins = [Xs[s] if isinstance(s, int) else values[s] for s in self.relations[node]]
+            if node in self._nets:
+                self._nets[node].params = self.params
+                values[node], stash[node] = self._nets[node].forward(ins[0], keep=True)
+            else:
+                values[node], stash[node] = concat_fwd(ins, self.layers[node][1].get('axis', -1)), [x.shape for x in ins]
+        preds = [Xs[s] if isinstance(s, int) else values[s] for s in (self.relations[k][0] for k in self.outputs)]
+        return (preds, values, stash) if keep else preds
+
+    def backward(self, gs, stash):
+        """Returns ([gradient w.r.t. input k, None where nothing reaches it], {param: gradient})."""
+        total, grads = {}, {}
+
+        def add(src, g):
+            total[src] = total[src] + g if src in total else g
+        for k, g in zip(self.outputs, gs):
+            add(self.relations[k][0], g)
+        for node in reversed(self.order):
+            if node in self._nets:
+                dx, own = self._nets[node].backward(total[node], stash[node])
+                grads.update(own)
+                parts = [dx]
+            else:
+                parts = concat_bwd(total[node], stash[node], self.layers[node][1].get('axis', -1))
+            for src, part in zip(self.relations[node], parts):
+                add(src, part)
+        return [total.get(k) for k in range(self.n_inputs)], grads
+
+    def loss_and_grads(self, Xs, ys):
+        """compute_loss_and_gradients (models.py:232-248): ({'output_losses', 'regularization_loss'}, outputs,
+        input gradients); the parameter gradients, regularisation included, are left in `grads`."""
+        preds, _, stash = self.forward(Xs, keep=True)
+        found = [LOSSES[name](pred, y) for name, pred, y in zip(self.loss, preds, ys)]
+        dxs, grads = self.backward([g for _, g in found], stash)
+        reg = 0.0
+        for pn in grads:
+            cfg = self.layers[pn.rsplit('/', 1)[0]][1]
+            for func, strength in ((l1_reg, cfg.get('l1')), (l2_reg, cfg.get('l2'))):
+                if strength:
+                    rl, rg = func(self.params[pn], strength)
+                    grads[pn] = grads[pn] + rg
+                    reg += rl
+        self.grads = grads
+        return {'output_losses': [loss for loss, _ in found], 'regularization_loss': reg}, preds, dxs
+
+    def train_step(self, Xs, ys, optimizer):
+        losses, preds, _ = self.loss_and_grads(Xs, ys)
+        for pn, g in self.grads.items():
+            self.params[pn] = optimizer.update(pn, self.params[pn], g)
+        return losses, preds
+
+
+def make_graph(layers, relations, loss, weights=None):
+    graph = Graph(layers, relations, loss)
+    spec = [(name, kind, cfg) for name, (kind, cfg) in layers.items()]
+    graph.params = dict(analytic_net_weights(spec) if weights is None else weights)
+    return graph
+
+
 # my_model nets (my_model/model.py:108-304) as chains; names = unravelled layer names
 def _conv_block(prefix, chans, cin, last_sigmoid, ks, padding, stride=1):
     """model.py:42-59 make_conv_block with make_conv's L2(0.01) (:36-39)."""

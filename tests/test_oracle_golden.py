@@ -272,3 +272,64 @@ def test_model_system_list_path_oracle():
                 close(value, g[key], 1e-10)
             else:
                 close(value.reshape(-1)[::97], g[key + '@stride97'], 1e-10)
+
+
+def dag_graph():
+    """test_gradients.py:225-259: three conv branches -> Concat -> MaxPool -> Flatten -> two dense heads."""
+    conv = dict(ks=(2, 2), cin=1, cout=3, stride=1, padding=0)
+    layers = {'conv1': ('conv', conv), 'conv2': ('conv', conv), 'conv3': ('conv', conv), 'concat': ('concat', {}),
+              'pool': ('maxpool', dict(ks=2)), 'flatten': ('flatten', {}),
+              'dense1': ('dense', dict(n_in=36, n_out=3)), 'dense2': ('dense', dict(n_in=3, n_out=3))}
+    relations = {'conv1': 0, 'conv2': 1, 'conv3': 2, 'concat': ['conv1', 'conv2', 'conv3'], 'pool': 'concat',
+                 'flatten': 'pool', 'dense1': 'flatten', 'dense2': 'dense1', 0: 'dense1', 1: 'dense2'}
+    return O.make_graph(layers, relations, 'sigmoid_ce')
+
+
+def nested_graph():
+    """test_gradients.py:261-308 with its Sequential sub-models flattened to 'parent/child' names (models.py:109-158):
+    both inputs consumed twice, Concat of model inputs, L2 on each first conv and L1 on each second."""
+    layers, relations = {}, {}
+
+    def sub(name, source, cin, cout):
+        layers[f'{name}/0_Convolutional2D'] = ('conv', dict(ks=(2, 2), cin=cin, cout=cout, stride=1, padding=0, l2=0.1))
+        layers[f'{name}/1_Convolutional2D'] = ('conv', dict(ks=(2, 2), cin=cout, cout=cout, stride=1, padding=0, l1=0.1))
+        layers[f'{name}/2_MaxPool2D'] = ('maxpool', dict(ks=(2, 2)))
+        relations.update({f'{name}/0_Convolutional2D': source, f'{name}/1_Convolutional2D': f'{name}/0_Convolutional2D',
+                          f'{name}/2_MaxPool2D': f'{name}/1_Convolutional2D'})
+        return f'{name}/2_MaxPool2D'
+    rows = [sub('row_1', 0, 3, 2), sub('row_2', 1, 3, 3)]
+    for name in ('concat_rows', 'concat_inputs', 'concat_all'):
+        layers[name] = ('concat', {})
+    relations.update({'concat_rows': rows, 'concat_inputs': [0, 1]})
+    relations['concat_all'] = ['concat_rows', sub('row_inputs', 'concat_inputs', 6, 2)]
+    layers.update({'pool_1': ('maxpool', dict(ks=(2, 2))), 'pool_2': ('maxpool', dict(ks=(2, 2))),
+                   'conv_end': ('conv', dict(ks=(2, 2), cin=7, cout=3, stride=1, padding=0))})
+    relations.update({'pool_1': 'concat_all', 'pool_2': 'pool_1', 'conv_end': 'pool_2', 0: 'conv_end'})
+    return O.make_graph(layers, relations, 'dice')
+
+
+def test_graph_evaluator_reproduces_the_reference_dags():
+    """oracle.Graph (a DAG of the layer functions above, gradients of a node with several consumers summed) against
+    the reference's own Model on the multi-input / multi-output DAG and on the nested model with L1 / L2."""
+    g = load_golden('graph_models')
+    graph = dag_graph()
+    assert graph.param_names() == sorted(str(s) for s in g['dag/param_names'])
+    losses, preds, dxs = graph.loss_and_grads([g[f'dag/X{i}'] for i in range(3)], [g[f'dag/y{i}'] for i in range(2)])
+    close(np.array(losses['output_losses']), g['dag/loss'])
+    for i in range(2):
+        close(preds[i], g[f'dag/pred{i}'])
+    for i in range(3):
+        close(dxs[i], g[f'dag/input_grad{i}'])
+    for pn in graph.param_names():
+        close(graph.grads[pn], g[f'dag/grad/{pn}'])
+
+    graph = nested_graph()
+    assert sorted(graph.layers) == [str(s) for s in g['nested/layer_names']]
+    assert graph.param_names() == sorted(str(s) for s in g['nested/param_names'])
+    losses, preds, dxs = graph.loss_and_grads([g['nested/X0'], g['nested/X1']], [g['nested/y']])
+    close(np.array([*losses['output_losses'], losses['regularization_loss']]), g['nested/loss'])
+    close(preds[0], g['nested/pred'])
+    for i in range(2):
+        close(dxs[i], g[f'nested/input_grad{i}'])
+    for pn in graph.param_names():
+        close(graph.grads[pn], g[f'nested/grad/{pn}'])

@@ -73,8 +73,8 @@ class _Graph:
         """Every Convolutional2D / FullyConnected whose ONLY consumer is a LeakyRelu(alpha > 0) / Sigmoid runs with it
         in the epilogue.  A fused activation whose ONLY consumer is again such a layer: that layer's dx kernel
         multiplies by the activation's derivative (input_of[layer] = act), and the producer skips its own
-        activation-gradient pass (folded)."""
-        fused_conv, fused_act, input_of, folded = {}, {}, {}, set()
+        activation-gradient pass (the activation is folded: compile_steps)."""
+        fused_conv, fused_act, input_of = {}, {}, {}
         for node in self.order:
             if not isinstance(self.layers[node], (Convolutional2D, FullyConnected)):
                 continue
@@ -87,8 +87,7 @@ class _Graph:
             dst = self.only_consumer(act_node, (Convolutional2D, FullyConnected))
             if dst is not None:
                 input_of[dst] = act_node
-                folded.add(act_node)
-        return fused_conv, fused_act, input_of, folded
+        return fused_conv, fused_act, input_of
 
     def find_pairs(self, fused_conv, fused_act, input_of):
         """conv3x3(1->16, pad 1) + LeakyReLU feeding only conv3x3(16->1, pad 1) [+ Sigmoid] -- the Monochrome block
@@ -157,11 +156,18 @@ def compile_steps(layers, relations, consumers, order, shape_of, outputs_count, 
     """layers / relations / consumers (= relations_backward) / order (= _plan) of an initialised Model;
     shape_of(source) -> the shape `initialize` propagated to a model input or a node's output."""
     graph = _Graph(layers, relations, consumers, order)
-    fused_conv, fused_act, input_of, folded = graph.find_activations() if fuse_activations else ({}, {}, {}, set())
+    fused_conv, fused_act, input_of = graph.find_activations() if fuse_activations else ({}, {}, {})
     pairs = graph.find_pairs(fused_conv, fused_act, input_of) if fuse_activations and fuse_pairs else {}
-    ups = graph.find_ups(fused_act) if fuse_activations and fuse_pairs else {}
-    wins = graph.find_windows(fused_act, shape_of) if fuse_activations and fuse_windows else {}
-    folded = folded | {v[-1] for v in list(ups.values()) + list(wins.values()) if v[-1] is not None}
+    # nothing folds across the edge of a pair: its backward kernel applies the derivative of its own Sigmoid and of no
+    # activation in front of its first conv, so that Sigmoid folds into no consumer and the activation in front keeps
+    # its derivative with its producer
+    pair_out = {act_b for _, _, act_b in pairs.values()} - {None}
+    pair_first = {first for first, _, _ in pairs.values()}
+    input_of = {dst: act for dst, act in input_of.items() if act not in pair_out and dst not in pair_first}
+    foldable = {act: conv for act, conv in fused_act.items() if act not in pair_out}
+    ups = graph.find_ups(foldable) if fuse_activations and fuse_pairs else {}
+    wins = graph.find_windows(foldable, shape_of) if fuse_activations and fuse_windows else {}
+    folded = set(input_of.values()) | {v[-1] for v in list(ups.values()) + list(wins.values()) if v[-1] is not None}
     absorbed = {n for first, act_a, _ in pairs.values() for n in (first, act_a)} | {up for up, _ in ups.values()} | \
         {n for fw, flat, _ in wins.values() for n in (fw, flat)}
 
@@ -172,7 +178,7 @@ def compile_steps(layers, relations, consumers, order, shape_of, outputs_count, 
         epilogue = dict(act_node=act_node, act=layers.get(act_node), act_folded=act_node in folded)
         if node in absorbed:
             step = Step(ABSORBED, node, layer)
-        elif node in pairs:                                # (the pair's backward takes no word from a consumer conv)
+        elif node in pairs:                                # (its Sigmoid is never folded: see above)
             first, act_a, _ = pairs[node]
             step = Step(PAIR, node, layer, relations[first], (first, act_a), first=layers[first],
                         first_act=layers[act_a], **dict(epilogue, act_folded=False))
