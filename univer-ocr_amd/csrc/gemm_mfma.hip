@@ -126,6 +126,18 @@ struct BRowMajor {
         code = in ? LD_KEEP : LD_ZERO;
         return *reinterpret_cast<const F4*>(in ? b + (long)d * ld + j : b);
     }
+    // The same load from a POSITION: the address of the thread's group in the first depth row it loads is built once per
+    // block, a later row is a block-uniform distance away (scalar arithmetic) -- no 64-bit multiply per load.
+    struct Pos {
+        const float* p;
+        bool col_ok;
+    };
+    __device__ __forceinline__ Pos pos(int d, int j) const { return Pos{b + (long)d * ld + j, j < n}; }
+    __device__ __forceinline__ F4 load_at(const Pos& c, long rows_on, int d, int& code) const {
+        const bool in = c.col_ok && d < rows;
+        code = in ? LD_KEEP : LD_ZERO;
+        return *reinterpret_cast<const F4*>(in ? c.p + rows_on * ld : b);
+    }
     __device__ __forceinline__ F4 load_slow(int d, int j) const {
         if (d >= rows || j >= n) return f4_zero();
         const float* p = b + (long)d * ld + j;
@@ -159,6 +171,22 @@ struct BDepthContig {
         const bool in = j < n && d0 < depth;
         code = in ? LD_KEEP : LD_ZERO;
         return *reinterpret_cast<const F4*>(in ? at(d0, j) : b);
+    }
+    // The same load from a POSITION, for operands whose depth tiles never straddle two segments (conv: cout % 32 == 0;
+    // dense: one segment): the segment of a tile is block-uniform, and so is the distance from the thread's group in
+    // depth tile 0 to its group in tile t.
+    struct Pos {
+        const float* p;        // column j, depth kq * 4 of the first segment
+        bool col_ok;
+    };
+    __device__ __forceinline__ bool tiles_in_segments() const { return rows == 0 || by_seg.d % BD == 0; }
+    __device__ __forceinline__ Pos pos(int j, int kq) const { return Pos{b + (long)j * ld + kq * 4, j < n}; }
+    __device__ __forceinline__ F4 load_at(const Pos& c, int tile, int d0, int& code) const {
+        const int kk = rows == 0 ? 0 : by_seg.div(tile * BD);                       // (scalar)
+        const long on = (long)kk * rows * ld + (tile * BD - kk * by_seg.d);          // (scalar)
+        const bool in = c.col_ok && d0 < depth;
+        code = in ? LD_KEEP : LD_ZERO;
+        return *reinterpret_cast<const F4*>(in ? c.p + on : b);
     }
     __device__ __forceinline__ F4 load_slow(int j, int d0) const {
         F4 r = f4_zero();
@@ -449,6 +477,18 @@ __device__ __forceinline__ void gemm_block_coords(int lin, int gx, int gy, int g
 }
 
 // one block's share of C = A . B: output tile (bx, by), depth slice bz; As / Bs: this block's LDS
+//
+// On gfx950 the vector instructions of a wave are paid in MFMA time, and a Char-net block runs only ~5
+// depth tiles, so prologue, loop and epilogue are all kept short of vector work:
+//   * the depth-tile loop exists twice: `run(fast)` with 16-byte loads only, which almost every launch takes, and the
+//     loop with the element-wise loads of unaligned / ragged operands; the choice is block-uniform and made once;
+//   * B is read from a POSITION (the loaders' `pos` / `load_at`): the thread's address in the first tile is built once,
+//     the distance to a later tile is block-uniform scalar arithmetic (tap changes, skipped tiles and a slab that starts
+//     inside a tap are all just another scalar distance) -- no 64-bit multiply or division per load;
+//   * the epilogue addresses an element as a wave-uniform 64-bit part plus one 32-bit register per lane, tests the
+//     bounds once per wave, and picks the form of the epilogue (slab / plain store, bias + ReLU kind, mask) outside the
+//     16-element loops.
+// (tools/isa_loop_stats.py prints the instruction mix of the loops from the assembly.)
 template <int BM, typename ALoader, typename BLoader>
 __device__ __forceinline__ void gemm_tile(const ALoader& A, const BLoader& B, const Epilogue& ep, int M, int N, int ntiles,
                                           int tiles_per_split, float* slabs, int bx, int by, int bz, float* As,
@@ -503,8 +543,20 @@ __device__ __forceinline__ void gemm_tile(const ALoader& A, const BLoader& B, co
             for (int sidx = 0; sidx < AM_PASSES; ++sidx) cursors[sidx] = A.cursor_at(t_begin * BD + a_pr + AM_ROWS * sidx);
         }
     }
-    auto load_tile = [&](int t) {
-        if (a_slow) {             // unaligned rows or ragged groups: element loads (block-uniform choice)
+    // positions of the thread's two B groups (the loaders' load_at)
+    typename BLoader::Pos bpos[2];
+    bool b_pos = true;
+    if constexpr (BLoader::DEPTH_CONTIG) {
+        b_pos = B.tiles_in_segments();
+#pragma unroll
+        for (int s = 0; s < 2; ++s) bpos[s] = B.pos(n0 + b_r + 32 * s, b_kq);
+    } else {
+        bpos[0] = B.pos(t_begin * BD + b_kr, n0 + b_nq * 4);
+    }
+    // `fast`: every operand takes 16-byte loads (block-uniform).  The depth-tile loop exists twice, and the one almost
+    // every launch runs holds no element-wise code.
+    auto load_tile = [&](auto fast, int t) {
+        if (!fast.value && a_slow) {             // unaligned rows or ragged groups: element loads
             if constexpr (ALoader::HAS_SLOW) {
 #pragma unroll
                 for (int s = 0; s < A_REGS; ++s) {
@@ -536,12 +588,14 @@ __device__ __forceinline__ void gemm_tile(const ALoader& A, const BLoader& B, co
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             if constexpr (BLoader::DEPTH_CONTIG) {
-                if (B.vec_ok) breg[s] = B.load(n0 + b_r + 32 * s, t * BD + b_kq * 4, bcode[s]);
+                if (fast.value && b_pos) breg[s] = B.load_at(bpos[s], t, t * BD + b_kq * 4, bcode[s]);
+                else if (fast.value || B.vec_ok) breg[s] = B.load(n0 + b_r + 32 * s, t * BD + b_kq * 4, bcode[s]);
                 else {
                     breg[s] = B.load_slow(n0 + b_r + 32 * s, t * BD + b_kq * 4);
                     bcode[s] = LD_KEEP;
                 }
-            } else if (B.vec_ok) breg[s] = B.load(t * BD + b_kr + 16 * s, n0 + b_nq * 4, bcode[s]);
+            } else if (fast.value) breg[s] = B.load_at(bpos[0], (t - t_begin) * BD + 16 * s, t * BD + b_kr + 16 * s, bcode[s]);
+            else if (B.vec_ok) breg[s] = B.load(t * BD + b_kr + 16 * s, n0 + b_nq * 4, bcode[s]);
             else {
                 breg[s] = B.load_slow(t * BD + b_kr + 16 * s, n0 + b_nq * 4);
                 bcode[s] = LD_KEEP;
@@ -603,68 +657,137 @@ __device__ __forceinline__ void gemm_tile(const ALoader& A, const BLoader& B, co
         }
         return t;
     };
-    int t = next_tile(t_begin);
-    if (t < t_end) {
-        load_tile(t);
-        store_tile(0);
-    }
-    __syncthreads();
-    for (int buf = 0; t < t_end; buf ^= 1) {
-        const int tn = next_tile(t + 1);
-        const bool more = tn < t_end;
-        if (more) load_tile(tn);
-        if (band_live) {
-            // fragments of depth step k+2 are read from LDS while the MFMAs of step k run
-            // one base address per operand and tile (buffer + lane part), made opaque so that the compiler keeps it in
-            // a VGPR and addresses the 16 depth steps with immediate offsets (it otherwise re-adds the buffer offset
-            // to sixteen hoisted per-step registers: a v_add3 in front of every ds_read, i.e. VALU time taken from
-            // the MFMAs, section 5a of DESIGN.md)
-            // (indices into the __shared__ arrays, not pointers: a pointer through the asm loses its address space and
-            // the reads become flat loads)
-            int ia = buf * ASZ + (ALoader::DEPTH_CONTIG ? fi * LDA + fk : fk * BM + fi);
-            int ib = buf * BSZ + (BLoader::DEPTH_CONTIG ? fj * LDA + fk : fk * BN + fj);
-            asm volatile("" : "+v"(ia), "+v"(ib));
-            auto frag_a = [&](int k) { return As[ia + (ALoader::DEPTH_CONTIG ? k : k * BM)]; };
-            auto frag_b = [&](int k, int nb) {
-                return Bs[ib + (BLoader::DEPTH_CONTIG ? nb * 32 * LDA + k : k * BN + nb * 32)];
-            };
-            float a = frag_a(0), b[NB];
+    auto run = [&](auto fast) {
+        int t = next_tile(t_begin);
+        if (t < t_end) {
+            load_tile(fast, t);
+            store_tile(0);
+        }
+        __syncthreads();
+        for (int buf = 0; t < t_end; buf ^= 1) {
+            const int tn = next_tile(t + 1);
+            const bool more = tn < t_end;
+            if (more) load_tile(fast, tn);
+            if (band_live) {
+                // fragments of depth step k+2 are read from LDS while the MFMAs of step k run
+                // one base address per operand and tile (buffer + lane part), made opaque so that the compiler keeps it in
+                // a VGPR and addresses the 16 depth steps with immediate offsets (it otherwise re-adds the buffer offset
+                // to sixteen hoisted per-step registers: a v_add3 in front of every ds_read, i.e. VALU time taken from
+                // the MFMAs, section 5a of DESIGN.md)
+                // (indices into the __shared__ arrays, not pointers: a pointer through the asm loses its address space and
+                // the reads become flat loads)
+                int ia = buf * ASZ + (ALoader::DEPTH_CONTIG ? fi * LDA + fk : fk * BM + fi);
+                int ib = buf * BSZ + (BLoader::DEPTH_CONTIG ? fj * LDA + fk : fk * BN + fj);
+                asm volatile("" : "+v"(ia), "+v"(ib));
+                auto frag_a = [&](int k) { return As[ia + (ALoader::DEPTH_CONTIG ? k : k * BM)]; };
+                auto frag_b = [&](int k, int nb) {
+                    return Bs[ib + (BLoader::DEPTH_CONTIG ? nb * 32 * LDA + k : k * BN + nb * 32)];
+                };
+                float a = frag_a(0), b[NB];
 #pragma unroll
-            for (int nb = 0; nb < NB; ++nb) b[nb] = frag_b(0, nb);
+                for (int nb = 0; nb < NB; ++nb) b[nb] = frag_b(0, nb);
 #pragma unroll
-            for (int k = 0; k < BD; k += 2) {
-                float an = 0.f, bn[NB];
-                if (k + 2 < BD) {
-                    an = frag_a(k + 2);
+                for (int k = 0; k < BD; k += 2) {
+                    float an = 0.f, bn[NB];
+                    if (k + 2 < BD) {
+                        an = frag_a(k + 2);
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) bn[nb] = frag_b(k + 2, nb);
-                }
+                        for (int nb = 0; nb < NB; ++nb) bn[nb] = frag_b(k + 2, nb);
+                    }
 #pragma unroll
-                for (int nb = 0; nb < NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b[nb], acc[nb], 0, 0, 0);
-                if (k + 2 < BD) {
-                    a = an;
+                    for (int nb = 0; nb < NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b[nb], acc[nb], 0, 0, 0);
+                    if (k + 2 < BD) {
+                        a = an;
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) b[nb] = bn[nb];
+                        for (int nb = 0; nb < NB; ++nb) b[nb] = bn[nb];
+                    }
                 }
             }
+            if (more) store_tile(buf ^ 1);
+            __syncthreads();
+            t = tn;
         }
-        if (more) store_tile(buf ^ 1);
-        __syncthreads();
-        t = tn;
-    }
+    };
+    if (!a_slow && B.vec_ok) run(std::true_type{});
+    else run(std::false_type{});
 
     // ---- epilogue: C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+    // Element (nb, r) of a lane lies at  wave origin + (row offset of r) * ld + 32 * nb  +  the lane's own offset: the first
+    // part is wave-uniform (scalar registers, 64-bit), the second one 32-bit register per lane, so a store needs no vector
+    // address arithmetic at all.  The bounds test is one vote per wave (interior waves store unguarded), and everything
+    // about the epilogue that is the same for the whole block -- slab or C, bias, activation, mask -- is decided outside
+    // the 16-element loops.
+    const int wrow = __builtin_amdgcn_readfirstlane(m0 + wm * 32);            // first row / column of the wave's part
+    const int wcol = __builtin_amdgcn_readfirstlane(n0 + wn * (BN / WN));
+    if (wrow >= M) return;
+    const int lrow = 4 * (lane >> 5), lcol = lane & 31;
+    const long ld = slabs ? (long)N : ep.ldc;                                // (ld < 2^28: launch_mfma)
+    const long origin = (long)wrow * ld + wcol;
+    float* const cw = (slabs ? slabs + (long)bz * M * N : ep.c) + origin;
+    const unsigned lane_bytes = (unsigned)(lrow * (int)ld + lcol) * 4u;
+    auto at = [&](auto* p, long u) {                                       // uniform 64-bit part + the lane's 32 bits
+        using Bytes = std::conditional_t<std::is_const_v<std::remove_pointer_t<decltype(p)>>, const char, char>;
+        return (decltype(p))((Bytes*)(p + u) + lane_bytes);
+    };
+    const int rows_left = M - wrow, cols_left = N - wcol;
+    // body(nb, row offset of r, wave-uniform element offset, value)
+    auto each = [&](auto guarded, auto&& body) {
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int j = n0 + fj + nb * 32;
+        for (int nb = 0; nb < NB; ++nb) {
+            const bool col_ok = !guarded.value || lcol + nb * 32 < cols_left;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int i = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            if (i < M && j < N) {
-                if (slabs) slabs[((long)bz * M + i) * N + j] = acc[nb][r];
-                else epilogue_store(ep, i, j, acc[nb][r]);
+            for (int r = 0; r < 16; ++r) {
+                const int roff = (r & 3) + 8 * (r >> 2);
+                if (!guarded.value || (col_ok && lrow < rows_left - roff)) body(nb, roff, roff * ld + nb * 32, acc[nb][r]);
             }
         }
+    };
+    const bool simple = !slabs && !ep.accumulate && ep.split_row < 0;
+    const bool plain = slabs || (simple && !ep.bias && ep.act == UOCR_ACT_NONE && ep.mask_act == UOCR_ACT_NONE);
+    const bool forward = simple && !plain && ep.mask_act == UOCR_ACT_NONE && ep.act != UOCR_ACT_SIGMOID;
+    const bool masked = simple && !plain && !ep.bias && ep.act == UOCR_ACT_NONE;
+    const float* const mw = ep.mask_y + origin;
+    auto finish = [&](auto guarded) {
+        if (plain) {
+            each(guarded, [&](int, int, long u, float v) { *at(cw, u) = v; });
+        } else if (forward) {
+            // a layer's forward: + bias, then ReLU / leaky ReLU as act_apply computes them (v * 1 for v >= 0, v * alpha or
+            // v * 0 for v < 0) or nothing.  (No bias: -0 is added, which changes no float.)
+            float bias[NB];
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb)
+                bias[nb] = (ep.bias && lcol + nb * 32 < cols_left) ? ep.bias[wcol + lcol + nb * 32] : -0.f;
+            if (ep.act == UOCR_ACT_NONE) {
+                each(guarded, [&](int nb, int, long u, float v) { *at(cw, u) = v + bias[nb]; });
+            } else {
+                const float neg = ep.act == UOCR_ACT_LEAKY ? ep.alpha : 0.f;
+                each(guarded, [&](int nb, int, long u, float v) {
+                    v += bias[nb];
+                    *at(cw, u) = v * (v >= 0.f ? 1.f : (v < 0.f ? neg : 0.f));
+                });
+            }
+        } else {
+            // dx through the activation that produced this layer's input
+            each(guarded, [&](int, int, long u, float v) {
+                *at(cw, u) = v * act_grad_from_output<float>(*at(mw, u), ep.mask_act, ep.mask_alpha);
+            });
+        }
+    };
+    if (!(plain || forward || masked)) {
+        // everything else (sigmoid, unsplit dw / db, accumulation): epilogue_store with its block-uniform conditions
+        each(std::true_type{}, [&](int nb, int roff, long u, float v) {
+            const int j = wcol + lcol + nb * 32;
+            if (ep.bias) v += ep.bias[j];
+            v = act_apply(v, ep.act, ep.alpha);
+            if (ep.mask_act != UOCR_ACT_NONE) v *= act_grad_from_output<float>(*at(mw, u), ep.mask_act, ep.mask_alpha);
+            float* dst = at(cw, u);
+            if (ep.split_row >= 0 && wrow + lrow + roff >= ep.split_row) dst = ep.c2 + j;
+            *dst = ep.accumulate ? *dst + v : v;
+        });
+    } else if (rows_left >= 32 && cols_left >= NB * 32) {
+        finish(std::false_type{});
+    } else {
+        finish(std::true_type{});
     }
 }
 
@@ -721,6 +844,7 @@ template <typename ALoader, typename BLoader>
 int launch_mfma(uocr_ctx* ctx, const ALoader& A, const BLoader& B, const Epilogue& ep, int M, int N, int depth,
                 bool allow_split) {
     const int ntiles = (depth + BD - 1) / BD;
+    if (ep.ldc >= (1l << 28)) return UOCR_ERR_UNSUPPORTED;      // (the epilogue keeps 4 rows' distance in 32 bits)
     // 128-row tiles (two MFMAs per A fragment read) when they still fill the chip: on their own, or -- very deep
     // GEMMs, dw of a wide conv -- together with the depth split
     const long tiles128 = (long)((M + 127) / 128) * ((N + BN - 1) / BN);
@@ -1027,7 +1151,7 @@ int uocr_gemm_mfma(uocr_ctx* ctx, const GemmArgs& g) {
         B = BRowMajor{bt, g.n, g.depth, g.n, (g.n % 4 == 0 && aligned16(bt)) ? 1 : 0};
     }
     const Epilogue ep = ep0;
-    if (g.a_cs == 1) {
+    if (g.a_cs == 1 && !g.a_ones_row) {        // (x of a 1-input dense layer has both strides 1: its dw is [x, 1]^T . dy)
         const int stored = g.a_ones_col ? g.depth - 1 : g.depth;
         ARowMajor A{(const float*)g.a, g.a_rs, g.m, stored, g.a_ones_col,
                     (g.a_rs % 4 == 0 && stored % 4 == 0 && aligned16(g.a)) ? 1 : 0};
