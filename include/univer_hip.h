@@ -399,6 +399,31 @@ int uocr_masked_crop(uocr_ctx* ctx, int dtype, const void* image, const int* lab
  * first): tests size their images from it so that components cross tile borders */
 int uocr_ctx_last_label(uocr_ctx* ctx, int* tile_h, int* tile_w, int* launches);
 
+/* ---- char labels (interpreter/interpreter.py:547-571 LabelChar._func1: the CharLabel stage) --------------------
+ * The one-hot training labels of the Char net from the bit layers of every cropped line, for ALL lines of a page in one
+ * call (the reference runs a Python loop per pixel in a worker pool, :524-545, between a device-to-host and a
+ * host-to-device copy of every line, my_model/model.py:614-623).  Line i is x[i]: (1, h[i], w[i], c) in `dtype`, its
+ * channels bit_0 .. bit_{bits-1} followed by whatever else the layer tag carries (letter_spacing, my_model/constants.py:
+ * 22-25).  t = 0.5 * (mean + max) over ALL h * w * c elements of the line (float64 reductions, :549); bit k of a pixel is
+ * set when x[y, x, k] > t; code = sum_k bit_k 2^k (primitives/__init__.py:46-50: least significant digit first);
+ * code < n_chars is that class (code 0 -- no bit set -- is class 0, a class like any other), every other code is
+ * "unknown".  Column x takes the most frequent candidate among its h pixels, all unknown codes counting as ONE candidate;
+ * on a tie the candidate that occurs first from the top (collections.Counter.most_common, :565-566).  Row x of labels[i] is
+ * one-hot at the winner, all zeros when "unknown" won (:567-570).
+ * x[i]: (1, h[i], w[i], c) in `dtype`; labels[i]: (w[i], n_chars) in `dtype`, every element written;
+ * ids: optional (may be NULL) -- ids[i]: int32 (w[i]), the winning class of each column or -1 for a zero row.
+ * x, h, w, labels, ids are HOST arrays of n_lines entries (device pointers / sizes).
+ * Limits: 1 <= bits <= 8, bits <= c <= 16, 1 <= n_chars <= 2^bits, h[i], w[i] >= 1 (UOCR_ERR_ARG otherwise, as for null
+ * pointers, pointers off their element's alignment and n_lines < 0); h[i] <= 256 (UOCR_ERR_UNSUPPORTED; the reference's is CHAR_INPUT_HEIGHT = 32).  Nothing is
+ * written on any error; n_lines = 0 is UOCR_OK and launches nothing (the other arguments are not looked at).  Two launches per 64 lines; 16 bytes of the ctx
+ * workspace per 8192 elements of a line (UOCR_ERR_WORKSPACE).  No atomics: results are bit-identical run to run.
+ * Asynchronous and capturable. */
+int uocr_char_label(uocr_ctx* ctx, int dtype, int n_lines, const void* const* x, const int* h, const int* w,
+                    int c, int bits, int n_chars, void* const* labels, int* const* ids);
+/* sizes the last uocr_char_label call on this ctx used: columns per vote block, elements per stats chunk,
+ * lines per launch, launches issued (all 0 before the first call) -- tests size their inputs from it */
+int uocr_ctx_last_char_label(uocr_ctx* ctx, int* cols_per_block, int* stats_chunk, int* lines_per_launch, int* launches);
+
 /* ---- data parallel over the GPUs of one node: RCCL over xGMI ------------------------------------
  * The reference has no multi-GPU path; BASELINE.json adds one to the step loop my_model/trainer.py:213-233
  * -> nn/model_system.py:104-118 -> nn/models.py:250-254: between compute_loss_and_gradients and update_grads

@@ -1,0 +1,177 @@
+"""Host side of the CharLabel feature: the fixture tests/golden/char_label.npz (made from the reference's
+LabelChar._func1 by tests/golden/make_golden_char_label.py), the NumPy restatement of the stage's four rules that the GPU
+tests use as expected value at sizes the fixture cannot know (trusted only because it is pinned to the fixture here), the
+nesting of LabelChars, the model-system component and the ABI names.  Nothing here needs a GPU."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, load_golden
+
+BITS, N_CHARS = 8, 162
+NEW_SYMBOLS = {'uocr_char_label': 11, 'uocr_ctx_last_char_label': 5}      # name -> arguments, the context included
+
+
+def char_label_rules(x, bits=BITS, n_chars=N_CHARS, threshold=None):
+    """labels (W, n_chars) float64 and ids (W,) int32 of one line x (1, H, W, C), by the four rules (`threshold`: what the
+    labels would be if t were that number instead -- tests use it to show that their expected values depend on t):
+    1. t = (mean + max) / 2 over every element, in float64; bit i of a pixel is x[y, x, i] > t
+    2. code = sum of bit_i 2^i; code < n_chars is that class, every other code is the one candidate "unknown" (-1)
+    3. per column the most frequent candidate; on a tie the one whose first occurrence is highest up
+    4. a one-hot row at the winner, a zero row (id -1) when "unknown" won"""
+    x = np.asarray(x, np.float64)
+    _, h, w, _ = x.shape
+    t = 0.5 * (np.mean(x) + np.max(x)) if threshold is None else threshold
+    codes = ((x[0, :, :, :bits] > t) * (1 << np.arange(bits))).sum(axis=2)
+    codes = np.where(codes < n_chars, codes, -1)
+    labels, ids = np.zeros((w, n_chars)), np.full(w, -1, np.int32)
+    for col in range(w):
+        best, best_count = -1, 0
+        for y in range(h):                                      # upwards: the first candidate to reach the top count stays
+            count = int(np.sum(codes[:, col] == codes[y, col]))
+            if count > best_count:
+                best, best_count = int(codes[y, col]), count
+        ids[col] = best
+        if best >= 0:
+            labels[col, best] = 1.0
+    return labels, ids
+
+
+@pytest.fixture(scope='module')
+def g():
+    return load_golden('char_label')
+
+
+def line_names(g):
+    return [str(s) for s in g['line_names']]
+
+
+def test_fixture_loads_and_is_consistent(g):
+    names = line_names(g)
+    assert len(names) == 11 and {'hand', 'constant', 'spacing', 'w8', 'w17', 'w64', 'w130', 'h5', 'h1'} <= set(names)
+    for name in names:
+        x, labels, ids = g[f'{name}/x'], g[f'{name}/labels'], g[f'{name}/ids']
+        assert x.ndim == 4 and x.shape[0] == 1 and x.shape[3] == BITS + 1
+        assert labels.shape == (x.shape[2], N_CHARS) and ids.shape == (x.shape[2],) and ids.dtype == np.int32
+        assert np.array_equal(x, x.astype(np.float16).astype(np.float64)), f'{name}: not exact in binary16'
+        if name != 'constant':                                  # (there every element EQUALS t, in every float type)
+            assert np.min(np.abs(x - 0.5 * (x.mean() + x.max()))) > 1e-3, f'{name}: an input lies within 1e-3 of t'
+        assert np.array_equal(np.where(labels.any(axis=1), labels.argmax(axis=1), -1), ids)
+        assert set(np.unique(labels)) <= {0.0, 1.0} and labels.sum(axis=1).max() <= 1
+    assert g['hand/ids'].tolist() == [5, 7, -1, -1, 9, 0], 'the hand-built tie / unknown / all-zero columns'
+    assert not g['constant/ids'].any() and not g['spacing/ids'].any()
+    assert [g[f'char{p}_{l}'].shape[2] for p, l in ((0, 0), (0, 1), (1, 0))] == [24, 40, 17]
+    for p, l in ((0, 0), (0, 1), (1, 0)):
+        assert g[f'mono{p}_{l}'].shape == (1, 32, g[f'char{p}_{l}'].shape[2], 1)
+        assert g[f'labels{p}_{l}'].shape == (g[f'char{p}_{l}'].shape[2], N_CHARS)
+
+
+def test_rules_reproduce_the_reference(g):
+    """the restatement equals LabelChar._func1 on every fixture line, bit for bit"""
+    lines = [(name, g[f'{name}/x'], g[f'{name}/labels'], g[f'{name}/ids']) for name in line_names(g)]
+    lines += [(f'char{p}_{l}', g[f'char{p}_{l}'], g[f'labels{p}_{l}'], None) for p, l in ((0, 0), (0, 1), (1, 0))]
+    for name, x, ref_labels, ref_ids in lines:
+        labels, ids = char_label_rules(x)
+        assert labels.tobytes() == ref_labels.tobytes(), f'{name}: labels'
+        assert ref_ids is None or np.array_equal(ids, ref_ids), f'{name}: ids'
+
+
+def test_rules_on_other_sizes():
+    """fewer bits than channels, a class count that is no power of two, and one that is (no code is unknown)"""
+    x = np.zeros((1, 3, 4, 4))
+    x[0, :, :, 3] = 1.0                                         # the extra channel: in the statistics only
+    x[0, :, 0, 0] = x[0, :, 0, 2] = 1.0                         # code 5: unknown for 5 classes, class 5 for 8
+    x[0, :2, 1, 1] = 1.0                                        # code 2 twice, code 0 once
+    x[0, 0, 2, 2] = x[0, 1, 2, 0] = 1.0                         # 4, 1, 0: a three-way tie, the top one wins
+    labels, ids = char_label_rules(x, bits=3, n_chars=5)
+    assert ids.tolist() == [-1, 2, 4, 0] and labels.shape == (4, 5) and labels.sum() == 3
+    assert char_label_rules(x, bits=3, n_chars=8)[1].tolist() == [5, 2, 4, 0]
+
+
+# ---- LabelChars and the component ------------------------------------------------------------------------------------
+def test_label_chars_keeps_the_nesting_with_one_call_per_page(monkeypatch):
+    from univer_ocr_amd.my_model import crop
+    from univer_ocr_amd.my_model.model import BITS_COUNT
+    from univer_ocr_amd.nn import CP
+    calls = []
+
+    def stub(lines, bits, n_chars, want_ids=False):
+        calls.append((list(lines), bits, n_chars))
+        return [('labels', id(a)) for a in lines]
+    monkeypatch.setattr(crop.ops, 'char_label', stub)
+    a, b, c = (CP.zeros((1, 32, w, 9)) for w in (8, 24, 16))
+    label_chars = crop.LabelChars()
+    assert label_chars([[a, b], [], [c]]) == [[('labels', id(a)), ('labels', id(b))], [], [('labels', id(c))]]
+    assert len(calls) == 1 and [id(v) for v in calls[0][0]] == [id(a), id(b), id(c)]
+    assert calls[0][1:] == (BITS_COUNT, N_CHARS)
+    assert label_chars([]) == [] and label_chars([[], [a]]) == [[], [('labels', id(a))]]
+    assert len(calls) == 3 and calls[1][0] == [] and [id(v) for v in calls[2][0]] == [id(a)]
+
+
+def test_char_label_of_nothing_and_of_wrong_arrays():
+    """an empty page needs no device; ranks, dtypes and channel counts are checked before any call"""
+    from univer_ocr_amd.nn import CP, ops
+    assert ops.char_label([], 8, 162) == [] and ops.char_label([], 8, 162, want_ids=True) == ([], [])
+    good = CP.zeros((1, 4, 6, 9), np.float32)
+    for bad in (CP.zeros((4, 6, 9), np.float32), CP.zeros((2, 4, 6, 9), np.float32), np.zeros((1, 4, 6, 9))):
+        with pytest.raises(ValueError, match='char_label'):
+            ops.char_label([good, bad], 8, 162)
+    for other in (CP.zeros((1, 4, 6, 9), np.float64), CP.zeros((1, 4, 6, 10), np.float32)):
+        with pytest.raises(ValueError, match='share dtype and channel count'):
+            ops.char_label([good, other], 8, 162)
+
+
+def test_bits_count_follows_the_class_count():
+    from univer_ocr_amd.my_model.model import BITS_COUNT, N_CHARS as model_n_chars
+    assert BITS_COUNT == 8 and model_n_chars == N_CHARS
+    assert 2 ** BITS_COUNT >= N_CHARS + 1 > 2 ** (BITS_COUNT - 1)
+
+
+def test_char_label_component_and_its_system_are_built_without_a_gpu(monkeypatch):
+    from univer_ocr_amd.my_model import crop
+    from univer_ocr_amd.my_model.model import CharSelector, make_char, make_char_label_component
+    from univer_ocr_amd.nn.model_system import ModelComponent, ModelSystem, RawFunctionComponent
+    from univer_ocr_amd.nn.progress_tracker import ProgressTracker
+    tracker = ProgressTracker(handler=lambda *a: None)
+    component = make_char_label_component(tracker)
+    assert isinstance(component, RawFunctionComponent) and 'CharLabel' in tracker.layers
+    char = ModelComponent('Char', make_char((1, 32, 24, 1)), CharSelector('cropped_2_monochrome', 'char_labels', 'char_pred'),
+                          delist_result=True)
+    system = ModelSystem([component, char])
+    assert system.components == [component, char]
+    # the component files LabelChars()(context[source]) at context[target], in every mode
+    monkeypatch.setattr(crop.ops, 'char_label', lambda lines, bits, n_chars, want_ids=False: [f'y{i}' for i, _ in enumerate(lines)])
+    monkeypatch.setattr(crop.ops, 'as_device', lambda a: a)
+    for run in (component.train, component.test, component.predict):
+        context = {'cropped_2_char': [['a', 'b'], ['c']]}
+        run(context)
+        assert context['char_labels'] == [['y0', 'y1'], ['y2']]
+    other = make_char_label_component(source='lines', target='labels')
+    context = {'lines': [[], ['a']]}
+    other.train(context)
+    assert context['labels'] == [[], ['y0']]
+
+
+# ---- ABI ---------------------------------------------------------------------------------------------------------------
+def test_header_and_binding_declare_the_new_entry_points():
+    from univer_ocr_amd.hip import lib as hiplib
+    header = open(os.path.join(ROOT, 'include', 'univer_hip.h')).read()
+    for name, arguments in NEW_SYMBOLS.items():
+        declaration = re.search(r'\bint\s+' + name + r'\s*\(([^)]*)\)', header)
+        assert declaration, f'{name} is not declared in univer_hip.h'
+        assert len(declaration.group(1).split(',')) == arguments
+        assert name in hiplib.ABI_SYMBOLS and len(hiplib._PROTOS[name]) == arguments
+    assert re.search(r'#define\s+UOCR_ABI_VERSION\s+4\b', header), 'symbols are added, the ABI version stays'
+
+
+def test_library_exports_the_new_entry_points():
+    from univer_ocr_amd.hip import lib as hiplib
+    lib = hiplib.get_lib()
+    assert lib.uocr_abi_version() == 4
+    for name in NEW_SYMBOLS:
+        assert getattr(lib, name)
+    # without a context both refuse with UOCR_ERR_ARG before touching anything
+    assert lib.uocr_char_label(None, 0, 0, None, None, None, 9, 8, 162, None, None) == -1
+    assert lib.uocr_ctx_last_char_label(None, None, None, None, None) == -1

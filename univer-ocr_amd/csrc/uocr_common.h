@@ -46,6 +46,7 @@ struct uocr_ctx {
     int pair_nw, pair_blocks_x, pair_bands, pair_band_h;   // ... and its geometry (waves per block, grid x, grid y, rows per band)
     int conv_entry, conv_kernel;                  // uocr_ctx_last_conv: entry point and kernel family of the last accepted conv call
     int label_th, label_tw, label_launches;       // uocr_ctx_last_label: tile and launch count of the last labelling call
+    int cl_cols, cl_chunk, cl_lines, cl_launches; // uocr_ctx_last_char_label: sizes and launch count of the last char-label call
     char err[512];
 };
 

@@ -6,6 +6,14 @@ CropParagraphs is the reference's CropAndRotateParagraphs (interpreter/interpret
 rotation angle `_func` (:314-348) hands the crops back unchanged, so that is the whole stage.  Arrays stay in HBM: the
 labelling, the boxes and the crops are kernels of libuniver_hip.so (nn/ops.py: label_components, masked_crop); the only
 thing the host reads is the component table (64 bytes per paragraph).  There is no worker pool.
+
+LabelChars is the reference's LabelChar (interpreter/interpreter.py:524-571): the `char` layer tag of every cropped line
+-- bit layers first, then letter_spacing -- becomes the (W, N_CHARS) one-hot labels the Char net trains on.  Per line:
+threshold at (mean + max) / 2 of the whole array, read every pixel's bits as a class number (least significant bit
+first; a number that is no class is "unknown"), let every column vote over its rows (the first candidate from the top
+wins a tie, "unknown" is one candidate) and write a one-hot row, or a zero row where "unknown" won.  The reference does
+this in a Python loop per pixel on a worker pool, between a device-to-host and a host-to-device copy of every line; here
+all lines of all paragraphs of a page are ONE kernel call (nn/ops.py: char_label) and nothing leaves HBM.
 """
 from ..nn import ops
 
@@ -33,3 +41,17 @@ class CropParagraphs:
         components = ops.label_components(mask, 'mean', self.max_components)
         paragraphs = int(components.count[0])
         return [[ops.masked_crop(a, components, 0, k, divisible_by) for k in range(1, paragraphs + 1)] for a in arrays]
+
+
+class LabelChars:
+    def __init__(self, bits=None, n_chars=None):
+        from . import model
+        self.bits = model.BITS_COUNT if bits is None else bits
+        self.n_chars = model.N_CHARS if n_chars is None else n_chars
+
+    def __call__(self, arrays):
+        """arrays[paragraph][line]: (1, H, W, C) DeviceArrays.  Returns the labels, (W, n_chars) each, in the same nesting
+        (a paragraph without lines stays [], a page without paragraphs []); one kernel call for the page."""
+        flat = [ops.as_device(line) for paragraph in arrays for line in paragraph]
+        labels = iter(ops.char_label(flat, self.bits, self.n_chars))
+        return [[next(labels) for _ in paragraph] for paragraph in arrays]

@@ -10,8 +10,9 @@ channel counts, kernel sizes and losses, so `model_weights.json` files are inter
 
 Every conv carries L2(0.01) (model.py:36-39).  Of the stages that sit between the nets in the
 reference's model system (host code, interpreter/), ParagraphCrop without the rotation search runs on
-the device (my_model/crop.py), which is what TRAIN_LINE needs; LineCrop, CharLabel and PredToText have
-no device form yet, and `make_model_system` says so for the modes that need them.
+the device (my_model/crop.py), which is what TRAIN_LINE needs, and CharLabel runs there too
+(`make_char_label_component`); LineCrop and PredToText have no device form yet, and `make_model_system` says
+so for the modes that need them (TRAIN_CHAR waits for LineCrop only).
 """
 from enum import Enum
 
@@ -32,6 +33,7 @@ from ..nn.regularizations import L2
 CHAR_INPUT_HEIGHT = 32
 CHAR_FIXED_WIDTH = 8
 N_CHARS = 162            # len(primitives.CHARS): tab, space, 66 Cyrillic, 10 digits, 52 Latin, 32 punctuation
+BITS_COUNT = next(b for b in range(1, 32) if 2 ** b >= N_CHARS + 1)   # primitives/__init__.py:44: ceil(log2(len(CHARS) + 1)) = 8
 OUTPUT_CHANNELS = {'monochrome': 1, 'paragraph': 1, 'line': 2}   # constants.py:19-29 LAYER_NAMES
 
 
@@ -187,6 +189,21 @@ def make_move_to_gpu_component(labels):
     return _make_move_component(CP.copy, labels)
 
 
+def make_char_label_component(progress_tracker=None, source='cropped_2_char', target='char_labels'):
+    """model.py:614-623 (make_char_label_component) and :640-643 (move_to_gpu_char_label) as one component: the nested
+    list context[source][paragraph][line] of cropped `char` arrays becomes context[target][paragraph][line], the
+    (W, N_CHARS) labels of the Char net, in one kernel call for the page (my_model/crop.py: LabelChars).  Nothing visits
+    the host."""
+    from .crop import LabelChars
+    label_chars = LabelChars()
+
+    @track_function('CharLabel', 'forward', progress_tracker)
+    def char_label(context):
+        context[target] = label_chars(context[source])
+
+    return RawFunctionComponent(char_label)
+
+
 class LineSelector(IterableSelector):
     """One sample per paragraph (model.py:353-373): context[X_label][p], context[y_label][p]; the prediction of
     paragraph p is filed at context[pred_label][p].  The position starts over with every bind."""
@@ -253,8 +270,8 @@ class CharSelector(LineSelector):
 
 # what the modes that still raise are waiting for (the reference's component order, model.py:489-500)
 _MISSING_STAGE = {
-    'TRAIN_CHAR': 'LineCrop (interpreter.py CropRotateAndZoomLines: ndimage.rotate / zoom of every line) and CharLabel',
-    'TRAIN_ALL': 'LineCrop (interpreter.py CropRotateAndZoomLines: ndimage.rotate / zoom of every line) and CharLabel',
+    'TRAIN_CHAR': 'LineCrop (interpreter.py CropRotateAndZoomLines: ndimage.rotate / zoom of every line)',
+    'TRAIN_ALL': 'LineCrop (interpreter.py CropRotateAndZoomLines: ndimage.rotate / zoom of every line)',
     'PREDICT': 'the rotation search of ParagraphCrop (find_rotation=True), LineCrop and PredToText',
 }
 

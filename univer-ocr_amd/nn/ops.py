@@ -596,6 +596,35 @@ def masked_crop(array, components, image_index, k, divisible_by=None):
     return out
 
 
+# ---- char labels (interpreter/interpreter.py:547-571: CharLabel) -----------------------------------------------------
+def char_label(lines, bits, n_chars, want_ids=False):
+    """The (W, n_chars) one-hot labels of every line of `lines`, a flat list of (1, H, W, C) DeviceArrays whose first
+    `bits` channels are the bit layers: threshold at (mean + max) / 2 of the line, decode, vote per column
+    (LabelChar._func1, interpreter.py:547-571).  ONE uocr_char_label call for all lines, whatever their sizes (none for an
+    empty list); labels
+    have the lines' dtype.  want_ids=True: also the int32 (W,) winning class of every column, -1 where the row is zero."""
+    lines = list(lines)
+    for a in lines:
+        if not isinstance(a, DeviceArray) or a.ndim != 4 or a.shape[0] != 1:
+            raise ValueError(f'char_label: expected (1, H, W, C) device arrays, got {getattr(a, "shape", type(a))}')
+    if not lines:
+        return ([], []) if want_ids else []
+    code, c = lines[0].code & 0xff, lines[0].shape[3]
+    for a in lines:
+        if a.code & 0xff != code or a.shape[3] != c:
+            raise ValueError('char_label: the lines of one call share dtype and channel count, got ' +
+                             ', '.join(f'{x.shape} {x.dtype}' for x in lines))
+    import ctypes as C
+    n = len(lines)
+    labels = [CP.empty((a.shape[2], n_chars), a.dtype) for a in lines]
+    ids = [CP.empty((a.shape[2],), np.int32) for a in lines] if want_ids else None
+    pointers = lambda arrays: (C.c_void_p * n)(*[a.ptr for a in arrays])
+    _rt().call('uocr_char_label', code, n, pointers(lines), (C.c_int * n)(*[a.shape[1] for a in lines]),
+               (C.c_int * n)(*[a.shape[2] for a in lines]), int(c), int(bits), int(n_chars), pointers(labels),
+               pointers(ids) if want_ids else None)
+    return (labels, ids) if want_ids else labels
+
+
 class _Ops:
     add = staticmethod(add)
 
