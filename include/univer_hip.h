@@ -94,7 +94,9 @@ void* uocr_ctx_get_stream(uocr_ctx* ctx);
  * "wgrad_bands" (row bands per tap / channel group of the direct weight-gradient
  * kernels, 0 = 64 or 512 by the kernel's accumulator count); "max_blocks" (k > 0 lowers every block budget that is
  * decided at run time -- persistent tile walks, rows or tiles per block -- to k, so that small shapes make blocks walk
- * several tiles; it never raises one; 0 = the budgets as they are).  Results do not depend on any of them beyond float32
+ * several tiles; it never raises one; 0 = the budgets as they are); "act_dispatch" (1 = kernels that have them take the
+ * activation / mask kinds the nets use as compile-time tags, 0 = every call runs the instantiation with the run-time
+ * switch: the same bits, for A/B runs).  Results do not depend on any of them beyond float32
  * summation order ("h16": beyond the binary16 rounding of the weight operands; "h3": 22 significant bits). */
 int uocr_ctx_set_option(uocr_ctx* ctx, const char* key, int value);
 /* the block count and the number of work items (tiles, or strips x row bands x images) of the most recent launch on

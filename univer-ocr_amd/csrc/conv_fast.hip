@@ -238,11 +238,12 @@ __global__ __launch_bounds__(256) void conv_dgrad_fast(const TA* __restrict__ dy
 // three quarters of the lanes idle in each of the 25 iterations).
 //   y = 2j:     ky = 0, 2, 4 -> dy rows j+1, j, j-1          y = 2j+1:  ky = 1, 3 -> dy rows j+1, j
 // ---------------------------------------------------------------------------------------------
-template <int CIN, int COUT, typename TA>
+template <int CIN, int COUT, typename TA, class K>
 __global__ __launch_bounds__(256) void conv_dgrad_s2(const TA* __restrict__ dy, const float* __restrict__ w,
                                                      TA* __restrict__ dx, FastDims d,
                                                      const TA* __restrict__ mask_y, int mask_act,
                                                      float mask_alpha) {
+    mask_act = act_kind<K::mask>(mask_act);                 // (a constant unless the tag is dynamic: uocr_common.h)
     const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, b = blockIdx.z;
     if (2 * i >= d.w || 2 * j >= d.h) return;
     const TA* gb = dy + (size_t)b * d.oh * d.ow * COUT;
@@ -377,10 +378,11 @@ __device__ __forceinline__ void load_row_c1(const TA* __restrict__ row, int a4, 
 //     loaded once and reused by all PX*KW taps, so L1 traffic per pixel drops from KW to
 //     ((PX-1)*SW + KW)/PX loads per row, and every weight is reused PX times from its SGPR.
 // ---------------------------------------------------------------------------------------------
-template <int KH, int KW, int CIN, int COUT, int SH, int SW, int PX, typename TA>
+template <int KH, int KW, int CIN, int COUT, int SH, int SW, int PX, typename TA, class K>
 __global__ __launch_bounds__(256) void conv_fwd_px(const TA* __restrict__ x, const float* __restrict__ w,
                                                    const float* __restrict__ bias, TA* __restrict__ y,
                                                    FastDims d, float pad, int use_bias, int act, float alpha) {
+    act = act_kind<K::act>(act);                 // (a constant unless the tag is dynamic: uocr_common.h)
     constexpr int NXV = (PX - 1) * SW + KW;
     const int ox0 = (blockIdx.x * 64 + threadIdx.x) * PX;
     const int oy = blockIdx.y * 4 + threadIdx.y;
@@ -1218,11 +1220,14 @@ struct FastConv {
 
     static int fwd(uocr_ctx* ctx, int dtype, const void* x, const void* w, const void* b, void* y, const ConvDims& d,
                    double pad, int use_bias, int act, double alpha) {
+        // (the activation kind as a tag where that was measured to pay: the row-loop kernels with 4 output channels)
+        return uocr_act_tags<0>(ctx, act, UOCR_ACT_NONE, [&](auto kinds) -> int {
+        using K = ActKindsIf<COUT == 4, decltype(kinds)>;
         UOCR_DISPATCH_TA(ctx, dtype, {
             if constexpr (FPX > 0) {
                 const int groups = (d.ow + FPX - 1) / FPX;
                 const dim3 grid((groups + 63) / 64, (d.oh + 3) / 4, d.n), block(64, 4);
-                hipLaunchKernelGGL((conv_fwd_px<KH, KW, CIN, COUT, SH, SW, FPX, TA>), grid, block, 0, ctx->stream,
+                hipLaunchKernelGGL((conv_fwd_px<KH, KW, CIN, COUT, SH, SW, FPX, TA, K>), grid, block, 0, ctx->stream,
                                    (const TA*)x, (const float*)w, (const float*)b, (TA*)y, dims(d), (float)pad,
                                    use_bias, act, (float)alpha);
             } else {
@@ -1235,6 +1240,7 @@ struct FastConv {
         });
         UOCR_LAUNCH_CHECK(ctx);
         return UOCR_OK;
+        });
     }
 
     static int dgrad(uocr_ctx* ctx, int dtype, const void* dy, const void* w, void* dx, const ConvDims& d,
@@ -1410,16 +1416,22 @@ int uocr_conv_dgrad_fast(uocr_ctx* ctx, int dtype, const void* dy, const void* w
         ((d.cin == 1 && (d.cout == 1 || d.cout == 4)) || (d.cin == 4 && d.cout == 4))) {
         const dim3 grid(((d.w + 1) / 2 + 63) / 64, ((d.h + 1) / 2 + 3) / 4, d.n), block(64, 4);
         const FastDims fd{d.n, d.h, d.w, d.oh, d.ow, d.ph, d.pw};
-        UOCR_DISPATCH_TA(ctx, dtype, {
-            auto launch = [&](auto kernel) {
-                hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, (const TA*)dy, (const float*)w, (TA*)dx, fd,
-                                   (const TA*)mask.y, mask.act, (float)mask.alpha);
-            };
-            if (d.cin == 4) launch(conv_dgrad_s2<4, 4, TA>);
-            else if (d.cout == 1) launch(conv_dgrad_s2<1, 1, TA>);
-            else launch(conv_dgrad_s2<1, 4, TA>);
+        const int rc = uocr_act_tags<1>(ctx, UOCR_ACT_NONE, mask.act, [&](auto kinds) -> int {
+            using K = decltype(kinds);             // (4 -> 4 only: the 1-channel forms gain nothing)
+            using D = ActKinds<UOCR_ACT_DYN, UOCR_ACT_DYN>;
+            UOCR_DISPATCH_TA(ctx, dtype, {
+                auto launch = [&](auto kernel) {
+                    hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, (const TA*)dy, (const float*)w, (TA*)dx, fd,
+                                       (const TA*)mask.y, mask.act, (float)mask.alpha);
+                };
+                if (d.cin == 4) launch(conv_dgrad_s2<4, 4, TA, K>);
+                else if (d.cout == 1) launch(conv_dgrad_s2<1, 1, TA, D>);
+                else launch(conv_dgrad_s2<1, 4, TA, D>);
+            });
+            UOCR_LAUNCH_CHECK(ctx);
+            return UOCR_OK;
         });
-        UOCR_LAUNCH_CHECK(ctx);
+        if (rc != UOCR_OK) return rc;
         uocr_note_conv(ctx, 1, UOCR_CONV_DGRAD_S2);
         return UOCR_OK;
     }

@@ -14,6 +14,9 @@
 // layers: float32 MFMAs and vector instructions do not overlap on a SIMD, so staging,
 // epilogue and address arithmetic (4 vector instructions per MFMA in the backward-data kernel) add to the MFMA
 // time, and with 3-6 blocks per CU the barrier-separated load / compute phases leave the matrix pipe 40 % busy.
+// Since then (profiles/t32_epilogue_*.txt) the epilogue kinds are template tags, a block lives for several tiles of 16
+// rows with the next tile's loads in flight, and the 4 -> 2 backward-data takes 32-33 us alone (2.7 vector instructions
+// per MFMA); the forward forms were not measured again.
 // Hence the default ("t32" option = 2) uses this file for the 4-channel backward-data only; the other
 // instantiations stay selectable (bits 1 / 4 / 8 / 16 / 32) and tested.  Results are exact float32 FMA chains
 // (the summation order differs from the reference's: tests at 1e-5 normalised, as for the other fused kernels).
@@ -50,7 +53,9 @@ struct Geo {
     static constexpr int NM = IB * Q;                          // MFMAs per chain
     static constexpr int BC = S == 1 ? 64 : 32;                // position columns of a block tile
     static constexpr int NCG = BC / 16;                        // chains per row band
-    static constexpr int BRT = S == 1 ? 32 : 16;               // target tile height
+    // target tile height.  16: a block lives for several tiles (prologue paid once, the next tile's loads in flight
+    // under the chains), so small tiles cost little and 32 x 256 x 512 gives 4096 of them to spread over the slots
+    static constexpr int BRT = 16;
     static constexpr int RPW = BRT / (4 * DY) > 0 ? BRT / (4 * DY) : 1;   // row bands per wave
     static constexpr int BR = 4 * RPW * DY;                    // position rows of a block tile
     static constexpr int IH = (BR - 1) * S + KH;               // staged input rows
@@ -65,6 +70,7 @@ struct Geo {
     static constexpr int NPASS = (IH + RPP - 1) / RPP;
     static constexpr int NW = (MODE == M_UPDGRAD || MODE == M_UPFWD || MODE == M_S2DGRAD ? 25 : KH * KW) * C * COUT;
     static_assert(16 % NCO == 0 && DY * NCO <= 16 && 4 % C == 0 && UW <= 256 && RS >= UW * 4, "unsupported geometry");
+    static_assert(RS % 4 == 0, "16-byte staging writes");
 };
 
 // the Q floats of one window row segment, with the widest aligned LDS reads the channel count allows
@@ -88,25 +94,117 @@ __device__ __forceinline__ void load_row(float (&bv)[G::Q], const float* p) {
     }
 }
 
+// The global loads of one input tile, pixel (iy0 + r, ix0 + c) -> unit (r, c*C ..), held in registers until tile_commit
+// writes them to LDS: a block requests its next tile before the chains of the current one.  No load is conditional and
+// no register is written twice (either makes hipcc wait for one row before it requests the next): a tile whose staged
+// window lies wholly inside the image (`plain`, wave-uniform) loads its 16-byte units as they are; at the image's edge
+// every pixel is read from its clamped position and the returned bits say which ones are image data (bit k * PXU + px;
+// the others become the padding value in tile_commit).
+template <class G>
+__device__ __forceinline__ bool tile_plain(int strip, int trow, int h_in, int w_in, int ph, int pw) {
+    const int iy0 = trow * G::BR * G::S - ph, wx0 = strip * G::BC * G::S - pw;
+    return iy0 >= 0 && iy0 + G::IH <= h_in && wx0 >= 0 && wx0 + G::UW * G::PXU <= w_in;
+}
+
+template <class G>
+__device__ __forceinline__ unsigned tile_fetch(float4 (&v)[G::NPASS], const float* __restrict__ in, bool plain, int strip,
+                                               int trow, int img, int h_in, int w_in, int ph, int pw, int sr, int su) {
+    constexpr int C = G::C, S = G::S;
+    static_assert(G::NPASS * G::PXU <= 32, "one bit per staged pixel");
+    const int iy0 = trow * G::BR * S - ph, gx0 = strip * G::BC * S - pw + su * G::PXU;
+    const float* inb = in + (size_t)img * h_in * w_in * C;               // (h_in * w_in * C < 2^31: launch_t32)
+    if (plain) {
+#pragma unroll
+        for (int k = 0; k < G::NPASS; ++k) {
+            int gy = iy0 + sr + k * G::RPP;
+            if (k * G::RPP + G::RPP > G::IH) gy = min(gy, h_in - 1);     // (rows past the tile: loaded, not stored)
+            v[k] = *reinterpret_cast<const float4*>(inb + (gy * w_in + gx0) * C);       // (4-byte aligned at least)
+        }
+        return ~0u;
+    }
+    unsigned bits = 0;
+    int gxc[G::PXU];
+    bool in_px[G::PXU];
+#pragma unroll
+    for (int px = 0; px < G::PXU; ++px) {
+        in_px[px] = (unsigned)(gx0 + px) < (unsigned)w_in;
+        gxc[px] = min(max(gx0 + px, 0), w_in - 1) * C;
+    }
+#pragma unroll
+    for (int k = 0; k < G::NPASS; ++k) {
+        const int gy = iy0 + sr + k * G::RPP;
+        const bool row_ok = (unsigned)gy < (unsigned)h_in;
+        const float* src = inb + min(max(gy, 0), h_in - 1) * w_in * C;
+#pragma unroll
+        for (int px = 0; px < G::PXU; ++px) {
+            if constexpr (C == 4) {
+                v[k] = *reinterpret_cast<const float4*>(src + gxc[px]);
+            } else if constexpr (C == 2) {
+                const float2 t = *reinterpret_cast<const float2*>(src + gxc[px]);
+                if (px == 0) v[k].x = t.x, v[k].y = t.y;
+                else v[k].z = t.x, v[k].w = t.y;
+            } else {
+                const float t = src[gxc[px]];
+                if (px == 0) v[k].x = t;
+                else if (px == 1) v[k].y = t;
+                else if (px == 2) v[k].z = t;
+                else v[k].w = t;
+            }
+            bits |= (row_ok && in_px[px] ? 1u : 0u) << (k * G::PXU + px);
+        }
+    }
+    return bits;
+}
+
+template <class G>
+__device__ __forceinline__ void tile_commit(float* tile, const float4 (&v)[G::NPASS], bool plain, unsigned bits, float pad,
+                                            int sr, int su) {
+#pragma unroll
+    for (int k = 0; k < G::NPASS; ++k) {
+        const int r = sr + k * G::RPP;
+        float4 t = v[k];
+        if (!plain) {
+            float* tf = reinterpret_cast<float*>(&t);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) tf[i] = (bits >> (k * G::PXU + i / G::C)) & 1u ? tf[i] : pad;
+        }
+        if (k * G::RPP + G::RPP <= G::IH || r < G::IH) *reinterpret_cast<float4*>(tile + r * G::RS + su * 4) = t;
+    }
+}
+
 // Persistent blocks over a flat tile index (image, tile row, column strip): block b takes tiles b, b + grid, ...
 // A tile is BR x BC positions; wave w owns its row bands w*RPW .. w*RPW + RPW - 1 (DY rows each), NCG chains of 16
-// columns per band.
+// columns per band.  What does not depend on the tile -- the zero fill, the weights, the wa[] operands, the bias -- is
+// made once per block; per tile: barrier, registers -> LDS, barrier, request the next tile, chains.
 //   in      [n][h_in][w_in][C]      float32
 //   out     [n][h_out][w_out][COUT] float32;  mask_y (backward-data: the activation OUTPUT of the layer below, same
 //           shape as out) multiplies the result by act'(y)
-template <class G>
+// ACT / MASK / BIAS: the epilogue kinds as compile-time tags (uocr_common.h), UOCR_ACT_DYN = from the arguments.
+template <class G, int ACT, int MASK, int BIAS>
 __global__ __launch_bounds__(256) void conv_t32_kernel(const float* __restrict__ in, const float* __restrict__ w,
                                                        const float* __restrict__ bias, float* __restrict__ out,
                                                        const float* __restrict__ mask_y, int h_in, int w_in, int h_out,
                                                        int w_out, int ph, int pw, int tiles_x, int tiles_y, int ntiles,
                                                        float pad, int use_bias, int act, float alpha, int mask_act,
                                                        float mask_alpha) {
-    constexpr int C = G::C, COUT = G::COUT, S = G::S, RS = G::RS;
+    constexpr int C = G::C, COUT = G::COUT, S = G::S, RS = G::RS, U = G::U;
     __shared__ __attribute__((aligned(16))) float tile[G::IHA * RS];
     __shared__ float wl[G::NW];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = lane & 15, kq = lane >> 4;
+    const int act_k = act_kind<ACT>(act), mask_k = act_kind<MASK>(mask_act);
+    const bool biased = act_kind<BIAS>(use_bias) != 0, masked = mask_k != UOCR_ACT_NONE;
+    // staging role of this thread: 16-byte unit su of tile rows sr, sr + RPP, ...
+    const int sr = tid / G::UW, su = tid - sr * G::UW;
+    const bool stager = sr < G::RPP;
 
-    // the rows / floats no load ever writes must read as zero (their weights are zero, 0 * garbage is not)
+    TileWalk walk(blockIdx.x, gridDim.x, tiles_x, tiles_y);
+    float4 v[G::NPASS];                                  // the next tile on its way (the first one: under the prologue)
+    bool plain = tile_plain<G>(walk.strip, walk.trow, h_in, w_in, ph, pw);
+    unsigned bits = 0;
+    if (stager) bits = tile_fetch<G>(v, in, plain, walk.strip, walk.trow, walk.img, h_in, w_in, ph, pw, sr, su);
+
+    // the rows / floats no load ever writes must read as zero (their weights are zero, 0 * garbage is not): every tile
+    // writes the same floats, so one fill serves all the tiles of the block
     for (int i = tid; i < G::IHA * RS; i += 256) tile[i] = 0.f;
     for (int i = tid; i < G::NW; i += 256) wl[i] = w[i];
     __syncthreads();
@@ -126,63 +224,34 @@ __global__ __launch_bounds__(256) void conv_t32_kernel(const float* __restrict__
     }
     float bias4[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) bias4[i] = use_bias ? bias[(4 * kq + i) % COUT] : 0.f;
-    // staging role of this thread: 16-byte unit su of tile rows sr, sr + RPP, ...
-    const int sr = tid / G::UW, su = tid - sr * G::UW;
-    const bool stager = sr < G::RPP;
+    for (int i = 0; i < 4; ++i) bias4[i] = biased ? bias[(4 * kq + i) % COUT] : 0.f;
 
-    TileWalk walk(blockIdx.x, gridDim.x, tiles_x, tiles_y);
-    for (int t = blockIdx.x; t < ntiles; t += gridDim.x, walk.next(tiles_x, tiles_y)) {
+    // where lane (column n, kq) stores: rows m = 4kq + i of a chain's result = (dy, (phase,) co).  Row and column
+    // relative to the chain's first output pixel; the i / hh part is added in the epilogue (wave-uniform).
+    //   4 channels: the 4 channels of one pixel; depth to space: phase = kq
+    //   2 channels: rows 2kq, 2kq + 1, both channels each
+    //   1 channel:  rows 4kq + i, or (depth to space) row kq, phase i
+    static_assert(COUT != 2 || U == 1, "2 channels: plain store only");
+    const int lrow = COUT == 4 ? (U == 2 ? kq >> 1 : kq) : COUT == 2 ? 2 * kq : (U == 2 ? 2 * kq : 4 * kq);
+    const int lcol = COUT == 4 && U == 2 ? 2 * n + (kq & 1) : U * n;
+    const int loff = (lrow * w_out + lcol) * COUT;       // (the bytes of BR * U + 1 output rows < 2^31: launch_t32)
+
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const int strip = walk.strip, trow = walk.trow, img = walk.img;
-        const int c_begin = strip * G::BC, r0 = trow * G::BR;
-        const float* inb = in + (size_t)img * h_in * w_in * C;
-        const size_t out_img = (size_t)img * h_out * w_out * COUT;
-        __syncthreads();                                 // the previous tile's reads are over (and the zero fill)
-        // ---- stage the input tile: pixel (iy0 + r, ix0 + c) -> tile[r][c*C ..], padding outside the image.
-        // The column part of a thread's address and its in-image bits are the same for all its rows.
-        if (stager) {
-            const int iy0 = r0 * S - ph, gx0 = c_begin * S - pw + su * G::PXU;
-            bool in_px[G::PXU];
-            bool all_in = true, any_in = false;
-#pragma unroll
-            for (int k = 0; k < G::PXU; ++k) {
-                in_px[k] = (unsigned)(gx0 + k) < (unsigned)w_in;
-                all_in = all_in && in_px[k];
-                any_in = any_in || in_px[k];
-            }
-            float4 v[G::NPASS];
-#pragma unroll
-            for (int k = 0; k < G::NPASS; ++k) {
-                const int gy = iy0 + sr + k * G::RPP;
-                const bool row_ok = (unsigned)gy < (unsigned)h_in;
-                const float* src = inb + (size_t)min(max(gy, 0), h_in - 1) * w_in * C;
-                v[k] = make_float4(pad, pad, pad, pad);
-                if (row_ok && all_in) {
-                    v[k] = *reinterpret_cast<const float4*>(src + (size_t)gx0 * C);      // (4-byte aligned at least)
-                } else if (row_ok && any_in) {                                          // the image edge cuts the unit
-                    float* vf = reinterpret_cast<float*>(&v[k]);
-#pragma unroll
-                    for (int px = 0; px < G::PXU; ++px)
-                        if (in_px[px]) {
-#pragma unroll
-                            for (int d = 0; d < C; ++d) vf[px * C + d] = src[(size_t)(gx0 + px) * C + d];
-                        }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < G::NPASS; ++k) {
-                const int r = sr + k * G::RPP;
-                if (r < G::IH) {
-                    if constexpr (RS % 4 == 0) {
-                        *reinterpret_cast<float4*>(tile + r * RS + su * 4) = v[k];
-                    } else {
-                        float* dst = tile + r * RS + su * 4;
-                        dst[0] = v[k].x, dst[1] = v[k].y, dst[2] = v[k].z, dst[3] = v[k].w;
-                    }
-                }
-            }
-        }
+        __syncthreads();                                 // the previous tile's reads are over
+        if (stager) tile_commit<G>(tile, v, plain, bits, pad, sr, su);
         __syncthreads();
+        if (t + (int)gridDim.x < ntiles) {
+            walk.next(tiles_x, tiles_y);
+            plain = tile_plain<G>(walk.strip, walk.trow, h_in, w_in, ph, pw);
+            if (stager) bits = tile_fetch<G>(v, in, plain, walk.strip, walk.trow, walk.img, h_in, w_in, ph, pw, sr, su);
+        }
+        // the tile's first output pixel, and how much of the image lies below / right of it (wave-uniform)
+        const size_t tile_off = ((size_t)img * h_out * w_out + (size_t)trow * (G::BR * U) * w_out + strip * (G::BC * U)) * COUT;
+        float* ot = out + tile_off;                      // (wave-uniform bases and an unsigned 32-bit lane offset)
+        const float* mt = masked ? mask_y + tile_off : nullptr;
+        const int hrem = h_out - trow * (G::BR * U) - lrow, wrem = w_out - strip * (G::BC * U) - lcol;
+        const bool whole = h_out - trow * (G::BR * U) >= G::BR * U && w_out - strip * (G::BC * U) >= G::BC * U;
         // ---- chains
 #pragma unroll
         for (int s = 0; s < G::RPW; ++s) {
@@ -191,7 +260,44 @@ __global__ __launch_bounds__(256) void conv_t32_kernel(const float* __restrict__
             // are issued (the compiler orders a read right before its use otherwise, and every batch of MFMAs then
             // waits out the LDS latency)
             const float* band = tile + (rb * S + kq) * RS + n * S * C;
-            float bcur[G::Q], bnxt[G::Q];
+            // result element i of chain cg in this lane: is it an output pixel, and where (floats from ot / mt; a lane
+            // without a pixel there points at the tile's first, which it may read but does not write)
+            const int crow = U * rb;                     // the band's first output row relative to the tile's
+            auto elem_ok = [&](int cg, int i) {
+                const int irow = COUT == 4 ? 0 : COUT == 2 ? i >> 1 : (U == 2 ? i >> 1 : i);
+                const int icol = COUT == 1 && U == 2 ? i & 1 : 0;
+                const bool live = COUT == 4 ? U == 2 || kq < G::DY : COUT == 2 ? 2 * kq + (i >> 1) < G::DY
+                                                                             : (U == 2 ? kq : 4 * kq + i) < G::DY;
+                return live && (whole || (crow + irow < hrem && U * cg * 16 + icol < wrem));
+            };
+            auto elem_off = [&](int cg, int i) -> unsigned {
+                const int coff = loff + (crow * w_out + U * cg * 16) * COUT;
+                int off;
+                if constexpr (COUT == 4) off = coff + i;
+                else if constexpr (COUT == 2) off = coff + (i >> 1) * w_out * 2 + (i & 1);
+                else off = coff + (U == 2 ? (i >> 1) * w_out + (i & 1) : i * w_out);
+                return elem_ok(cg, i) ? off : 0;
+            };
+            // the mask values of a chain's four results, one memory instruction per run of consecutive floats,
+            // requested a chain ahead: loads and stores share one in-order counter, so a wait for a mask value
+            // requested after the previous chain's store would wait for that store as well
+            auto mask_fetch = [&](float (&m)[4], int cg) {
+                if constexpr (COUT == 4) {
+                    const float4 my = *reinterpret_cast<const float4*>(mt + elem_off(cg, 0));
+                    m[0] = my.x, m[1] = my.y, m[2] = my.z, m[3] = my.w;
+                } else if constexpr (COUT == 2) {
+#pragma unroll
+                    for (int hh = 0; hh < 2; ++hh) {
+                        const float2 my = *reinterpret_cast<const float2*>(mt + elem_off(cg, 2 * hh));
+                        m[2 * hh] = my.x, m[2 * hh + 1] = my.y;
+                    }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) m[i] = mt[elem_off(cg, i)];
+                }
+            };
+            float bcur[G::Q], bnxt[G::Q], mcur[4], mnxt[4];
+            if (masked) mask_fetch(mcur, 0);
             load_row<G>(bcur, band);
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -201,6 +307,7 @@ __global__ __launch_bounds__(256) void conv_t32_kernel(const float* __restrict__
                     const int cg1 = (step + 1) / G::IB, ib1 = (step + 1) % G::IB;
                     load_row<G>(bnxt, band + cg1 * 16 * S * C + ib1 * 4 * RS);
                 }
+                if (masked && ib == 0 && cg + 1 < G::NCG) mask_fetch(mnxt, cg + 1);
 #pragma unroll
                 for (int e = 0; e < G::Q; ++e) acc = mfma4(wa[ib * G::Q + e], bcur[e], acc);
 #pragma unroll
@@ -208,80 +315,81 @@ __global__ __launch_bounds__(256) void conv_t32_kernel(const float* __restrict__
                 if (ib != G::IB - 1) continue;
                 const f32x4 res = acc;
                 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-                // lane (column n, kq): rows m = 4kq + i of the result = (dy, (phase,) co)
-                const int col = c_begin + cg * 16 + n;
-                float v[4];
+                float r[4];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = act_apply(res[i] + bias4[i], act, alpha);
-                if constexpr (COUT == 4) {               // the 4 channels of one pixel; depth to space: phase = kq
-                    const int row = G::U == 2 ? 2 * (r0 + rb) + (kq >> 1) : r0 + rb + kq;
-                    const int ocol = G::U == 2 ? 2 * col + (kq & 1) : col;
-                    if (row >= h_out || ocol >= w_out || (G::U == 1 && kq >= G::DY)) continue;
-                    const size_t off = out_img + ((size_t)row * w_out + ocol) * 4;
-                    if (mask_act != UOCR_ACT_NONE) {
-                        const float4 my = *reinterpret_cast<const float4*>(mask_y + off);
-                        v[0] *= act_grad_from_output<float>(my.x, mask_act, mask_alpha);
-                        v[1] *= act_grad_from_output<float>(my.y, mask_act, mask_alpha);
-                        v[2] *= act_grad_from_output<float>(my.z, mask_act, mask_alpha);
-                        v[3] *= act_grad_from_output<float>(my.w, mask_act, mask_alpha);
-                    }
-                    *reinterpret_cast<float4*>(out + off) = make_float4(v[0], v[1], v[2], v[3]);
-                } else if constexpr (COUT == 2) {        // rows 2kq, 2kq + 1, both channels each
-                    static_assert(COUT != 2 || G::U == 1, "2 channels: plain store only");
-                    if (col >= w_out) continue;
+                for (int i = 0; i < 4; ++i) {
+                    r[i] = act_apply(res[i] + bias4[i], act_k, alpha);
+                    if (masked) r[i] *= act_grad_from_output<float>(mcur[i], mask_k, mask_alpha);
+                    if (cg + 1 < G::NCG) mcur[i] = mnxt[i];
+                }
+                // the results are complete here on every path: were the mask product left to sink into the branch of
+                // the store, a wave that skips it would carry a pending mask load round the loop, and the wait-count
+                // pass would then drain every load -- the next tile's among them -- in front of the first chain
+                asm volatile("" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]));
+                if constexpr (COUT == 4) {
+                    if (elem_ok(cg, 0)) *reinterpret_cast<float4*>(ot + elem_off(cg, 0)) = make_float4(r[0], r[1], r[2], r[3]);
+                } else if constexpr (COUT == 2) {
 #pragma unroll
-                    for (int hh = 0; hh < 2; ++hh) {
-                        const int row = r0 + rb + 2 * kq + hh;
-                        if (row >= h_out || 2 * kq + hh >= G::DY) continue;
-                        const size_t off = out_img + ((size_t)row * w_out + col) * 2;
-                        float v0 = v[2 * hh], v1 = v[2 * hh + 1];
-                        if (mask_act != UOCR_ACT_NONE) {
-                            const float2 my = *reinterpret_cast<const float2*>(mask_y + off);
-                            v0 *= act_grad_from_output<float>(my.x, mask_act, mask_alpha);
-                            v1 *= act_grad_from_output<float>(my.y, mask_act, mask_alpha);
-                        }
-                        *reinterpret_cast<float2*>(out + off) = make_float2(v0, v1);
-                    }
-                } else {                                 // 1 channel: rows 4kq + i, or (depth to space) row kq, phase i
+                    for (int hh = 0; hh < 2; ++hh)
+                        if (elem_ok(cg, 2 * hh))
+                            *reinterpret_cast<float2*>(ot + elem_off(cg, 2 * hh)) = make_float2(r[2 * hh], r[2 * hh + 1]);
+                } else {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int dyi = G::U == 2 ? kq : 4 * kq + i;
-                        const int row = G::U == 2 ? 2 * (r0 + rb + dyi) + (i >> 1) : r0 + rb + dyi;
-                        const int ocol = G::U == 2 ? 2 * col + (i & 1) : col;
-                        if (row >= h_out || ocol >= w_out || dyi >= G::DY) continue;
-                        const size_t off = out_img + (size_t)row * w_out + ocol;
-                        float vi = v[i];
-                        if (mask_act != UOCR_ACT_NONE) vi *= act_grad_from_output<float>(mask_y[off], mask_act, mask_alpha);
-                        out[off] = vi;
-                    }
+                    for (int i = 0; i < 4; ++i)
+                        if (elem_ok(cg, i)) ot[elem_off(cg, i)] = r[i];
                 }
             }
         }
     }
 }
 
-template <class G>
-int launch_t32(uocr_ctx* ctx, const void* in, const void* w, const void* bias, void* out, const void* mask_y, int n,
-               int h_in, int w_in, int h_out, int w_out, int ph, int pw, float pad, int use_bias, int act, float alpha,
-               int mask_act, float mask_alpha) {
+// one instantiation: its residency, its grid and the launch
+template <class G, int ACT, int MASK, int BIAS>
+int launch_t32_kinds(uocr_ctx* ctx, const void* in, const void* w, const void* bias, void* out, const void* mask_y, int n,
+                     int h_in, int w_in, int h_out, int w_out, int ph, int pw, float pad, int use_bias, int act,
+                     float alpha, int mask_act, float mask_alpha) {
     static int resident = 0;                             // blocks of this kernel one CU holds
     if (resident == 0) {
         int nb = 0;
-        UOCR_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_t32_kernel<G>, 256, 0));
+        UOCR_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_t32_kernel<G, ACT, MASK, BIAS>, 256, 0));
         resident = nb > 0 ? nb : 1;
     }
     const int hp = (h_out + G::U - 1) / G::U, wp = (w_out + G::U - 1) / G::U;      // the position grid
     const int tiles_x = (wp + G::BC - 1) / G::BC, tiles_y = (hp + G::BR - 1) / G::BR;
     const long ntiles = (long)n * tiles_y * tiles_x;
-    UOCR_REQUIRE(ctx, ntiles < (1l << 31) && (long)h_in * w_in * G::C < (1l << 31));
-    const long cap = uocr_budget(ctx, (long)ctx->cu_count * resident * 4);   // (4 x: conv_h16.hip, the tail when lanes share the CUs)
+    UOCR_REQUIRE(ctx, ntiles < (1l << 31) && (long)h_in * w_in * G::C < (1l << 31) &&
+                          (long)(G::BR * G::U + 1) * w_out * G::COUT < (1l << 29));
+    // one block per resident slot: at 32 x 256 x 512 a block walks two or three tiles, with its prologue paid once and
+    // the next tile's loads under the chains of the current one
+    const long cap = uocr_budget(ctx, (long)ctx->cu_count * resident);
     const int grid = (int)(ntiles < cap ? ntiles : cap);
     uocr_note_split(ctx, grid, ntiles);
-    hipLaunchKernelGGL(conv_t32_kernel<G>, dim3(grid), dim3(256), 0, ctx->stream, (const float*)in, (const float*)w,
-                       (const float*)bias, (float*)out, (const float*)mask_y, h_in, w_in, h_out, w_out, ph, pw, tiles_x,
-                       tiles_y, (int)ntiles, pad, use_bias, act, alpha, mask_act, mask_alpha);
+    hipLaunchKernelGGL((conv_t32_kernel<G, ACT, MASK, BIAS>), dim3(grid), dim3(256), 0, ctx->stream, (const float*)in,
+                       (const float*)w, (const float*)bias, (float*)out, (const float*)mask_y, h_in, w_in, h_out, w_out, ph,
+                       pw, tiles_x, tiles_y, (int)ntiles, pad, use_bias, act, alpha, mask_act, mask_alpha);
     UOCR_LAUNCH_CHECK(ctx);
     return UOCR_OK;
+}
+
+// SIDE 0: a forward conv (bias, activation), SIDE 1: backward-data (no bias, mask).  The kinds become template tags
+// here, once per launch; a pair the nets do not use, a forward conv without bias and "act_dispatch" = 0 take the
+// instantiation with the dynamic tags.
+template <class G, int SIDE>
+int launch_t32(uocr_ctx* ctx, const void* in, const void* w, const void* bias, void* out, const void* mask_y, int n,
+               int h_in, int w_in, int h_out, int w_out, int ph, int pw, float pad, int use_bias, int act, float alpha,
+               int mask_act, float mask_alpha) {
+    return uocr_act_tags<SIDE>(ctx, act, mask_act, [&](auto kinds) {
+        using K = decltype(kinds);
+        if constexpr (!K::dynamic) {
+            if ((use_bias != 0) == (SIDE == 0))
+                return launch_t32_kinds<G, K::act, K::mask, SIDE == 0>(ctx, in, w, bias, out, mask_y, n, h_in, w_in, h_out,
+                                                                        w_out, ph, pw, pad, use_bias, act, alpha, mask_act,
+                                                                        mask_alpha);
+        }
+        return launch_t32_kinds<G, UOCR_ACT_DYN, UOCR_ACT_DYN, UOCR_ACT_DYN>(ctx, in, w, bias, out, mask_y, n, h_in, w_in,
+                                                                            h_out, w_out, ph, pw, pad, use_bias, act, alpha,
+                                                                            mask_act, mask_alpha);
+    });
 }
 
 inline bool same5x5(const ConvDims& d) {
@@ -311,7 +419,7 @@ int uocr_conv_fwd_t32(uocr_ctx* ctx, const void* x, const void* w, const void* b
                       double pad_value, int use_bias, int act, double act_alpha) {
     auto run = [&](auto geo) {
         using G = decltype(geo);
-        return launch_t32<G>(ctx, x, w, b, y, nullptr, d.n, d.h, d.w, d.oh, d.ow, d.ph, d.pw, (float)pad_value, use_bias,
+        return launch_t32<G, 0>(ctx, x, w, b, y, nullptr, d.n, d.h, d.w, d.oh, d.ow, d.ph, d.pw, (float)pad_value, use_bias,
                              act, (float)act_alpha, UOCR_ACT_NONE, 0.f);
     };
 #ifdef UOCR_EXPERIMENTS
@@ -329,7 +437,7 @@ int uocr_conv_dgrad_t32(uocr_ctx* ctx, const void* dy, const void* w, void* dx, 
     const int mact = mask.y ? mask.act : UOCR_ACT_NONE;
     auto run = [&](auto geo) {                           // a forward conv over dy with flipped taps: padding kh - 1 - ph
         using G = decltype(geo);
-        return launch_t32<G>(ctx, dy, w, nullptr, dx, mask.y, d.n, d.oh, d.ow, d.h, d.w, d.kh - 1 - d.ph,
+        return launch_t32<G, 1>(ctx, dy, w, nullptr, dx, mask.y, d.n, d.oh, d.ow, d.h, d.w, d.kh - 1 - d.ph,
                              d.kw - 1 - d.pw, 0.f, 0, UOCR_ACT_NONE, 0.f, mact, (float)mask.alpha);
     };
 #ifdef UOCR_EXPERIMENTS
@@ -353,9 +461,9 @@ int uocr_upconv_dgrad_t32(uocr_ctx* ctx, const void* dy, const void* w, void* dx
 #else
     const int mact = mask_y ? mask_act : UOCR_ACT_NONE;
     if (ch == 1)
-        return launch_t32<Geo<1, 1, 6, 6, 2, M_UPDGRAD, 4>>(ctx, dy, w, nullptr, dx_low, mask_y, n, 2 * hl, 2 * wl, hl, wl,
+        return launch_t32<Geo<1, 1, 6, 6, 2, M_UPDGRAD, 4>, 1>(ctx, dy, w, nullptr, dx_low, mask_y, n, 2 * hl, 2 * wl, hl, wl,
                                                              2, 2, 0.f, 0, UOCR_ACT_NONE, 0.f, mact, (float)mask_alpha);
-    return launch_t32<Geo<4, 4, 6, 6, 2, M_UPDGRAD>>(ctx, dy, w, nullptr, dx_low, mask_y, n, 2 * hl, 2 * wl, hl, wl, 2, 2,
+    return launch_t32<Geo<4, 4, 6, 6, 2, M_UPDGRAD>, 1>(ctx, dy, w, nullptr, dx_low, mask_y, n, 2 * hl, 2 * wl, hl, wl, 2, 2,
                                                      0.f, 0, UOCR_ACT_NONE, 0.f, mact, (float)mask_alpha);
 #endif
 }

@@ -113,10 +113,11 @@ constexpr int WTH = 16, WTW = 64, WH = WTH + 4, WW = WTW + 4;
 __device__ __forceinline__ int swz(int row, int c) { return row * WW + (c & 3) * (WW / 4) + (c >> 2); }
 }  // namespace wide
 
-template <typename TA>
+template <typename TA, class K>
 __global__ __launch_bounds__(256) void conv_fwd_t542(const TA* __restrict__ src, const float* __restrict__ w,
                                                      const float* __restrict__ bias, TA* __restrict__ dst, int h,
                                                      int wd, float pad, int use_bias, int act, float alpha) {
+    act = act_kind<K::act>(act);                 // (a constant unless the tag is dynamic: uocr_common.h)
     using namespace wide;
     __shared__ float4 xs[WH * WW];
     const int tid = threadIdx.x, cg = tid & 15, r = tid >> 4;
@@ -213,8 +214,12 @@ int uocr_conv_fwd_tiled(uocr_ctx* ctx, int dtype, const void* x, const void* w, 
     UOCR_DISPATCH_TA(ctx, dtype, {
         if (d.cout == 2 && d.ph == 2 && d.pw == 2 && ctx->opt_tiled != 2) {
             const dim3 wgrid((d.w + wide::WTW - 1) / wide::WTW, (d.h + wide::WTH - 1) / wide::WTH, d.n);
-            hipLaunchKernelGGL((conv_fwd_t542<TA>), wgrid, block, 0, ctx->stream, (const TA*)x, (const float*)w,
-                               (const float*)b, (TA*)y, d.h, d.w, (float)pad_value, use_bias, act, (float)act_alpha);
+            uocr_act_tags<0>(ctx, act, UOCR_ACT_NONE, [&](auto kinds) -> int {
+                hipLaunchKernelGGL((conv_fwd_t542<TA, decltype(kinds)>), wgrid, block, 0, ctx->stream, (const TA*)x,
+                                   (const float*)w, (const float*)b, (TA*)y, d.h, d.w, (float)pad_value, use_bias, act,
+                                   (float)act_alpha);
+                return UOCR_OK;
+            });
         } else if (d.cout == 4) {
             hipLaunchKernelGGL((conv_tiled_kernel<5, 5, 4, 4, TA>), grid, block, 0, ctx->stream, (const TA*)x,
                                (const float*)w, (const float*)b, (TA*)y, td, (float)pad_value, use_bias, act,

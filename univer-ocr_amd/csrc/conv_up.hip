@@ -110,11 +110,12 @@ __device__ __forceinline__ void stage_planar(float* __restrict__ xs, const TA* _
 
 // forward.  Block = 16 x 32 low-res positions per tile iteration over a band of rows; wave w owns rows
 // 4w..4w+3 (8 groups of 16 consecutive positions).
-template <typename TA>
+template <typename TA, class K>
 __global__ __launch_bounds__(256) void upconv_fwd_kernel(const TA* __restrict__ xl, const float* __restrict__ w,
                                                          const float* __restrict__ bias, TA* __restrict__ y,
                                                          int hl, int wl, int rows_per_block, int use_bias, int act,
                                                          float alpha, float* __restrict__ weff_out) {
+    act = act_kind<K::act>(act);                 // (a constant unless the tag is dynamic: uocr_common.h)
     __shared__ float xs[CH * XPLANE];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = lane & 15, kq = lane >> 4;
     // the per-phase 3 x 3 weights the backward-data kernel of this layer wants (upconv_weff_kernel's table), written by
@@ -292,11 +293,12 @@ __global__ __launch_bounds__(256) void colsum_finish_kernel(const float* __restr
 // dx on the vector ALU.  Block = 16 x 32 low-res positions, 2 per thread (rows r and r + 8); dy tile of the
 // (16 + 2) x (32 + 2) source blocks = 36 x 68 high-res pixels in LDS.
 constexpr int GH = 2 * (RH + 2), GW = 2 * (RW + 2);
-template <typename TA>
+template <typename TA, class K>
 __global__ __launch_bounds__(256) void upconv_dgrad_kernel(const TA* __restrict__ dy, const float* __restrict__ weff,
                                                            TA* __restrict__ dxl, int hl, int wl,
                                                            const TA* __restrict__ mask_y, int mask_act,
                                                            float mask_alpha) {
+    mask_act = act_kind<K::mask>(mask_act);                 // (a constant unless the tag is dynamic: uocr_common.h)
     __shared__ float4 gs[GH * GW];
     const int tid = threadIdx.x;
     const int rx = blockIdx.x * RW, ry = blockIdx.y * RH;
@@ -557,18 +559,21 @@ extern "C" int uocr_upconv2x_fwd(uocr_ctx* ctx, int dtype, const void* x_low, co
         return uocr_upconv_fwd_h16(ctx, x_low, w, b, y, n, hl, wl, use_bias, act, act_alpha);
     const int strips = (wl + RW - 1) / RW, rows = up_rows_per_block(strips, hl, n, (unsigned)uocr_budget(ctx, 2048));
     if (cin != 1) uocr_note_split(ctx, (long long)strips * ((hl + rows - 1) / rows) * n, (long long)strips * ((hl + RH - 1) / RH) * n);
+    return uocr_act_tags<0>(ctx, act, UOCR_ACT_NONE, [&](auto kinds) -> int {
+    using K = decltype(kinds);
     UOCR_DISPATCH_TA(ctx, dtype, {
         if (cin == 1)
             hipLaunchKernelGGL((up1_fwd_kernel<TA>), dim3((wl + RW - 1) / RW, (hl + RH - 1) / RH, n), dim3(256), 0,
                                ctx->stream, (const TA*)x_low, (const float*)w, (const float*)b, (TA*)y, hl, wl, use_bias,
                                act, (float)act_alpha);
         else
-            hipLaunchKernelGGL((upconv_fwd_kernel<TA>), dim3(strips, (hl + rows - 1) / rows, n), dim3(256), 0,
+            hipLaunchKernelGGL((upconv_fwd_kernel<TA, K>), dim3(strips, (hl + rows - 1) / rows, n), dim3(256), 0,
                                ctx->stream, (const TA*)x_low, (const float*)w, (const float*)b, (TA*)y, hl, wl, rows,
                                use_bias, act, (float)act_alpha, (float*)weff);
     });
     UOCR_LAUNCH_CHECK(ctx);
     return UOCR_OK;
+    });
 }
 
 extern "C" int uocr_upconv2x_bwd_data(uocr_ctx* ctx, int dtype, const void* dy, const void* w, void* dx_low, int n,
@@ -593,16 +598,19 @@ extern "C" int uocr_upconv2x_bwd_data(uocr_ctx* ctx, int dtype, const void* dy, 
         weff = (const float*)ctx->workspace;
     }
     const dim3 grid((wl + RW - 1) / RW, (hl + RH - 1) / RH, n);
+    return uocr_act_tags<1>(ctx, UOCR_ACT_NONE, act, [&](auto kinds) -> int {
+    using K = decltype(kinds);
     UOCR_DISPATCH_TA(ctx, dtype, {
         if (cin == 1)
             hipLaunchKernelGGL((up1_dgrad_kernel<TA>), grid, dim3(256), 0, ctx->stream, (const TA*)dy, (const float*)w,
                                (TA*)dx_low, hl, wl, (const TA*)x_act, act, (float)act_alpha);
         else
-            hipLaunchKernelGGL((upconv_dgrad_kernel<TA>), grid, dim3(256), 0, ctx->stream, (const TA*)dy,
+            hipLaunchKernelGGL((upconv_dgrad_kernel<TA, K>), grid, dim3(256), 0, ctx->stream, (const TA*)dy,
                                weff, (TA*)dx_low, hl, wl, (const TA*)x_act, act, (float)act_alpha);
     });
     UOCR_LAUNCH_CHECK(ctx);
     return UOCR_OK;
+    });
 }
 
 extern "C" int uocr_upconv2x_bwd_weight(uocr_ctx* ctx, int dtype, const void* x_low, const void* dy, void* dw, void* db,

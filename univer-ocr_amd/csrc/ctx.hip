@@ -46,6 +46,7 @@ int uocr_ctx_create(int device, size_t workspace_bytes, uocr_ctx** out) {
     ctx->opt_group_blocks = 0;
     ctx->opt_wgrad_bands = 0;
     ctx->opt_max_blocks = 0;
+    ctx->opt_act_dispatch = 1;
     ctx->split_blocks = 0;
     ctx->split_items = 0;
     ctx->gemm_bm = ctx->gemm_gm = ctx->gemm_gn = ctx->gemm_nsplit = 0;
@@ -153,6 +154,7 @@ int uocr_ctx_set_option(uocr_ctx* ctx, const char* key, int value) {
     else if (!strcmp(key, "group_blocks")) ctx->opt_group_blocks = value;
     else if (!strcmp(key, "wgrad_bands") && value >= 0) ctx->opt_wgrad_bands = value;
     else if (!strcmp(key, "max_blocks") && value >= 0) ctx->opt_max_blocks = value;
+    else if (!strcmp(key, "act_dispatch")) ctx->opt_act_dispatch = value != 0;
     else if (!strcmp(key, "h3")) {
 #ifndef UOCR_EXPERIMENTS
         if (value) UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "option h3: this library was built without conv_h3 "

@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "univer_hip.h"
 
 struct uocr_ctx {
@@ -37,6 +39,7 @@ struct uocr_ctx {
     int opt_group_blocks; // blocks of a deferred weight-gradient group (0 = four per CU)
     int opt_wgrad_bands;  // row bands per tap / channel group of the direct weight-gradient kernels (0 = by accumulator count)
     int opt_pair_g;      // groups of 16 columns per wave of the strip kernels: 4 (8 waves per block) or 2 (16 waves)
+    int opt_act_dispatch; // 1 = activation / mask kinds the nets use are compile-time tags of the kernel (default), 0 = the run-time switch
     int opt_max_blocks;  // k > 0 lowers every run-time block budget to k (tests: several tiles per block at small shapes)
     int split_blocks;    // uocr_ctx_last_split: blocks and work items of the last launch with a run-time split
     long long split_items;
@@ -311,6 +314,42 @@ __device__ __forceinline__ T act_grad_from_output(T y, int act, T alpha) {
     if (act == UOCR_ACT_LEAKY) return y >= T(0) ? T(1) : alpha;
     if (act == UOCR_ACT_SIGMOID) return y * (T(1) - y);
     return T(1);
+}
+
+// ---- epilogue kinds at compile time
+// A kernel that applies act(v) to its results or multiplies them by act'(y) takes the two kinds as the template tags
+// ActKinds<ACT, MASK>.  UOCR_ACT_DYN in a place keeps the run-time switch on the kernel argument: the same template, one
+// body, and what every pair the nets never use runs.  act_kind<KIND>(argument) is the kind a kernel works with: a
+// constant unless the tag is dynamic, so the switches of act_apply / act_grad_from_output fold away.
+constexpr int UOCR_ACT_DYN = -1;
+template <int ACT, int MASK>
+struct ActKinds {
+    static constexpr int act = ACT, mask = MASK;
+    static constexpr bool dynamic = ACT == UOCR_ACT_DYN;
+};
+// (a launcher keeps the tags only for the instantiations where they were measured to pay)
+template <bool KEEP, class K>
+using ActKindsIf = std::conditional_t<KEEP, K, ActKinds<UOCR_ACT_DYN, UOCR_ACT_DYN>>;
+template <int KIND>
+__host__ __device__ __forceinline__ int act_kind(int argument) {
+    return KIND == UOCR_ACT_DYN ? argument : KIND;
+}
+// Calls f(ActKinds<..>{}) with the tags of (act, mask_act) where the four nets use that pair, with the dynamic tags for
+// every other pair and when the "act_dispatch" option is 0.  SIDE 0: forward epilogues (no mask; none / LeakyReLU /
+// Sigmoid), SIDE 1: masked backward-data (no activation; no mask / LeakyReLU').
+template <int SIDE, class F>
+static inline int uocr_act_tags(const uocr_ctx* ctx, int act, int mask_act, F&& f) {
+    if (ctx->opt_act_dispatch) {
+        if constexpr (SIDE == 0) {
+            if (mask_act == UOCR_ACT_NONE && act == UOCR_ACT_NONE) return f(ActKinds<UOCR_ACT_NONE, UOCR_ACT_NONE>{});
+            if (mask_act == UOCR_ACT_NONE && act == UOCR_ACT_LEAKY) return f(ActKinds<UOCR_ACT_LEAKY, UOCR_ACT_NONE>{});
+            if (mask_act == UOCR_ACT_NONE && act == UOCR_ACT_SIGMOID) return f(ActKinds<UOCR_ACT_SIGMOID, UOCR_ACT_NONE>{});
+        } else {
+            if (act == UOCR_ACT_NONE && mask_act == UOCR_ACT_NONE) return f(ActKinds<UOCR_ACT_NONE, UOCR_ACT_NONE>{});
+            if (act == UOCR_ACT_NONE && mask_act == UOCR_ACT_LEAKY) return f(ActKinds<UOCR_ACT_NONE, UOCR_ACT_LEAKY>{});
+        }
+    }
+    return f(ActKinds<UOCR_ACT_DYN, UOCR_ACT_DYN>{});
 }
 
 // A tile staging loop `for (i = tid; i < COUNT; i += NT) lds[i] = in_image(i) ? load(i) : fill` compiles to ONE load, a wait
