@@ -426,6 +426,31 @@ int uocr_char_label(uocr_ctx* ctx, int dtype, int n_lines, const void* const* x,
  * lines per launch, launches issued (all 0 before the first call) -- tests size their inputs from it */
 int uocr_ctx_last_char_label(uocr_ctx* ctx, int* cols_per_block, int* stats_chunk, int* lines_per_launch, int* launches);
 
+/* ---- line crops (interpreter/interpreter.py:504-523 CropRotateAndZoomLines._func2: the gather half of LineCrop) ----
+ * Crop, quarter-turn, zoom and pad every (array, line) pair of a page in one call.  Entry i cuts the box [y0, y0 + box_h)
+ * x [x0, x0 + box_w) out of src[i]: (1, src_h, src_w, c) in `dtype` (nothing is masked, :506), turns it by
+ * quarter_turns * 90 degrees (np.rot90(.., quarter_turns, axes=(1, 2)), which ndimage.rotate(.., axes=(2, 1), order=1,
+ * reshape=True) of 90 / 180 / 270 degrees equals bit for bit; 0 = upright) and zooms the turned box -- rot_h x rot_w,
+ * (box_w, box_h) for an odd number of turns -- to zoom_h x zoom_w as ndimage.zoom(.., order=0) does: per axis z =
+ * (n_in - 1) / (n_out - 1), one float64 division made on the host (n_out = 1 reads index 0); output index j reads input
+ * index floor(j * z + 0.5), the product and the sum each rounded to float64 on their own, and where j * z comes out
+ * above n_in - 1 (a rounding artefact of scipy's that only the last index of an axis can show) the element is 0.
+ * Columns zoom_w .. out_w - 1 are zero (the reference's padding to CHAR_FIXED_WIDTH, :516-521).  The caller chooses
+ * zoom_h, zoom_w (the reference: Python round(n * zoom_h / rot_h), which may give zoom_w = 0) and out_w.
+ * out[i]: (1, zoom_h, out_w, c) in `dtype`, EVERY element written.  A pure index map: results are equal to the
+ * reference's in every dtype.  All arguments but ctx, dtype and n_entries are HOST arrays of n_entries entries.
+ * UOCR_ERR_ARG for null pointers (out[i] may be NULL where out_w[i] = 0), pointers off their element's alignment, a box
+ * that is empty or not inside its source, quarter_turns outside 0..3, out_w < zoom_w, zoom_h < 1, zoom_w < 0, c < 1 and
+ * n_entries < 0; UOCR_ERR_UNSUPPORTED for an output too large for one grid; nothing is written on any error.  n_entries = 0 is UOCR_OK and launches nothing (the other arguments are not looked at).  One launch per 48
+ * entries; no workspace, no atomics.  Asynchronous and capturable. */
+int uocr_line_crop(uocr_ctx* ctx, int dtype, int n_entries, const void* const* src, const int* src_h, const int* src_w,
+                   const int* c, const int* y0, const int* x0, const int* box_h, const int* box_w,
+                   const int* quarter_turns, const int* zoom_h, const int* zoom_w, void* const* out, const int* out_w);
+/* sizes the last uocr_line_crop call on this ctx used: output elements per block (an entry's output is cut into flat
+ * ranges of that many elements), bytes per vector store, entries per launch, launches issued (all 0 before the first
+ * call) -- tests size their inputs from it */
+int uocr_ctx_last_line_crop(uocr_ctx* ctx, int* elements_per_block, int* store_bytes, int* entries_per_launch, int* launches);
+
 /* ---- data parallel over the GPUs of one node: RCCL over xGMI ------------------------------------
  * The reference has no multi-GPU path; BASELINE.json adds one to the step loop my_model/trainer.py:213-233
  * -> nn/model_system.py:104-118 -> nn/models.py:250-254: between compute_loss_and_gradients and update_grads

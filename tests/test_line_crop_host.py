@@ -1,0 +1,426 @@
+"""Host side of the LineCrop feature: the fixture tests/golden/line_crop.npz (made from the reference's label_layer,
+rearrange_lines, CropRotateAndZoomLines._func1 / _func2 and LabelChar._func1 by tests/golden/make_golden_line_crop.py), the
+NumPy restatement of the stage that the GPU tests use as expected value at sizes the fixture cannot know (trusted only
+because it is pinned to the fixture here and, where scipy is installed, to ndimage.rotate / ndimage.zoom over a sweep of
+sizes), the host pairing logic of my_model/crop.py, the TRAIN_CHAR system's assembly and the ABI names.  Nothing here
+needs a GPU."""
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, load_golden
+from test_char_label_host import char_label_rules
+
+ZOOMED_HEIGHT, MINIMAL_WIDTH = 32, 8
+NEW_SYMBOLS = {'uocr_line_crop': 16, 'uocr_ctx_last_line_crop': 5}        # name -> arguments, the context included
+ROTATIONS = (0, 90, 180, 270)                                             # 0: the reference's None
+STAGE_NAMES = ('upright', 'shared', 'turned', 'stray')
+LINES_OF_THE_PAGE = ((0, 0), (0, 1), (1, 0))
+
+
+# ---- the restatement ---------------------------------------------------------------------------------------------------
+def zoom_indices(n_in, n_out):
+    """ndimage.zoom at order 0 along one axis: per output index the input index it reads, -1 where scipy writes 0.
+    z = (n_in - 1) / (n_out - 1) in float64 (one output element reads index 0); index j reads floor(j * z + 0.5), the
+    product and the sum each rounded on their own; where j * z exceeds n_in - 1 scipy's constant mode gives 0"""
+    if n_out <= 1:
+        return [0] * n_out
+    z = (n_in - 1) / (n_out - 1)
+    return [-1 if j * z > n_in - 1 else int(math.floor(j * z + 0.5)) for j in range(n_out)]
+
+
+def zoom_rules(a, n_rows, n_cols):
+    """a (1, h, w, c) -> (1, n_rows, n_cols, c)"""
+    rows, cols = np.array(zoom_indices(a.shape[1], n_rows), int), np.array(zoom_indices(a.shape[2], n_cols), int)
+    out = a[0][np.ix_(np.maximum(rows, 0), np.maximum(cols, 0))]
+    out[rows < 0] = 0
+    out[:, cols < 0] = 0
+    return out[None]
+
+
+def line_crop_rules(image, y0, x0, box_h, box_w, rotation, zoomed_height=ZOOMED_HEIGHT, minimal_width=MINIMAL_WIDTH):
+    """steps 3-4 for one line and one array: crop the box, np.rot90 by rotation / 90, zoom to zoomed_height rows (sizes by
+    Python round of n * zf, half to even), zero-pad the width up to minimal_width"""
+    a = np.rot90(image[:, y0:y0 + box_h, x0:x0 + box_w, :], (rotation or 0) // 90, axes=(1, 2))
+    zf = zoomed_height / a.shape[1]
+    a = zoom_rules(a, int(round(a.shape[1] * zf)), int(round(a.shape[2] * zf)))
+    out = np.zeros((1, a.shape[1], max(a.shape[2], minimal_width), a.shape[3]), image.dtype)
+    out[:, :, :a.shape[2]] = a
+    return out
+
+
+def label_rules(on):
+    """scipy's ndimage.label of a boolean (H, W) image with the default structure: 4-connected components numbered in the
+    order of their first pixel, row by row -> int labels (H, W), count"""
+    labels, count = np.zeros(on.shape, int), 0
+    for y, x in zip(*np.nonzero(on)):
+        if labels[y, x]:
+            continue
+        count += 1
+        labels[y, x] = count
+        todo = [(y, x)]
+        while todo:
+            cy, cx = todo.pop()
+            for ny, nx in ((cy - 1, cx), (cy + 1, cx), (cy, cx - 1), (cy, cx + 1)):
+                if 0 <= ny < on.shape[0] and 0 <= nx < on.shape[1] and on[ny, nx] and not labels[ny, nx]:
+                    labels[ny, nx] = count
+                    todo.append((ny, nx))
+    return labels, count
+
+
+def components_rules(layer):
+    """step 1 for one channel (H, W): the components of layer > (mean + max) / 2 -> [(centre (y, x), box (y0, y1, x0, x1))]"""
+    labels, count = label_rules(layer > 0.5 * (np.mean(layer) + np.max(layer)))
+    found = []
+    for k in range(1, count + 1):
+        ys, xs = np.nonzero(labels == k)
+        found.append(((ys.sum() / len(ys), xs.sum() / len(xs)), (ys.min(), ys.max() + 1, xs.min(), xs.max() + 1)))
+    return found
+
+
+def find_lines_rules(mask):
+    """steps 1-3 for one paragraph mask (1, H, W, 2): (rotation, [(y0, x0, height, width)] in output order), or
+    (0, []) where the reference raises"""
+    tops, bottoms = components_rules(mask[0, :, :, 0]), components_rules(mask[0, :, :, 1])
+    if not tops or not bottoms:
+        return 0, []
+    distance = lambda p, q: math.sqrt((p[0] - q[0]) ** 2 + (p[1] - q[1]) ** 2)
+    paired = [sorted(bottoms, key=lambda b: distance(t[0], b[0]))[0] for t in tops]       # (sorted is stable)
+    dy, dx = tops[0][0][0] - bottoms[0][0][0], tops[0][0][1] - bottoms[0][0][1]
+    if abs(dy) > abs(dx):
+        rotation, key = (0, lambda item: item[0][0]) if dy < 0 else (180, lambda item: -item[0][0])
+    elif dx < 0:
+        rotation, key = 270, lambda item: item[0][1]
+    elif dx > 0:
+        rotation, key = 90, lambda item: -item[0][1]
+    else:
+        return 0, []
+    boxes = []
+    for (_, t), (_, b) in zip(sorted(tops, key=key), sorted(paired, key=key)):
+        y0, y1, x0, x1 = min(t[0], b[0]), max(t[1], b[1]), min(t[2], b[2]), max(t[3], b[3])
+        boxes.append((y0, x0, y1 - y0, x1 - x0))
+    return rotation, boxes
+
+
+def crop_lines_rules(mask, arrays):
+    """the whole stage for one paragraph: (rotation, boxes, result[array][line])"""
+    rotation, boxes = find_lines_rules(mask)
+    return rotation, boxes, [[line_crop_rules(a, *box, rotation) for box in boxes] for a in arrays]
+
+
+def paragraph_crops_rules(mask, arrays, multiple=16):
+    """ParagraphCrop without the rotation search, then make_divisible_by: result[array][paragraph]"""
+    from univer_ocr_amd.my_model.model import make_divisible_by
+    labels, count = label_rules(mask[0, :, :, 0] > np.mean(mask))
+    result = [[] for _ in arrays]
+    for k in range(1, count + 1):
+        ys, xs = np.nonzero(labels == k)
+        window = (slice(None), slice(ys.min(), ys.max() + 1), slice(xs.min(), xs.max() + 1))
+        for i, a in enumerate(arrays):
+            result[i].append(make_divisible_by((a * (labels == k)[None, :, :, None])[window], multiple, multiple))
+    return result
+
+
+# ---- the fixture ---------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope='module')
+def g():
+    return load_golden('line_crop')
+
+
+def f64(a):
+    return np.asarray(a, np.float64)
+
+
+def gather_cases(g):
+    """(case, c, rotation, image, (y0, x0, box_h, box_w), expected) for every gather/ entry; float64"""
+    for i, (k, y0, x0, bh, bw) in enumerate(g['gather/cases'].tolist()):
+        for c in (1, 9):
+            for rotation in ROTATIONS:
+                yield i, c, rotation, f64(g[f'gather/img{c}_{k}']), (y0, x0, bh, bw), f64(g[f'gather/{i}/c{c}/r{rotation}'])
+
+
+def stage_lines(g, name, c):
+    return [f64(g[f'stage/{name}/c{c}/{line}']) for line in range(len(g[f'stage/{name}/boxes']))]
+
+
+def test_fixture_loads_and_is_consistent(g):
+    assert os.path.getsize(os.path.join(ROOT, 'tests', 'golden', 'line_crop.npz')) <= os.path.getsize(
+        os.path.join(ROOT, 'tests', 'golden', 'paragraph_crop.npz'))
+    boxes = [tuple(row[3:]) for row in g['gather/cases'].tolist()]
+    assert {(32, 40), (16, 20), (64, 10), (33, 31), (5, 8), (37, 64), (64, 1), (32, 3), (32, 8), (32, 257)} <= set(boxes)
+    for i, c, rotation, image, (y0, x0, bh, bw), expected in gather_cases(g):
+        assert image.shape[3] == c and 0 < y0 and y0 + bh < image.shape[1] and 0 < x0 and x0 + bw < image.shape[2]
+        assert bh != bw and image.min() >= 1 / 64 and image.max() <= 1 and np.array_equal(image * 64, np.round(image * 64))
+        assert expected.shape[:2] == (1, ZOOMED_HEIGHT) and expected.shape[2] >= MINIMAL_WIDTH and expected.shape[3] == c
+    assert [str(s) for s in g['stage/names']] == list(STAGE_NAMES)
+    assert {int(g[f'stage/{name}/rotation']) for name in STAGE_NAMES} == set(ROTATIONS)
+    for name in STAGE_NAMES:
+        mask = f64(g[f'stage/{name}/mask'])
+        assert mask.ndim == 4 and mask.shape[0] == 1 and mask.shape[3] == 2 and 2 <= len(g[f'stage/{name}/boxes']) <= 4
+        for ch in range(2):
+            layer = mask[..., ch]
+            assert np.min(np.abs(layer - 0.5 * (layer.mean() + layer.max()))) > 1e-3, f'{name}: a mask value within 1e-3 of t'
+    for p, l in LINES_OF_THE_PAGE:
+        mono, char, labels = g[f'system/mono{p}_{l}'], g[f'system/char{p}_{l}'], g[f'system/labels{p}_{l}']
+        assert mono.shape[:2] == (1, 32) and mono.shape[3] == 1 and char.shape == (*mono.shape[:3], 9)
+        assert labels.shape == (mono.shape[2], 162)
+
+
+def test_rules_reproduce_the_gather_cases(g):
+    """the restatement equals _func2 on every gather/ entry, and the special columns occur where the issue says"""
+    seen = set()
+    for i, c, rotation, image, box, expected in gather_cases(g):
+        got = line_crop_rules(image, *box, rotation)
+        assert got.shape == expected.shape and np.array_equal(got, expected), f'case {i} {box} c={c} rotation {rotation}'
+        rh, rw = box[2:] if rotation in (0, 180) else box[:1:-1]
+        zoom_w = int(round(rw * (ZOOMED_HEIGHT / rh)))
+        columns = zoom_indices(rw, zoom_w)
+        seen |= {'artefact'} if -1 in columns else set()
+        seen |= {'empty'} if zoom_w == 0 else set()
+        seen |= {'padded'} if 0 < zoom_w < MINIMAL_WIDTH else set()
+        seen |= {'exact half'} if zoom_w > 1 and any((j * ((rw - 1) / (zoom_w - 1))) % 1 == 0.5 for j in range(zoom_w)) else set()
+        if -1 in columns:
+            assert columns.index(-1) == zoom_w - 1 and not expected[:, :, zoom_w - 1].any() and expected[:, :, :zoom_w - 1].all()
+    assert seen == {'artefact', 'empty', 'padded', 'exact half'}
+
+
+def test_rules_reproduce_the_stage_cases(g):
+    """steps 1-4 restated give the reference's rotation, line order, boxes and arrays for every stage/ paragraph"""
+    for name in STAGE_NAMES:
+        mask, images = f64(g[f'stage/{name}/mask']), [f64(g[f'stage/{name}/img1']), f64(g[f'stage/{name}/img9'])]
+        rotation, boxes, result = crop_lines_rules(mask, images)
+        assert rotation == int(g[f'stage/{name}/rotation']), name
+        assert np.array_equal(np.array(boxes), g[f'stage/{name}/boxes']), name
+        for c, per_line in zip((1, 9), result):
+            for got, expected in zip(per_line, stage_lines(g, name, c)):
+                assert got.shape == expected.shape and np.array_equal(got, expected), f'{name} c={c}'
+
+
+def test_stage_cases_are_what_they_claim(g):
+    """label order differs from reading order; a bottom serves two tops; a bottom serves none"""
+    def pairing(name):
+        mask = f64(g[f'stage/{name}/mask'])
+        tops, bottoms = components_rules(mask[0, :, :, 0]), components_rules(mask[0, :, :, 1])
+        nearest = [min(range(len(bottoms)), key=lambda b: math.dist(t[0], bottoms[b][0])) for t in tops]
+        return tops, bottoms, nearest
+    tops, _, _ = pairing('upright')
+    assert [t[0][0] for t in tops] != sorted(t[0][0] for t in tops)
+    _, bottoms, nearest = pairing('shared')
+    assert len(nearest) == 3 and len(set(nearest)) == 2 == len(bottoms)
+    _, bottoms, nearest = pairing('stray')
+    assert len(bottoms) == 3 and len(set(nearest)) == 2 == len(nearest)
+
+
+def test_arrange_lines_and_line_boxes_equal_the_reference(g):
+    """the host logic of my_model/crop.py on the components of every stage/ mask and of the system's paragraphs"""
+    from univer_ocr_amd.my_model.crop import QUARTER_TURNS, arrange_lines, line_boxes
+    assert QUARTER_TURNS == {None: 0, 90: 1, 180: 2, 270: 3}
+    for name in STAGE_NAMES:
+        mask = f64(g[f'stage/{name}/mask'])
+        tops, bottoms = components_rules(mask[0, :, :, 0]), components_rules(mask[0, :, :, 1])
+        top_ids, bottom_ids, rotation = arrange_lines([t[0] for t in tops], [b[0] for b in bottoms])
+        assert (rotation or 0) == int(g[f'stage/{name}/rotation']), name
+        boxes = line_boxes([t[1] for t in tops], [b[1] for b in bottoms], top_ids, bottom_ids)
+        assert np.array_equal(np.array(boxes), g[f'stage/{name}/boxes']), name
+    # where the reference raises: no top, no bottom, the first top on the first bottom
+    assert arrange_lines([], [(1.0, 2.0)]) is None and arrange_lines([(1.0, 2.0)], []) is None
+    assert arrange_lines(np.zeros((0, 2)), np.zeros((0, 2))) is None
+    assert arrange_lines([(3.0, 4.0), (9.0, 4.0)], [(3.0, 4.0)]) is None
+    # |dy| = |dx| goes by dx; a tie between two bottoms goes to the first in label order
+    assert arrange_lines([(5.0, 5.0)], [(7.0, 7.0)]) == ([0], [0], 270)
+    assert arrange_lines([(5.0, 5.0)], [(7.0, 3.0)]) == ([0], [0], 90)
+    assert arrange_lines([(2.0, 5.0), (6.0, 5.0)], [(4.0, 5.0), (8.0, 5.0)]) == ([0, 1], [0, 0], None)
+    assert arrange_lines([(2.0, 5.0), (6.0, 5.0)], [(0.5, 5.0), (4.5, 5.0)]) == ([1, 0], [1, 0], 180)
+    # the direction is taken from the FIRST bottom in label order, not the paired one
+    assert arrange_lines([(10.0, 5.0), (20.0, 5.0)], [(4.0, 5.0), (13.0, 5.0), (23.0, 5.0)])[2] == 180
+
+
+def test_rules_equal_scipy_over_a_sweep_of_sizes():
+    """np.rot90 + the index rule against ndimage.rotate / ndimage.zoom as _func2 calls them, at sizes that include the
+    last-index artefact, exact halves, empty zooms and one-row / one-column boxes"""
+    ndimage = pytest.importorskip('scipy.ndimage')
+    rng = np.random.default_rng(40)
+    sizes = {(33, 31), (5, 8), (37, 64), (64, 10), (64, 1), (1, 64), (1, 1), (2, 2), (32, 40), (16, 20), (129, 3), (3, 129)}
+    sizes |= {(int(h), int(w)) for h, w in zip(rng.integers(1, 130, 120), rng.integers(1, 300, 120))}
+    artefacts = halves = empty = 0
+    for n, (h, w) in enumerate(sorted(sizes)):
+        a = rng.integers(1, 65, (1, h, w, 1 + n % 3)) / 64.0
+        for angle in (None, 90, 180, 270)[n % 2::2] if h * w > 4000 else (None, 90, 180, 270):
+            turned = a if angle is None else ndimage.rotate(a, angle, axes=(2, 1), order=1, reshape=True)
+            assert np.array_equal(turned, np.rot90(a, (angle or 0) // 90, axes=(1, 2))), (h, w, angle)
+            zf = ZOOMED_HEIGHT / turned.shape[1]
+            zoomed = ndimage.zoom(turned, (1, zf, zf, 1), order=0)
+            got = line_crop_rules(a, 0, 0, h, w, angle, minimal_width=0)
+            assert got.shape == zoomed.shape and np.array_equal(got, zoomed), (h, w, angle)
+            columns = zoom_indices(turned.shape[2], zoomed.shape[2])
+            artefacts += -1 in columns
+            empty += zoomed.shape[2] == 0
+            halves += zoomed.shape[2] > 1 and any((j * ((turned.shape[2] - 1) / (zoomed.shape[2] - 1))) % 1 == 0.5
+                                                  for j in range(zoomed.shape[2]))
+    assert len(sizes) >= 100 and artefacts >= 10 and halves >= 3 and empty >= 2, (len(sizes), artefacts, halves, empty)
+
+
+def test_line_crop_shape_equals_the_fixture(g):
+    from univer_ocr_amd.nn.ops import line_crop_shape
+    for i, c, rotation, image, (y0, x0, bh, bw), expected in gather_cases(g):
+        zoom_h, zoom_w, out_w = line_crop_shape(bh, bw, rotation // 90, ZOOMED_HEIGHT, MINIMAL_WIDTH)
+        assert (zoom_h, out_w) == expected.shape[1:3] and zoom_w <= out_w and out_w == max(zoom_w, MINIMAL_WIDTH)
+        assert not expected[:, :, zoom_w:].any()
+    for name in STAGE_NAMES:
+        turns = int(g[f'stage/{name}/rotation']) // 90
+        for (_, _, bh, bw), expected in zip(g[f'stage/{name}/boxes'].tolist(), stage_lines(g, name, 1)):
+            assert line_crop_shape(bh, bw, turns)[::2] == expected.shape[1:3]
+    assert line_crop_shape(64, 1, 0) == (32, 0, 8) and line_crop_shape(64, 1, 1) == (32, 2048, 2048)
+    assert line_crop_shape(64, 10, 0) == (32, 5, 8)
+    assert line_crop_shape(5, 7, 1, None, None) == (7, 5, 5) and line_crop_shape(5, 7, 2, None, 8) == (5, 7, 8)
+    assert line_crop_shape(20, 5, 0, 8, 1) == (8, 2, 2)            # 5 * 0.4 = 2.0; (20, 25): 10.0; round half to even:
+    assert line_crop_shape(16, 5, 0, 8, 1) == (8, 2, 2) and line_crop_shape(16, 7, 0, 8, 1) == (8, 4, 4)   # 2.5 -> 2, 3.5 -> 4
+
+
+def test_system_fixture_follows_from_the_page(g):
+    """ParagraphCrop, make_divisible_by, LineCrop and CharLabel restated on the page give the lines and labels the
+    reference's Char net was trained on"""
+    page = {tag: f64(g[f'system/page/{tag}']) for tag in ('monochrome', 'paragraph', 'line', 'char')}
+    mono, line, char = paragraph_crops_rules(page['paragraph'], [page['monochrome'], page['line'], page['char']])
+    assert [m.shape[1:3] for m in mono] == [(64, 48), (32, 48)]
+    for p in range(2):
+        rotation, boxes, (mono_lines, char_lines) = crop_lines_rules(line[p], [mono[p], char[p]])
+        assert rotation == 0 and len(boxes) == (2, 1)[p]
+        for l in range(len(boxes)):
+            assert np.array_equal(mono_lines[l], f64(g[f'system/mono{p}_{l}'])), f'mono[{p}][{l}]'
+            assert np.array_equal(char_lines[l], f64(g[f'system/char{p}_{l}'])), f'char[{p}][{l}]'
+            assert np.array_equal(char_label_rules(char_lines[l])[0], f64(g[f'system/labels{p}_{l}'])), f'labels[{p}][{l}]'
+
+
+# ---- CropLines, the component and the system -----------------------------------------------------------------------------
+def test_crop_lines_refuses_masks_and_arrays_that_do_not_fit():
+    from univer_ocr_amd.my_model.crop import CropLines
+    from univer_ocr_amd.nn import CP
+    crop_lines = CropLines()
+    assert (crop_lines.zoomed_height, crop_lines.minimal_width) == (ZOOMED_HEIGHT, MINIMAL_WIDTH)
+    good, array = CP.zeros((1, 12, 16, 2), np.float32), CP.zeros((1, 12, 16, 9), np.float32)
+    for bad in (CP.zeros((1, 12, 16, 1), np.float32), CP.zeros((2, 12, 16, 2), np.float32), CP.zeros((12, 16, 2), np.float32),
+                CP.zeros((1, 12, 16, 3), np.float32)):
+        with pytest.raises(ValueError, match=r'\(1, H, W, 2\)'):
+            crop_lines([good, bad], [[array, array]])
+    for other in (CP.zeros((1, 12, 15, 9), np.float32), CP.zeros((1, 11, 16, 9), np.float32), CP.zeros((12, 16, 9), np.float32)):
+        with pytest.raises(ValueError, match='does not match the mask'):
+            crop_lines([good], [[array], [other]])
+    with pytest.raises(ValueError, match='one per paragraph'):
+        crop_lines([good, good], [[array]])
+
+
+def test_crop_lines_makes_one_call_per_page_and_keeps_the_nesting(monkeypatch):
+    from univer_ocr_amd.my_model import crop
+    from univer_ocr_amd.nn import CP
+    found = [(90, [(1, 2, 3, 4), (2, 3, 4, 5)]), (None, []), (180, [(0, 0, 5, 6)])]
+    calls = []
+
+    def stub(entries, zoomed_height, minimal_width):
+        calls.append((list(entries), zoomed_height, minimal_width))
+        return [f'crop{i}' for i, _ in enumerate(entries)]
+    monkeypatch.setattr(crop.ops, 'line_crop', stub)
+    monkeypatch.setattr(crop.CropLines, 'find_lines', lambda self, masks: found[:len(masks)])
+    masks = [CP.zeros((1, 12, 16, 2), np.float32) for _ in range(3)]
+    a, b = ([CP.zeros((1, 12, 16, c), np.float32) for _ in range(3)] for c in (1, 9))
+    result = crop.CropLines(24, 6)(masks, [a, b])
+    assert result == [[['crop0', 'crop1'], [], ['crop2']], [['crop3', 'crop4'], [], ['crop5']]]
+    assert len(calls) == 1 and calls[0][1:] == (24, 6)
+    assert [(id(e[0]), *e[1:]) for e in calls[0][0]] == [
+        (id(a[0]), 1, 2, 3, 4, 1), (id(a[0]), 2, 3, 4, 5, 1), (id(a[2]), 0, 0, 5, 6, 2),
+        (id(b[0]), 1, 2, 3, 4, 1), (id(b[0]), 2, 3, 4, 5, 1), (id(b[2]), 0, 0, 5, 6, 2)]
+    assert crop.CropLines()([], [[], []]) == [[], []] and calls[1][0] == []
+
+
+def test_line_crop_of_nothing_and_of_wrong_entries():
+    """an empty page needs no device; ranks, boxes, turns and dtypes are checked before any call"""
+    from univer_ocr_amd.nn import CP, ops
+    assert ops.line_crop([]) == []
+    good = CP.zeros((1, 10, 12, 9), np.float32)
+    for bad in (CP.zeros((10, 12, 9), np.float32), CP.zeros((2, 10, 12, 9), np.float32), np.zeros((1, 10, 12, 9))):
+        with pytest.raises(ValueError, match='line_crop: expected'):
+            ops.line_crop([(good, 0, 0, 4, 4, 0), (bad, 0, 0, 4, 4, 0)])
+    for box in ((0, 0, 11, 4), (0, 9, 4, 4), (-1, 0, 4, 4), (0, 0, 0, 4), (7, 0, 4, 4)):
+        with pytest.raises(ValueError, match='empty or not inside'):
+            ops.line_crop([(good, *box, 0)])
+    for turns in (-1, 4):
+        with pytest.raises(ValueError, match='quarter_turns'):
+            ops.line_crop([(good, 0, 0, 4, 4, turns)])
+    with pytest.raises(ValueError, match='share a dtype'):
+        ops.line_crop([(good, 0, 0, 4, 4, 0), (CP.zeros((1, 10, 12, 1), np.float64), 0, 0, 4, 4, 0)])
+
+
+def test_train_char_system_is_built_without_a_gpu(monkeypatch):
+    from univer_ocr_amd.my_model import crop
+    from univer_ocr_amd.my_model.model import (CharSelector, make_line_crop_component, make_train_char_context_maker,
+                                               make_train_char_system)
+    from univer_ocr_amd.nn.model_system import ModelComponent, ModelSystem, RawFunctionComponent
+    from univer_ocr_amd.nn.progress_tracker import ProgressTracker
+    tracker = ProgressTracker(handler=lambda *a: None)
+    system, models, names = make_train_char_system((1, 32, 24, 1), progress_tracker=tracker)
+    assert names == ['ParagraphCrop', 'LineCrop', 'CharLabel', 'Char'] and list(models) == ['Char']
+    assert isinstance(system, ModelSystem) and len(system.components) == 4
+    assert all(isinstance(c, RawFunctionComponent) for c in system.components[:3])
+    char = system.components[3]
+    assert isinstance(char, ModelComponent) and char.model is models['Char'] and isinstance(char.selector, CharSelector)
+    assert (char.selector.X_label, char.selector.y_label, char.selector.pred_label) == ('cropped_2_monochrome', 'char_labels', 'char_pred')
+    assert {'ParagraphCrop', 'LineCrop', 'CharLabel', 'Char'} <= set(tracker.layers)
+    # the LineCrop component files CropLines()(context[mask], [context[source], ...]) at the targets, in every mode
+    monkeypatch.setattr(crop.CropLines, '__call__', lambda self, masks, arrays: [[[f'{tag}{p}'] for p, _ in enumerate(masks)] for tag in arrays])
+    component = make_line_crop_component()
+    for run in (component.train, component.test, component.predict):
+        context = {'cropped_line': ['m0', 'm1'], 'cropped_monochrome': 'mono', 'cropped_char': 'char'}
+        run(context)
+        assert context['cropped_2_monochrome'] == [['mono0'], ['mono1']] and context['cropped_2_char'] == [['char0'], ['char1']]
+    other = make_line_crop_component(mask='line_pred', sources=('a',), targets=('b',))
+    context = {'line_pred': ['m'], 'a': 'x'}
+    other.train(context)
+    assert context['b'] == [['x0']]
+    with pytest.raises(ValueError, match='sources'):
+        make_line_crop_component(sources=('a', 'b'), targets=('c',))
+    # the context maker asks the dataset for the four layers and files them under the names ParagraphCrop reads
+    asked = []
+
+    def get(index, layer_tags=None):
+        asked.append((index, list(layer_tags)))
+        return {tag: np.full((1, 4, 4, 1), i) for i, tag in enumerate(layer_tags)}
+    context = make_train_char_context_maker()(get, (3,))
+    assert asked == [(3, ['char', 'line', 'monochrome', 'paragraph'])]
+    assert sorted(context) == ['char', 'line', 'monochrome_pred', 'paragraph_pred']
+
+
+def test_enum_modes_still_raise_and_say_where_the_system_is():
+    from univer_ocr_amd.my_model.model import Modes, make_context_maker, make_model_system
+    for mode in (Modes.TRAIN_CHAR, Modes.TRAIN_ALL):
+        with pytest.raises(NotImplementedError, match='LineCrop') as info:
+            make_model_system((1, 32, 32, 1), mode=mode)
+        assert 'make_train_char_system' in str(info.value)
+        with pytest.raises(NotImplementedError, match='LineCrop') as info:
+            make_context_maker(mode)
+        assert 'make_train_char_system' in str(info.value)
+
+
+# ---- ABI ---------------------------------------------------------------------------------------------------------------
+def test_header_and_binding_declare_the_new_entry_points():
+    from univer_ocr_amd.hip import lib as hiplib
+    header = open(os.path.join(ROOT, 'include', 'univer_hip.h')).read()
+    for name, arguments in NEW_SYMBOLS.items():
+        declaration = re.search(r'\bint\s+' + name + r'\s*\(([^)]*)\)', header)
+        assert declaration, f'{name} is not declared in univer_hip.h'
+        assert len(declaration.group(1).split(',')) == arguments
+        assert name in hiplib.ABI_SYMBOLS and len(hiplib._PROTOS[name]) == arguments
+    assert re.search(r'#define\s+UOCR_ABI_VERSION\s+4\b', header), 'symbols are added, the ABI version stays'
+
+
+def test_library_exports_the_new_entry_points():
+    from univer_ocr_amd.hip import lib as hiplib
+    lib = hiplib.get_lib()
+    assert lib.uocr_abi_version() == 4
+    for name in NEW_SYMBOLS:
+        assert getattr(lib, name)
+    # without a context both refuse with UOCR_ERR_ARG before touching anything
+    assert lib.uocr_line_crop(None, 0, 0, *[None] * 13) == -1
+    assert lib.uocr_ctx_last_line_crop(None, None, None, None, None) == -1

@@ -14,8 +14,63 @@ first; a number that is no class is "unknown"), let every column vote over its r
 wins a tie, "unknown" is one candidate) and write a one-hot row, or a zero row where "unknown" won.  The reference does
 this in a Python loop per pixel on a worker pool, between a device-to-host and a host-to-device copy of every line; here
 all lines of all paragraphs of a page are ONE kernel call (nn/ops.py: char_label) and nothing leaves HBM.
+
+CropLines is the reference's CropRotateAndZoomLines (interpreter/interpreter.py:421-523).  Per paragraph, the two
+channels of the line mask (line_top, line_bottom) are thresholded at (mean + max) / 2 of their own and labelled
+(:437-453; label_layer's second threshold at the mean changes nothing) -- nn/ops.py: label_components with 'mean_max'.
+The host reads the two component tables, nothing else, and `arrange_lines` restates rearrange_lines (:42-82) on the
+centres of mass: which bottom belongs to which top, which way the text runs, the reading order.  A line's box is the
+union of its two components' boxes (:494-502); every companion array is cut to it unmasked, turned by a multiple of 90
+degrees so that the text reads left to right, zoomed to 32 rows at order 0 and zero-padded to 8 columns (:504-523).  All
+lines of all paragraphs and all arrays of a page are ONE kernel call (nn/ops.py: line_crop); there is no worker pool.
 """
+import numpy as np
+
 from ..nn import ops
+from .model import CHAR_FIXED_WIDTH, CHAR_INPUT_HEIGHT
+
+QUARTER_TURNS = {None: 0, 90: 1, 180: 2, 270: 3}     # the reference's `rotation` -> np.rot90's k
+
+
+def arrange_lines(top_centers, bottom_centers):
+    """rearrange_lines (interpreter.py:42-82) on the (y, x) centres of mass of a paragraph's line_top and line_bottom
+    components, both in label order: returns (top_ids, bottom_ids, rotation) -- line i of the paragraph is made of top
+    component top_ids[i] and bottom component bottom_ids[i] (0-based), rotation is None, 90, 180 or 270 -- or None where
+    the reference raises: no top, no bottom, or the first top's centre on the first bottom's.
+      * every top takes the bottom whose centre is nearest, the first in label order on a tie; a bottom may serve two tops
+        or none
+      * the direction is the first top's centre minus the centre of the FIRST bottom in label order (not the paired
+        one); the reference's `*= 1000` loop only pushes positive components past the image, so the sign decides:
+        |dy| > |dx|: dy < 0 upright, lines by y ascending; dy > 0 180, by y descending;
+        otherwise: dx < 0 270, by x ascending; dx > 0 90, by x descending
+      * tops are sorted by their own centres and the paired bottoms SEPARATELY by theirs, both stably"""
+    top = np.asarray(top_centers, np.float64).reshape(-1, 2)
+    bottom = np.asarray(bottom_centers, np.float64).reshape(-1, 2)
+    if not len(top) or not len(bottom):
+        return None
+    paired = np.array([int(np.argmin([np.linalg.norm(t - b) for b in bottom])) for t in top])
+    dy, dx = top[0] - bottom[0]
+    if abs(dy) > abs(dx):
+        rotation, key = (None, top[:, 0]) if dy < 0 else (180, -top[:, 0])
+        bottom_key = bottom[paired, 0] if dy < 0 else -bottom[paired, 0]
+    elif dx < 0:
+        rotation, key, bottom_key = 270, top[:, 1], bottom[paired, 1]
+    elif dx > 0:
+        rotation, key, bottom_key = 90, -top[:, 1], -bottom[paired, 1]
+    else:
+        return None
+    return (np.argsort(key, kind='stable').tolist(), paired[np.argsort(bottom_key, kind='stable')].tolist(), rotation)
+
+
+def line_boxes(top_boxes, bottom_boxes, top_ids, bottom_ids):
+    """_func1 (interpreter.py:494-502): per line (y0, x0, height, width) of the union of its two components' boxes
+    (boxes: y0, y1, x0, x1, half-open)"""
+    result = []
+    for t, b in zip(top_ids, bottom_ids):
+        (ty0, ty1, tx0, tx1), (by0, by1, bx0, bx1) = top_boxes[t], bottom_boxes[b]
+        y0, y1, x0, x1 = min(ty0, by0), max(ty1, by1), min(tx0, bx0), max(tx1, bx1)
+        result.append((int(y0), int(x0), int(y1 - y0), int(x1 - x0)))
+    return result
 
 
 class CropParagraphs:
@@ -41,6 +96,54 @@ class CropParagraphs:
         components = ops.label_components(mask, 'mean', self.max_components)
         paragraphs = int(components.count[0])
         return [[ops.masked_crop(a, components, 0, k, divisible_by) for k in range(1, paragraphs + 1)] for a in arrays]
+
+
+class CropLines:
+    def __init__(self, zoomed_height=CHAR_INPUT_HEIGHT, minimal_width=CHAR_FIXED_WIDTH, max_components=4096):
+        self.zoomed_height, self.minimal_width = zoomed_height, minimal_width    # (None: no zoom / no padding, :511, :516)
+        self.max_components = max_components
+
+    def find_lines(self, masks):
+        """per paragraph (rotation, [(y0, x0, height, width) per line in reading order]) from masks[p]: (1, H, W, 2);
+        (None, []) for a paragraph where the reference would raise"""
+        components = []
+        for mask in masks:
+            _, h, w, _ = mask.shape
+            top, bottom = ops.split(mask, [(1, h, w, 1), (1, h, w, 1)])
+            components.append((ops.label_components(top, 'mean_max', self.max_components),
+                               ops.label_components(bottom, 'mean_max', self.max_components)))
+        found = []
+        for top, bottom in components:                              # (the component tables: the only host traffic)
+            arranged = arrange_lines(top.center_of_mass[0], bottom.center_of_mass[0])
+            if arranged is None:
+                found.append((None, []))
+            else:
+                top_ids, bottom_ids, rotation = arranged
+                found.append((rotation, line_boxes(top.boxes[0], bottom.boxes[0], top_ids, bottom_ids)))
+        return found
+
+    def __call__(self, masks, arrays):
+        """masks[p]: (1, H, W, 2) DeviceArrays, line_top in channel 0 and line_bottom in channel 1; arrays[a][p]:
+        (1, H, W, C) DeviceArrays of the same H, W.  Returns result[a][p][line], the nesting of the reference, every
+        line (1, zoomed_height, >= minimal_width, C), lines in reading order.  Where the reference would raise -- a
+        paragraph without a line_top component, without a line_bottom component, or whose first top and first bottom
+        share a centre -- the paragraph yields no lines.  One kernel call for the page."""
+        masks = [ops.as_device(m) for m in masks]
+        arrays = [[ops.as_device(a) for a in per_array] for per_array in arrays]
+        for mask in masks:
+            if mask.ndim != 4 or mask.shape[0] != 1 or mask.shape[3] != 2:
+                raise ValueError(f'CropLines: a mask must have shape (1, H, W, 2) -- line_top, line_bottom -- got {mask.shape}')
+        for per_array in arrays:
+            if len(per_array) != len(masks):
+                raise ValueError(f'CropLines: {len(per_array)} arrays for {len(masks)} masks (one per paragraph)')
+            for a, mask in zip(per_array, masks):
+                if a.ndim != 4 or a.shape[:3] != mask.shape[:3]:
+                    raise ValueError(f'CropLines: array {a.shape} does not match the mask {mask.shape}')
+        found = self.find_lines(masks)
+        entries = [(per_array[p], y0, x0, bh, bw, QUARTER_TURNS[rotation])
+                   for per_array in arrays for p, (rotation, boxes) in enumerate(found) for y0, x0, bh, bw in boxes]
+        crops = iter(ops.line_crop(entries, self.zoomed_height, self.minimal_width))
+        return [[[next(crops) for _ in boxes] for _, boxes in found] for _ in arrays]
 
 
 class LabelChars:

@@ -9,10 +9,11 @@ channel counts, kernel sizes and losses, so `model_weights.json` files are inter
               dense 512->1024->128->162, softmax cross-entropy                     (:250-304)
 
 Every conv carries L2(0.01) (model.py:36-39).  Of the stages that sit between the nets in the
-reference's model system (host code, interpreter/), ParagraphCrop without the rotation search runs on
-the device (my_model/crop.py), which is what TRAIN_LINE needs, and CharLabel runs there too
-(`make_char_label_component`); LineCrop and PredToText have no device form yet, and `make_model_system` says
-so for the modes that need them (TRAIN_CHAR waits for LineCrop only).
+reference's model system (host code, interpreter/), ParagraphCrop without the rotation search, LineCrop and
+CharLabel run on the device (my_model/crop.py): TRAIN_LINE is `make_model_system(mode=Modes.TRAIN_LINE)`, and
+`make_train_char_system` assembles [ParagraphCrop, LineCrop, CharLabel, Char], the reference's TRAIN_CHAR system.
+PredToText and the rotation search have no device form yet, and `make_model_system` says so for the modes that need
+them; the TRAIN_CHAR and TRAIN_ALL members of `Modes` are not routed to the new system yet and say where it is.
 """
 from enum import Enum
 
@@ -204,6 +205,27 @@ def make_char_label_component(progress_tracker=None, source='cropped_2_char', ta
     return RawFunctionComponent(char_label)
 
 
+def make_line_crop_component(progress_tracker=None, mask='cropped_line', sources=('cropped_monochrome', 'cropped_char'),
+                             targets=('cropped_2_monochrome', 'cropped_2_char')):
+    """model.py:595-612 (make_line_crop_component) as a device component: context[mask][paragraph] is the paragraph's
+    (1, H, W, 2) line mask (the reference reads it as `line_pred_cpu`, in TRAIN_CHAR the renamed `cropped_line_cpu`,
+    :635-637), context[source][paragraph] a companion array; context[target][paragraph][line] becomes the line cut out
+    of it, turned upright, zoomed to CHAR_INPUT_HEIGHT rows and padded to CHAR_FIXED_WIDTH columns
+    (my_model/crop.py: CropLines).  One kernel call for the page; the host reads the component tables only."""
+    from .crop import CropLines
+    crop_lines = CropLines(CHAR_INPUT_HEIGHT, CHAR_FIXED_WIDTH)
+    if len(sources) != len(targets):
+        raise ValueError(f'make_line_crop_component: {len(sources)} sources for {len(targets)} targets')
+
+    @track_function('LineCrop', 'forward', progress_tracker)
+    def line_crop(context):
+        results = crop_lines(context[mask], [context[source] for source in sources])
+        for target, result in zip(targets, results):
+            context[target] = result
+
+    return RawFunctionComponent(line_crop)
+
+
 class LineSelector(IterableSelector):
     """One sample per paragraph (model.py:353-373): context[X_label][p], context[y_label][p]; the prediction of
     paragraph p is filed at context[pred_label][p].  The position starts over with every bind."""
@@ -270,9 +292,12 @@ class CharSelector(LineSelector):
 
 # what the modes that still raise are waiting for (the reference's component order, model.py:489-500)
 _MISSING_STAGE = {
-    'TRAIN_CHAR': 'LineCrop (interpreter.py CropRotateAndZoomLines: ndimage.rotate / zoom of every line)',
-    'TRAIN_ALL': 'LineCrop (interpreter.py CropRotateAndZoomLines: ndimage.rotate / zoom of every line)',
-    'PREDICT': 'the rotation search of ParagraphCrop (find_rotation=True), LineCrop and PredToText',
+    'TRAIN_CHAR': 'this mode is not routed through the device LineCrop stage yet: build the system [ParagraphCrop, '
+                  'LineCrop, CharLabel, Char] with make_train_char_system and its context with '
+                  'make_train_char_context_maker',
+    'TRAIN_ALL': 'the nets have not been chained through the device ParagraphCrop / LineCrop / CharLabel stages yet '
+                 '(TRAIN_CHAR alone is make_train_char_system)',
+    'PREDICT': 'the rotation search of ParagraphCrop (find_rotation=True) and PredToText',
 }
 
 
@@ -304,7 +329,7 @@ def make_context_maker(mode=Modes.PREDICT):
     }
     if mode not in wanted:
         raise NotImplementedError(
-            f'{mode.name} needs a stage that has no device form yet: {_MISSING_STAGE[mode.name]} '
+            f'{mode.name} has no context maker here: {_MISSING_STAGE[mode.name]} '
             f'(the device stages are in my_model/crop.py)')
     mapping = wanted[mode]
 
@@ -334,7 +359,7 @@ def make_model_system(input_shape, optimizer=None, progress_tracker=None, weight
     }
     if mode not in plan:
         raise NotImplementedError(
-            f'{mode.name} needs a stage that has no device form yet: {_MISSING_STAGE[mode.name]}; '
+            f'{mode.name} is not assembled by make_model_system: {_MISSING_STAGE[mode.name]}; '
             f'use TRAIN_MONOCHROME / TRAIN_PARAGRAPH / TRAIN_LINE / TRAIN_PAGE')
     components, models = [], {}
     for name in plan[mode]:
@@ -371,3 +396,46 @@ def _make_train_line_system(input_shape, optimizer, progress_tracker, weights):
     line = ModelComponent('Line', model, LineSelector('cropped_monochrome', 'cropped_line', 'line_pred'),
                           delist_result=True)
     return ModelSystem([RawFunctionComponent(paragraph_crop), line]), {'Line': model}, ['ParagraphCrop', 'Line']
+
+
+def make_train_char_context_maker():
+    """model.py:449-459 (the TRAIN_CHAR context) for `make_train_char_system`: the layers monochrome, paragraph, line and
+    char of one page, moved to the device (the reference keeps them on the host for its host stages)."""
+    mapping = {'monochrome_pred': 'monochrome', 'paragraph_pred': 'paragraph', 'line': 'line', 'char': 'char'}
+
+    def make_context(dataset_get_func, args=(), kwargs={}):
+        layers = dataset_get_func(*args, layer_tags=sorted(mapping.values()), **kwargs)
+        return {label: CP.copy(layers[tag]) for label, tag in mapping.items()}
+    return make_context
+
+
+def make_train_char_system(input_shape, optimizer=None, progress_tracker=None, weights=None):
+    """model.py:632-645: the reference's TRAIN_CHAR system built with find_rotation=False, minus its rename and move
+    components -- no array visits the host between the stages.  Returns (model_system, {'Char': model},
+    ['ParagraphCrop', 'LineCrop', 'CharLabel', 'Char']).
+      ParagraphCrop  labels context['paragraph_pred'], cuts context['monochrome_pred'], ['line'] and ['char'] to every
+                     paragraph and pads the crops to multiples of 16: context['cropped_monochrome' / '_line' / '_char']
+      LineCrop       finds the lines of every paragraph in cropped_line and cuts them out of cropped_monochrome and
+                     cropped_char: context['cropped_2_monochrome'][p][l], ['cropped_2_char'][p][l]
+      CharLabel      context['char_labels'][p][l] from cropped_2_char
+      Char           one step per line through a CharSelector; predictions at context['char_pred'][p][l]
+    input_shape is the Char net's, (batch, *, width, channels): its height is CHAR_INPUT_HEIGHT."""
+    from .crop import CropParagraphs
+    crop_paragraphs = CropParagraphs(find_rotation=False)
+
+    @track_function('ParagraphCrop', 'forward', progress_tracker)
+    def paragraph_crop(context):
+        crops = crop_paragraphs(context['paragraph_pred'], [context['monochrome_pred'], context['line'], context['char']],
+                                divisible_by=(16, 16))
+        context['cropped_monochrome'], context['cropped_line'], context['cropped_char'] = crops
+
+    model = make_char(input_shape, optimizer)
+    if progress_tracker is not None:
+        model.init_progress_tracker(progress_tracker, 'Char')
+    if weights is not None:
+        model.set_weights(weights)
+    char = ModelComponent('Char', model, CharSelector('cropped_2_monochrome', 'char_labels', 'char_pred'),
+                          delist_result=True)
+    components = [RawFunctionComponent(paragraph_crop), make_line_crop_component(progress_tracker),
+                  make_char_label_component(progress_tracker), char]
+    return ModelSystem(components), {'Char': model}, ['ParagraphCrop', 'LineCrop', 'CharLabel', 'Char']

@@ -187,6 +187,14 @@ class Runtime:
         self.call('uocr_ctx_last_char_label', *[C.byref(x) for x in v])
         return tuple(x.value for x in v)
 
+    def last_line_crop(self):
+        """(output elements per block, bytes per vector store, entries per launch, kernel launches) of the most recent
+        uocr_line_crop call on the current lane (uocr_ctx_last_line_crop); all 0 before the first."""
+        import ctypes as C
+        v = [C.c_int() for _ in range(4)]
+        self.call('uocr_ctx_last_line_crop', *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
     def set_loss_snapshot(self, arena):
         """From now on the fused optimizer tails launched on the CURRENT lane end by copying `arena`'s slots into the next
         row of its ring (LossArena.arm); None switches it off."""

@@ -625,6 +625,53 @@ def char_label(lines, bits, n_chars, want_ids=False):
     return (labels, ids) if want_ids else labels
 
 
+# ---- line crops (interpreter/interpreter.py:504-523: the gather half of LineCrop) -------------------------------------
+def line_crop_shape(box_h, box_w, quarter_turns, zoomed_height=32, minimal_width=8):
+    """(zoom_h, zoom_w, out_w) of a box_h x box_w box after `quarter_turns` turns of 90 degrees, ndimage.zoom by
+    zf = zoomed_height / height in both directions (:512-514: output sizes are Python round(n * zf), half to even; the
+    width may come out 0) and zero padding of the width up to minimal_width (:516-521).  None switches a step off, as in
+    the reference."""
+    h, w = (box_w, box_h) if quarter_turns % 2 else (box_h, box_w)
+    if zoomed_height is not None:
+        zf = zoomed_height / h
+        h, w = int(round(h * zf)), int(round(w * zf))
+    return h, w, w if minimal_width is None else max(w, minimal_width)
+
+
+def line_crop(entries, zoomed_height=32, minimal_width=8):
+    """CropRotateAndZoomLines._func2 (interpreter.py:504-523) for a flat list of entries (array, y0, x0, box_h, box_w,
+    quarter_turns): the box of the (1, H, W, C) DeviceArray `array`, turned by quarter_turns * 90 degrees (0-3; the
+    reference's rotation None / 90 / 180 / 270), zoomed to zoomed_height rows at order 0 and zero-padded to minimal_width
+    columns.  ONE uocr_line_crop call for all entries, whatever their sizes and channel counts (none for an empty list);
+    returns the (1, zoomed_height, out_w, C) DeviceArrays in the entries' order and dtype."""
+    entries = [(a, int(y0), int(x0), int(bh), int(bw), int(turns)) for a, y0, x0, bh, bw, turns in entries]
+    for a, y0, x0, bh, bw, turns in entries:
+        if not isinstance(a, DeviceArray) or a.ndim != 4 or a.shape[0] != 1:
+            raise ValueError(f'line_crop: expected (1, H, W, C) device arrays, got {getattr(a, "shape", type(a))}')
+        if not (0 <= y0 and 0 <= x0 and bh >= 1 and bw >= 1 and y0 + bh <= a.shape[1] and x0 + bw <= a.shape[2]):
+            raise ValueError(f'line_crop: the box [{y0}, {y0 + bh}) x [{x0}, {x0 + bw}) is empty or not inside {a.shape}')
+        if not 0 <= turns <= 3:
+            raise ValueError(f'line_crop: quarter_turns must be 0, 1, 2 or 3, got {turns}')
+    if not entries:
+        return []
+    code = entries[0][0].code & 0xff
+    if any(a.code & 0xff != code for a, *_ in entries):
+        raise ValueError('line_crop: the arrays of one call share a dtype, got ' +
+                         ', '.join(sorted({str(a.dtype) for a, *_ in entries})))
+    import ctypes as C
+    n = len(entries)
+    shapes = [line_crop_shape(bh, bw, turns, zoomed_height, minimal_width) for _, _, _, bh, bw, turns in entries]
+    outs = [CP.empty((1, zh, ow, a.shape[3]), a.dtype) for (a, *_), (zh, _, ow) in zip(entries, shapes)]
+    pointers = lambda arrays: (C.c_void_p * n)(*[a.ptr for a in arrays])
+    ints = lambda values: (C.c_int * n)(*values)
+    _rt().call('uocr_line_crop', code, n, pointers([e[0] for e in entries]), ints([e[0].shape[1] for e in entries]),
+               ints([e[0].shape[2] for e in entries]), ints([e[0].shape[3] for e in entries]), ints([e[1] for e in entries]),
+               ints([e[2] for e in entries]), ints([e[3] for e in entries]), ints([e[4] for e in entries]),
+               ints([e[5] for e in entries]), ints([s[0] for s in shapes]), ints([s[1] for s in shapes]), pointers(outs),
+               ints([s[2] for s in shapes]))
+    return outs
+
+
 class _Ops:
     add = staticmethod(add)
 
