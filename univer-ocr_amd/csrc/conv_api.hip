@@ -4,8 +4,6 @@
 
 namespace {
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 int check_dims(uocr_ctx* ctx, const ConvDims& d) {
     UOCR_REQUIRE(ctx, d.n > 0 && d.h > 0 && d.w > 0 && d.cin > 0 && d.cout > 0);
     UOCR_REQUIRE(ctx, d.kh > 0 && d.kw > 0 && d.sh > 0 && d.sw > 0 && d.ph >= 0 && d.pw >= 0);
@@ -32,10 +30,10 @@ int uocr_conv2d_fwd(uocr_ctx* ctx, int dtype, const void* x, const void* w, cons
     if (uocr_conv_h16_eligible(ctx, dtype, d, 0) && uocr_aligned_act(x, dtype) && uocr_aligned_act(y, dtype))
         return uocr_noted_conv(ctx, 0, UOCR_CONV_H16,
                                uocr_conv_fwd_h16(ctx, x, w, b, y, d, pad_value, use_bias, act, act_alpha));
-    if (uocr_conv_t32_eligible(ctx, dtype, d, 0) && aligned16(x) && aligned16(y))
+    if (uocr_conv_t32_eligible(ctx, dtype, d, 0) && uocr_aligned16(x) && uocr_aligned16(y))
         return uocr_noted_conv(ctx, 0, UOCR_CONV_T32,
                                uocr_conv_fwd_t32(ctx, x, w, b, y, d, pad_value, use_bias, act, act_alpha));
-    if (uocr_conv_h3_eligible(ctx, dtype, d) && aligned16(x) && aligned16(y))
+    if (uocr_conv_h3_eligible(ctx, dtype, d) && uocr_aligned16(x) && uocr_aligned16(y))
         return uocr_noted_conv(ctx, 0, UOCR_CONV_H3,
                                uocr_conv_fwd_h3(ctx, x, w, b, y, d, pad_value, use_bias, act, act_alpha));
     if (uocr_conv_tiled_eligible(ctx, dtype, d) && uocr_aligned_act(x, dtype) && uocr_aligned_act(y, dtype))
@@ -63,7 +61,7 @@ int uocr_conv2d_bwd_data(uocr_ctx* ctx, int dtype, const void* dy, const void* w
     if (uocr_conv_h16_eligible(ctx, dtype, d, 1) && uocr_aligned_act(dy, dtype) && uocr_aligned_act(dx, dtype) &&
         (!mask.y || uocr_aligned_act(mask.y, dtype)))
         return uocr_noted_conv(ctx, 1, UOCR_CONV_H16, uocr_conv_dgrad_h16(ctx, dy, w, dx, d, mask));
-    if (uocr_conv_t32_eligible(ctx, dtype, d, 1) && aligned16(dy) && aligned16(dx) && (!mask.y || aligned16(mask.y)))
+    if (uocr_conv_t32_eligible(ctx, dtype, d, 1) && uocr_aligned16(dy) && uocr_aligned16(dx) && (!mask.y || uocr_aligned16(mask.y)))
         return uocr_noted_conv(ctx, 1, UOCR_CONV_T32, uocr_conv_dgrad_t32(ctx, dy, w, dx, d, mask));
     if (uocr_conv_fast_eligible(ctx, dtype, d, dy, dx, w)) return uocr_conv_dgrad_fast(ctx, dtype, dy, w, dx, d, mask);
     if (uocr_conv_mfma_eligible(ctx, dtype, d, 1))
@@ -82,7 +80,7 @@ int uocr_conv2d_bwd_weight(uocr_ctx* ctx, int dtype, const void* x, const void* 
     if (uocr_conv_wgrad_h16_eligible(ctx, dtype, d) && uocr_aligned_act(x, dtype) && uocr_aligned_act(dy, dtype))
         return uocr_noted_conv(ctx, 2, UOCR_CONV_H16_WGRAD,
                                uocr_conv_wgrad_h16(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate));
-    if (uocr_conv_wgrad_t32_eligible(ctx, dtype, d) && aligned16(x) && aligned16(dy))
+    if (uocr_conv_wgrad_t32_eligible(ctx, dtype, d) && uocr_aligned16(x) && uocr_aligned16(dy))
         return uocr_noted_conv(ctx, 2, UOCR_CONV_T32_WGRAD,
                                uocr_conv_wgrad_t32(ctx, x, dy, dw, db, d, pad_value, use_bias, accumulate));
     if (uocr_conv_wgrad_s2_h16_eligible(ctx, dtype, d) && uocr_aligned_act(x, dtype) && uocr_aligned_act(dy, dtype))

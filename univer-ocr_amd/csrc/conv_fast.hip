@@ -1178,9 +1178,8 @@ int launch_wgrad_s2(uocr_ctx* ctx, int dtype, const void* x, const void* dy, voi
                     double pad_value, int use_bias, int accumulate) {
     using C = S2Cfg<CIN, COUT>;
     const int tiles_x = (d.ow + C::TW - 1) / C::TW, tiles_y = (d.oh + C::TH - 1) / C::TH;
-    int per_block = 1;                                      // ~1024 blocks: a few tiles of one column strip each
-    while (per_block < tiles_y && (size_t)tiles_x * ((tiles_y + per_block - 1) / per_block) * d.n > (size_t)uocr_budget(ctx, 1024))
-        ++per_block;
+    // ~1024 blocks: a few tiles of one column strip each
+    const int per_block = uocr_tiles_per_block(tiles_x, tiles_y, d.n, uocr_budget(ctx, 1024));
     const dim3 grid(tiles_x, (tiles_y + per_block - 1) / per_block, d.n);
     const int nblocks = (int)(grid.x * grid.y * grid.z);
     uocr_note_split(ctx, nblocks, (long long)tiles_x * tiles_y * d.n);
@@ -1192,22 +1191,13 @@ int launch_wgrad_s2(uocr_ctx* ctx, int dtype, const void* x, const void* dy, voi
                            (const TA*)dy, partial, d.h, d.w, d.oh, d.ow, (float)pad_value, per_block);
     });
     UOCR_LAUNCH_CHECK(ctx);
-    FinishDesc fd{};                                     // recorded when a deferred group is open (finish_group.h)
-    fd.kind = FIN_TAPROWS;
-    fd.partial = partial;
-    fd.nblocks = nblocks;
-    fd.ncols = fd.group_cols = 5 * C::NP;
-    fd.row_stride = (size_t)5 * C::NP;
-    fd.dw = (float*)dw, fd.db = (float*)db;
-    fd.use_bias = use_bias, fd.accumulate = accumulate;
-    fd.unscale = (float)uocr_grad_unscale(dtype);
-    fd.p[0] = C::NP, fd.p[1] = C::NW, fd.p[2] = COUT;
-    if (uocr_finish_defer(ctx, fd)) return UOCR_OK;
-    hipLaunchKernelGGL((conv_wgrad_s2_finish<CIN, COUT>), dim3(5 * C::NW + COUT), dim3(256), 0, ctx->stream,
-                       (const float*)partial, (float*)dw, (float*)db, nblocks, use_bias, accumulate,
-                       (float)uocr_grad_unscale(dtype));
-    UOCR_LAUNCH_CHECK(ctx);
-    return UOCR_OK;
+    const float unscale = (float)uocr_grad_unscale(dtype);
+    const FinishDesc fd = finish_taprows(partial, nblocks, C::NP, C::NW, COUT, (float*)dw, (float*)db, use_bias, accumulate,
+                                         unscale);
+    return uocr_finish(ctx, fd, [&] {
+        hipLaunchKernelGGL((conv_wgrad_s2_finish<CIN, COUT>), dim3(5 * C::NW + COUT), dim3(256), 0, ctx->stream,
+                           (const float*)partial, (float*)dw, (float*)db, nblocks, use_bias, accumulate, unscale);
+    });
 }
 
 template <int KH, int KW, int CIN, int COUT, int SH, int SW, int COB, int PY, int DPY, int KYR, int WCOB, int WPY, int FPX,
@@ -1289,24 +1279,14 @@ struct FastConv {
                                partial, dims(d), (float)pad, rows, nbands);
         });
         UOCR_LAUNCH_CHECK(ctx);
-        FinishDesc fd{};                                 // recorded when a deferred group is open (finish_group.h)
-        fd.kind = FIN_FAST;
-        fd.partial = partial;
-        fd.nblocks = nblocks;
-        fd.ncols = ngroups * C::NP;
-        fd.group_cols = C::NP;
-        fd.group_stride = (size_t)nblocks * C::NP;
-        fd.row_stride = C::NP;
-        fd.dw = (float*)dw, fd.db = (float*)db;
-        fd.use_bias = use_bias, fd.accumulate = accumulate;
-        fd.unscale = (float)uocr_grad_unscale(dtype);
-        fd.p[0] = C::NP, fd.p[1] = C::NW, fd.p[2] = KW, fd.p[3] = CIN, fd.p[4] = COUT, fd.p[5] = KYR, fd.p[6] = WCOB;
-        if (uocr_finish_defer(ctx, fd)) return UOCR_OK;
-        hipLaunchKernelGGL((conv_wgrad_fast_finish<KH, KW, CIN, COUT, KYR, WCOB, C::NW, C::NP>),
-                           dim3(C::NACC, ngroups), dim3(256), 0, ctx->stream, (const float*)partial, (float*)dw,
-                           (float*)db, nblocks, use_bias, accumulate, (float)uocr_grad_unscale(dtype));
-        UOCR_LAUNCH_CHECK(ctx);
-        return UOCR_OK;
+        const float unscale = (float)uocr_grad_unscale(dtype);
+        const FinishDesc fd = finish_fast(partial, nblocks, ngroups, {C::NP, C::NW, KW, CIN, COUT, KYR, WCOB}, (float*)dw,
+                                          (float*)db, use_bias, accumulate, unscale);
+        return uocr_finish(ctx, fd, [&] {
+            hipLaunchKernelGGL((conv_wgrad_fast_finish<KH, KW, CIN, COUT, KYR, WCOB, C::NW, C::NP>),
+                               dim3(C::NACC, ngroups), dim3(256), 0, ctx->stream, (const float*)partial, (float*)dw,
+                               (float*)db, nblocks, use_bias, accumulate, unscale);
+        });
     }
 };
 
@@ -1445,6 +1425,31 @@ int uocr_conv_dgrad_fast(uocr_ctx* ctx, int dtype, const void* dy, const void* w
     UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "no fast conv kernel for this shape");
 }
 
+static int launch_wgrad_t542(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw, void* db, const ConvDims& d,
+                             double pad_value, int use_bias, int accumulate) {
+    const int tiles_x = (d.w + t542::TW - 1) / t542::TW, tiles_y = (d.h + t542::TH - 1) / t542::TH;
+    // ~1024 blocks: a few tiles of one column strip each (measured at 32 x 256 x 512: 512 blocks 58 us, 1024 57, 2048 65, 4096 74)
+    const int per_block = uocr_tiles_per_block(tiles_x, tiles_y, d.n, uocr_budget(ctx, 1024));
+    const dim3 grid(tiles_x, (tiles_y + per_block - 1) / per_block, d.n);
+    const int nblocks = (int)(grid.x * grid.y * grid.z);
+    uocr_note_split(ctx, nblocks, (long long)tiles_x * tiles_y * d.n);
+    int rc = UOCR_OK;
+    float* partial = uocr_partial_buffer(ctx, (size_t)nblocks * 5 * t542::NACC * sizeof(float), &rc);
+    if (rc) return rc;
+    UOCR_DISPATCH_TA(ctx, dtype, {
+        hipLaunchKernelGGL((conv_wgrad_t542<TA>), grid, dim3(320), 0, ctx->stream, (const TA*)x, (const TA*)dy, partial,
+                           d.h, d.w, (float)pad_value, per_block);
+    });
+    UOCR_LAUNCH_CHECK(ctx);
+    const float unscale = (float)uocr_grad_unscale(dtype);
+    const FinishDesc fd = finish_taprows(partial, nblocks, t542::NACC, 40, 2, (float*)dw, (float*)db, use_bias, accumulate,
+                                         unscale);
+    return uocr_finish(ctx, fd, [&] {
+        hipLaunchKernelGGL(conv_wgrad_t542_finish, dim3(202), dim3(256), 0, ctx->stream, (const float*)partial, (float*)dw,
+                           (float*)db, nblocks, use_bias, accumulate, unscale);
+    });
+}
+
 int uocr_conv_wgrad_fast(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw, void* db,
                          const ConvDims& d, double pad_value, int use_bias, int accumulate) {
     const bool f32 = UOCR_DTYPE_BASE(dtype) == UOCR_F32;
@@ -1475,40 +1480,9 @@ int uocr_conv_wgrad_fast(uocr_ctx* ctx, int dtype, const void* x, const void* dy
             return uocr_noted_conv(ctx, 2, UOCR_CONV_WGRAD_S2_TILED,
                                    launch_wgrad_s2<1, 4>(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate));
     }
-    if (d.kh == 5 && d.kw == 5 && d.cin == 4 && d.cout == 2 && d.sh == 1 && d.sw == 1 && d.ph == 2 && d.pw == 2) {
-        const int tiles_x = (d.w + t542::TW - 1) / t542::TW, tiles_y = (d.h + t542::TH - 1) / t542::TH;
-        int per_block = 1;                                  // ~1024 blocks: a few tiles of one column strip each
-        // (measured at 32 x 256 x 512: 512 blocks 58 us, 1024 57, 2048 65, 4096 74)
-        while (per_block < tiles_y && (size_t)tiles_x * ((tiles_y + per_block - 1) / per_block) * d.n > (size_t)uocr_budget(ctx, 1024))
-            ++per_block;
-        const dim3 grid(tiles_x, (tiles_y + per_block - 1) / per_block, d.n);
-        const int nblocks = (int)(grid.x * grid.y * grid.z);
-        uocr_note_split(ctx, nblocks, (long long)tiles_x * tiles_y * d.n);
-        int rc = UOCR_OK;
-        float* partial = uocr_partial_buffer(ctx, (size_t)nblocks * 5 * t542::NACC * sizeof(float), &rc);
-        if (rc) return rc;
-        UOCR_DISPATCH_TA(ctx, dtype, {
-            hipLaunchKernelGGL((conv_wgrad_t542<TA>), grid, dim3(320), 0, ctx->stream, (const TA*)x, (const TA*)dy,
-                               partial, d.h, d.w, (float)pad_value, per_block);
-        });
-        UOCR_LAUNCH_CHECK(ctx);
-        FinishDesc fd{};                                 // recorded when a deferred group is open (finish_group.h)
-        fd.kind = FIN_TAPROWS;
-        fd.partial = partial;
-        fd.nblocks = nblocks;
-        fd.ncols = fd.group_cols = 5 * t542::NACC;
-        fd.row_stride = (size_t)5 * t542::NACC;
-        fd.dw = (float*)dw, fd.db = (float*)db;
-        fd.use_bias = use_bias, fd.accumulate = accumulate;
-        fd.unscale = (float)uocr_grad_unscale(dtype);
-        fd.p[0] = t542::NACC, fd.p[1] = 40, fd.p[2] = 2;
-        if (uocr_finish_defer(ctx, fd)) return uocr_noted_conv(ctx, 2, UOCR_CONV_WGRAD_T542, UOCR_OK);
-        hipLaunchKernelGGL(conv_wgrad_t542_finish, dim3(202), dim3(256), 0, ctx->stream, (const float*)partial,
-                           (float*)dw, (float*)db, nblocks, use_bias, accumulate, (float)uocr_grad_unscale(dtype));
-        UOCR_LAUNCH_CHECK(ctx);
-        uocr_note_conv(ctx, 2, UOCR_CONV_WGRAD_T542);
-        return UOCR_OK;
-    }
+    if (d.kh == 5 && d.kw == 5 && d.cin == 4 && d.cout == 2 && d.sh == 1 && d.sw == 1 && d.ph == 2 && d.pw == 2)
+        return uocr_noted_conv(ctx, 2, UOCR_CONV_WGRAD_T542,
+                               launch_wgrad_t542(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate));
 #define X(KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX)                   \
     if (FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::match(d)) \
         return uocr_noted_conv(ctx, 2, UOCR_CONV_TABLE_FAST,                                    \

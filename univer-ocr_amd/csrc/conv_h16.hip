@@ -375,21 +375,16 @@ int launch_h16(uocr_ctx* ctx, const void* in, const void* w, const void* bias, v
                int h_in, int w_in, int h_out, int w_out, int ph, int pw, float pad, int use_bias, int act, float alpha,
                int mask_act, float mask_alpha) {
     static int resident = 0;                             // blocks of this kernel one CU holds
-    if (resident == 0) {
-        int nb = 0;
-        UOCR_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_h16_kernel<G>, 256, 0));
-        resident = nb > 0 ? nb : 1;
-    }
     const int hp = (h_out + G::U - 1) / G::U, wp = (w_out + G::U - 1) / G::U;      // the position grid
     const int tiles_x = (wp + G::BC - 1) / G::BC, tiles_y = (hp + G::BR - 1) / G::BR;
     const long ntiles = (long)n * tiles_y * tiles_x;
-    UOCR_REQUIRE(ctx, ntiles < (1l << 31) && (long)h_in * w_in * G::C < (1l << 31));
+    UOCR_REQUIRE(ctx, (long)h_in * w_in * G::C < (1l << 31));
     // 4 x the resident blocks: when other lanes hold part of the CUs only some blocks of a launch are resident and
     // the rest start late -- with exactly one block per slot the late ones still own 1/grid of the tiles each (measured
     // in the three-lane step: 6.66 -> 6.75 k pages/s; alone the kernels do not care)
-    const long cap = uocr_budget(ctx, (long)ctx->cu_count * resident * 4);
-    const int grid = (int)(ntiles < cap ? ntiles : cap);
-    uocr_note_split(ctx, grid, ntiles);
+    int grid = 0;
+    const int rc = uocr_persistent_grid(ctx, conv_h16_kernel<G>, ntiles, 4, &resident, &grid);
+    if (rc != UOCR_OK) return rc;
     hipLaunchKernelGGL(conv_h16_kernel<G>, dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)in, (const float*)w,
                        (const float*)bias, (_Float16*)out, (const _Float16*)mask_y, h_in, w_in, h_out, w_out, ph, pw,
                        tiles_x, tiles_y, (int)ntiles, pad, use_bias, act, alpha, mask_act, mask_alpha);

@@ -307,20 +307,13 @@ __global__ __launch_bounds__(256) void wgrad_h16_finish(const float* __restrict_
     *dst = accumulate ? (float)((double)*dst + s) : (float)s;
 }
 
-// the same finish as a record of an open deferred group (finish_group.h); false: launch wgrad_h16_finish
-static bool h16_finish_deferred(uocr_ctx* ctx, const float* partial, int nv, int ndw, float* dw, float* db, int nblocks,
-                                int use_bias, int accumulate, float unscale) {
-    FinishDesc fd{};
-    fd.kind = FIN_COLS;
-    fd.partial = partial;
-    fd.nblocks = nblocks;
-    fd.ncols = fd.group_cols = nv;
-    fd.row_stride = nv;
-    fd.dw = dw, fd.db = db;
-    fd.use_bias = use_bias, fd.accumulate = accumulate;
-    fd.unscale = unscale;
-    fd.p[0] = ndw;
-    return uocr_finish_defer(ctx, fd);
+// the end of the conv launchers: recorded when a deferred group is open (finish_group.h), else wgrad_h16_finish
+static int h16_finish(uocr_ctx* ctx, const float* partial, int nv, int ndw, float* dw, float* db, int nblocks,
+                      int use_bias, int accumulate, float unscale) {
+    return uocr_finish(ctx, finish_cols(partial, nblocks, nv, ndw, dw, db, use_bias, accumulate, unscale), [&] {
+        hipLaunchKernelGGL(wgrad_h16_finish, dim3(nv), dim3(256), 0, ctx->stream, partial, nv, ndw, dw, db, nblocks,
+                           use_bias, accumulate, unscale);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -789,16 +782,6 @@ __global__ __launch_bounds__(256) void wgrad_h16_s2_kernel(const _Float16* __res
         partial[(size_t)blockIdx.x * G::NV + i] = red[0][i] + red[1][i] + red[2][i] + red[3][i];
 }
 
-template <typename K>
-int resident_blocks(uocr_ctx* ctx, K kernel, int* cache) {
-    if (*cache == 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 256, 0) != hipSuccess || nb < 1) nb = 1;
-        *cache = nb;
-    }
-    return *cache;
-}
-
 }  // namespace
 
 bool uocr_conv_wgrad_h16_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d) {
@@ -815,26 +798,17 @@ int uocr_conv_wgrad_h16(uocr_ctx* ctx, int dtype, const void* x, const void* dy,
     const int br = one ? e11::BR : e42::BR;
     const int tiles_x = (d.w + 4 + e42::BC - 1) / e42::BC, tiles_y = (d.h + br - 1) / br;   // (both: 64 columns)
     const long ntiles = (long)d.n * tiles_y * tiles_x;
-    UOCR_REQUIRE(ctx, ntiles < (1l << 31));
-    const long cap = uocr_budget(ctx, (long)ctx->cu_count * (one ? resident_blocks(ctx, wgrad_h16_e11_kernel, &cache11)
-                                                                : resident_blocks(ctx, wgrad_h16_e42_kernel, &cache42)));
-    const int grid = (int)(ntiles < cap ? ntiles : cap);
-    uocr_note_split(ctx, grid, ntiles);
-    int rc = UOCR_OK;
+    const auto kernel = one ? wgrad_h16_e11_kernel : wgrad_h16_e42_kernel;
+    int grid = 0;
+    int rc = uocr_persistent_grid(ctx, kernel, ntiles, 1, one ? &cache11 : &cache42, &grid);
+    if (rc != UOCR_OK) return rc;
     float* partial = uocr_partial_buffer(ctx, (size_t)grid * nv * sizeof(float), &rc);
     if (rc != UOCR_OK) return rc;
-    hipLaunchKernelGGL(one ? wgrad_h16_e11_kernel : wgrad_h16_e42_kernel, dim3(grid), dim3(256), 0, ctx->stream,
-                       (const _Float16*)x, (const _Float16*)dy, partial, d.h, d.w, tiles_x, tiles_y, (int)ntiles,
-                       (float)pad_value);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)x, (const _Float16*)dy, partial,
+                       d.h, d.w, tiles_x, tiles_y, (int)ntiles, (float)pad_value);
     UOCR_LAUNCH_CHECK(ctx);
-    if (h16_finish_deferred(ctx, partial, nv, one ? 25 : 200, (float*)dw, (float*)db, grid, use_bias, accumulate,
-                            (float)uocr_grad_unscale(dtype)))
-        return UOCR_OK;
-    hipLaunchKernelGGL(wgrad_h16_finish, dim3(nv), dim3(256), 0, ctx->stream, (const float*)partial, nv,
-                       one ? 25 : 200, (float*)dw, (float*)db, grid, use_bias, accumulate,
-                       (float)uocr_grad_unscale(dtype));
-    UOCR_LAUNCH_CHECK(ctx);
-    return UOCR_OK;
+    return h16_finish(ctx, partial, nv, one ? 25 : 200, (float*)dw, (float*)db, grid, use_bias, accumulate,
+                      (float)uocr_grad_unscale(dtype));
 }
 
 // partial rows as conv_up.hip's producers write them: dw and db themselves (up_phase.h: UP4_NOUT / UP1_NOUT floats)
@@ -844,10 +818,10 @@ int uocr_upconv_wgrad_h16(uocr_ctx* ctx, const void* x_low, const void* dy, floa
         static int cache1 = 0;
         const int tiles_x = (wl + up1::BC - 1) / up1::BC, tiles_y = (hl + up1::BR - 1) / up1::BR;
         const long ntiles = (long)n * tiles_y * tiles_x;
-        UOCR_REQUIRE(ctx, ntiles < (1l << 31) && (long)hl * wl * 4 < (1l << 31));
-        const long cap = uocr_budget(ctx, (long)ctx->cu_count * resident_blocks(ctx, wgrad_h16_up1_kernel, &cache1));
-        const int grid = (int)(ntiles < cap ? ntiles : cap);
-        uocr_note_split(ctx, grid, ntiles);
+        UOCR_REQUIRE(ctx, (long)hl * wl * 4 < (1l << 31));
+        int grid = 0;
+        const int rc = uocr_persistent_grid(ctx, wgrad_h16_up1_kernel, ntiles, 1, &cache1, &grid);
+        if (rc != UOCR_OK) return rc;
         UOCR_REQUIRE(ctx, (size_t)grid * UP1_NOUT <= partial_floats);
         hipLaunchKernelGGL(wgrad_h16_up1_kernel, dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)x_low,
                            (const _Float16*)dy, partial, hl, wl, tiles_x, tiles_y, (int)ntiles);
@@ -858,10 +832,10 @@ int uocr_upconv_wgrad_h16(uocr_ctx* ctx, const void* x_low, const void* dy, floa
     static int cache = 0;
     const int tiles_x = (wl + up::BC - 1) / up::BC, tiles_y = (hl + up::BR - 1) / up::BR;
     const long ntiles = (long)n * tiles_y * tiles_x;
-    UOCR_REQUIRE(ctx, ntiles < (1l << 31) && (long)hl * wl * 16 < (1l << 31));
-    const long cap = uocr_budget(ctx, (long)ctx->cu_count * resident_blocks(ctx, wgrad_h16_up_kernel, &cache));
-    const int grid = (int)(ntiles < cap ? ntiles : cap);
-    uocr_note_split(ctx, grid, ntiles);
+    UOCR_REQUIRE(ctx, (long)hl * wl * 16 < (1l << 31));
+    int grid = 0;
+    const int rc = uocr_persistent_grid(ctx, wgrad_h16_up_kernel, ntiles, 1, &cache, &grid);
+    if (rc != UOCR_OK) return rc;
     UOCR_REQUIRE(ctx, (size_t)grid * UP4_NOUT <= partial_floats);
     hipLaunchKernelGGL(wgrad_h16_up_kernel, dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)x_low,
                        (const _Float16*)dy, partial, hl, wl, tiles_x, tiles_y, (int)ntiles);
@@ -886,23 +860,16 @@ int launch_s2(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw,
     static int cache = 0;
     const int tiles_x = (d.ow + 2 + G::BC - 1) / G::BC, tiles_y = (d.oh + G::BR - 1) / G::BR;   // Q runs over [-1, ow]
     const long ntiles = (long)d.n * tiles_y * tiles_x;
-    UOCR_REQUIRE(ctx, ntiles < (1l << 31));
-    const long cap = uocr_budget(ctx, (long)ctx->cu_count * resident_blocks(ctx, wgrad_h16_s2_kernel<CI, CO>, &cache));
-    const int grid = (int)(ntiles < cap ? ntiles : cap);
-    uocr_note_split(ctx, grid, ntiles);
-    int rc = UOCR_OK;
+    int grid = 0;
+    int rc = uocr_persistent_grid(ctx, wgrad_h16_s2_kernel<CI, CO>, ntiles, 1, &cache, &grid);
+    if (rc != UOCR_OK) return rc;
     float* partial = uocr_partial_buffer(ctx, (size_t)grid * G::NV * sizeof(float), &rc);
     if (rc != UOCR_OK) return rc;
     hipLaunchKernelGGL((wgrad_h16_s2_kernel<CI, CO>), dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)x,
                        (const _Float16*)dy, partial, d.h, d.w, d.oh, d.ow, tiles_x, tiles_y, (int)ntiles, (float)pad_value);
     UOCR_LAUNCH_CHECK(ctx);
-    if (h16_finish_deferred(ctx, partial, G::NV, 25 * CI * CO, (float*)dw, (float*)db, grid, use_bias, accumulate,
-                            (float)uocr_grad_unscale(dtype)))
-        return UOCR_OK;
-    hipLaunchKernelGGL(wgrad_h16_finish, dim3(G::NV), dim3(256), 0, ctx->stream, (const float*)partial, G::NV,
-                       25 * CI * CO, (float*)dw, (float*)db, grid, use_bias, accumulate, (float)uocr_grad_unscale(dtype));
-    UOCR_LAUNCH_CHECK(ctx);
-    return UOCR_OK;
+    return h16_finish(ctx, partial, G::NV, 25 * CI * CO, (float*)dw, (float*)db, grid, use_bias, accumulate,
+                      (float)uocr_grad_unscale(dtype));
 }
 }  // namespace
 

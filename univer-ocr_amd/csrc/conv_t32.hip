@@ -349,21 +349,15 @@ int launch_t32_kinds(uocr_ctx* ctx, const void* in, const void* w, const void* b
                      int h_in, int w_in, int h_out, int w_out, int ph, int pw, float pad, int use_bias, int act,
                      float alpha, int mask_act, float mask_alpha) {
     static int resident = 0;                             // blocks of this kernel one CU holds
-    if (resident == 0) {
-        int nb = 0;
-        UOCR_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_t32_kernel<G, ACT, MASK, BIAS>, 256, 0));
-        resident = nb > 0 ? nb : 1;
-    }
     const int hp = (h_out + G::U - 1) / G::U, wp = (w_out + G::U - 1) / G::U;      // the position grid
     const int tiles_x = (wp + G::BC - 1) / G::BC, tiles_y = (hp + G::BR - 1) / G::BR;
     const long ntiles = (long)n * tiles_y * tiles_x;
-    UOCR_REQUIRE(ctx, ntiles < (1l << 31) && (long)h_in * w_in * G::C < (1l << 31) &&
-                          (long)(G::BR * G::U + 1) * w_out * G::COUT < (1l << 29));
+    UOCR_REQUIRE(ctx, (long)h_in * w_in * G::C < (1l << 31) && (long)(G::BR * G::U + 1) * w_out * G::COUT < (1l << 29));
     // one block per resident slot: at 32 x 256 x 512 a block walks two or three tiles, with its prologue paid once and
     // the next tile's loads under the chains of the current one
-    const long cap = uocr_budget(ctx, (long)ctx->cu_count * resident);
-    const int grid = (int)(ntiles < cap ? ntiles : cap);
-    uocr_note_split(ctx, grid, ntiles);
+    int grid = 0;
+    const int rc = uocr_persistent_grid(ctx, conv_t32_kernel<G, ACT, MASK, BIAS>, ntiles, 1, &resident, &grid);
+    if (rc != UOCR_OK) return rc;
     hipLaunchKernelGGL((conv_t32_kernel<G, ACT, MASK, BIAS>), dim3(grid), dim3(256), 0, ctx->stream, (const float*)in,
                        (const float*)w, (const float*)bias, (float*)out, (const float*)mask_y, h_in, w_in, h_out, w_out, ph,
                        pw, tiles_x, tiles_y, (int)ntiles, pad, use_bias, act, alpha, mask_act, mask_alpha);
@@ -399,7 +393,6 @@ inline bool half5x5(const ConvDims& d) {                 // the encoder convs: 5
     return d.kh == 5 && d.kw == 5 && d.sh == 2 && d.sw == 2 && d.ph == 2 && d.pw == 2 && d.oh == (d.h + 1) / 2 &&
            d.ow == (d.w + 1) / 2;
 }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 

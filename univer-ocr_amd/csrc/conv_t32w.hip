@@ -305,16 +305,6 @@ __global__ __launch_bounds__(256) void wgrad_t32_e_kernel(const float* __restric
         partial[(size_t)blockIdx.x * G::NV + i] = red[0][i] + red[1][i] + red[2][i] + red[3][i];
 }
 
-template <typename K>
-int resident_blocks(K kernel, int* cache) {
-    if (*cache == 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 256, 0) != hipSuccess || nb < 1) nb = 1;
-        *cache = nb;
-    }
-    return *cache;
-}
-
 template <int CI, int CO>
 int launch_s2(uocr_ctx* ctx, const void* x, const void* dy, void* dw, void* db, const ConvDims& d, double pad_value,
               int use_bias, int accumulate) {
@@ -322,11 +312,10 @@ int launch_s2(uocr_ctx* ctx, const void* x, const void* dy, void* dw, void* db, 
     static int cache = 0;
     const int tiles_x = (d.ow + 2 + G::BC - 1) / G::BC, tiles_y = (d.oh + G::BR - 1) / G::BR;   // Q runs over [-1, ow]
     const long ntiles = (long)d.n * tiles_y * tiles_x;
-    UOCR_REQUIRE(ctx, ntiles < (1l << 31));
-    const long cap = uocr_budget(ctx, (long)ctx->cu_count * resident_blocks(wgrad_t32_s2_kernel<CI, CO>, &cache));
-    const int grid = (int)(ntiles < cap ? ntiles : cap);
-    uocr_note_split(ctx, grid, ntiles);
-    int rc = uocr_need_workspace(ctx, (size_t)grid * G::NV * sizeof(float));
+    int grid = 0;
+    int rc = uocr_persistent_grid(ctx, wgrad_t32_s2_kernel<CI, CO>, ntiles, 1, &cache, &grid);
+    if (rc != UOCR_OK) return rc;
+    rc = uocr_need_workspace(ctx, (size_t)grid * G::NV * sizeof(float));
     if (rc != UOCR_OK) return rc;
     float* partial = (float*)ctx->workspace;
     hipLaunchKernelGGL((wgrad_t32_s2_kernel<CI, CO>), dim3(grid), dim3(256), 0, ctx->stream, (const float*)x,
@@ -345,11 +334,10 @@ int launch_e(uocr_ctx* ctx, const void* x, const void* dy, void* dw, void* db, c
     static int cache = 0;
     const int tiles_x = (d.w + 4 + G::BC - 1) / G::BC, tiles_y = (d.h + G::BR - 1) / G::BR;     // col runs over [-4, w)
     const long ntiles = (long)d.n * tiles_y * tiles_x;
-    UOCR_REQUIRE(ctx, ntiles < (1l << 31));
-    const long cap = uocr_budget(ctx, (long)ctx->cu_count * resident_blocks(wgrad_t32_e_kernel<CI, CO>, &cache));
-    const int grid = (int)(ntiles < cap ? ntiles : cap);
-    uocr_note_split(ctx, grid, ntiles);
-    int rc = uocr_need_workspace(ctx, (size_t)grid * G::NV * sizeof(float));
+    int grid = 0;
+    int rc = uocr_persistent_grid(ctx, wgrad_t32_e_kernel<CI, CO>, ntiles, 1, &cache, &grid);
+    if (rc != UOCR_OK) return rc;
+    rc = uocr_need_workspace(ctx, (size_t)grid * G::NV * sizeof(float));
     if (rc != UOCR_OK) return rc;
     float* partial = (float*)ctx->workspace;
     hipLaunchKernelGGL((wgrad_t32_e_kernel<CI, CO>), dim3(grid), dim3(256), 0, ctx->stream, (const float*)x,

@@ -587,8 +587,8 @@ extern "C" int uocr_upconv2x_bwd_data(uocr_ctx* ctx, int dtype, const void* dy, 
     if (uocr_upconv_h16_eligible(ctx, dtype, cin, cout) && uocr_aligned_act(dy, dtype) &&
         uocr_aligned_act(dx_low, dtype) && (act == UOCR_ACT_NONE || uocr_aligned_act(x_act, dtype)))
         return uocr_upconv_dgrad_h16(ctx, dy, w, dx_low, n, hl, wl, act == UOCR_ACT_NONE ? nullptr : x_act, act, act_alpha);
-    if (uocr_upconv_t32_eligible(ctx, dtype, cin, cout) && (reinterpret_cast<uintptr_t>(dy) & 15u) == 0 &&
-        (reinterpret_cast<uintptr_t>(dx_low) & 15u) == 0 && (act == UOCR_ACT_NONE || (reinterpret_cast<uintptr_t>(x_act) & 15u) == 0))
+    if (uocr_upconv_t32_eligible(ctx, dtype, cin, cout) && uocr_aligned16(dy) && uocr_aligned16(dx_low) &&
+        (act == UOCR_ACT_NONE || uocr_aligned16(x_act)))
         return uocr_upconv_dgrad_t32(ctx, dy, w, dx_low, n, hl, wl, cin, act == UOCR_ACT_NONE ? nullptr : x_act, act, act_alpha);
     const float* weff = (const float*)weff_in;             // from this layer's forward call with the same w, or null
     if (cin != 1 && !weff) {
@@ -625,21 +625,11 @@ extern "C" int uocr_upconv2x_bwd_weight(uocr_ctx* ctx, int dtype, const void* x_
     // the block partials are rows of dw and db themselves (up_phase.h); their float64 column sums: recorded when a deferred
     // group is open (finish_group.h), else one coalesced launch
     auto finish = [&](const float* partial, int nblocks) -> int {
-        FinishDesc fd{};
-        fd.kind = FIN_COLS;
-        fd.partial = partial;
-        fd.nblocks = nblocks;
-        fd.ncols = fd.group_cols = ncols;
-        fd.row_stride = ncols;
-        fd.dw = (float*)dw, fd.db = (float*)db;
-        fd.use_bias = use_bias, fd.accumulate = accumulate;
-        fd.unscale = unscale;
-        fd.p[0] = ndw;
-        if (uocr_finish_defer(ctx, fd)) return UOCR_OK;
-        hipLaunchKernelGGL(colsum_finish_kernel, dim3((ncols + 7) / 8), dim3(256), 0, ctx->stream, partial, nblocks, ncols,
-                           ndw, (float*)dw, (float*)db, use_bias, accumulate, unscale);
-        UOCR_LAUNCH_CHECK(ctx);
-        return UOCR_OK;
+        const FinishDesc fd = finish_cols(partial, nblocks, ncols, ndw, (float*)dw, (float*)db, use_bias, accumulate, unscale);
+        return uocr_finish(ctx, fd, [&] {
+            hipLaunchKernelGGL(colsum_finish_kernel, dim3((ncols + 7) / 8), dim3(256), 0, ctx->stream, partial, nblocks,
+                               ncols, ndw, (float*)dw, (float*)db, use_bias, accumulate, unscale);
+        });
     };
     if (UOCR_DTYPE_BASE(dtype) == UOCR_F16 && ctx->opt_fast && ctx->opt_h16 && uocr_aligned_act(x_low, dtype) &&
         uocr_aligned_act(dy, dtype)) {

@@ -38,3 +38,58 @@ float* uocr_partial_buffer(uocr_ctx* ctx, size_t bytes, int* rc);
 // true: recorded -- the caller returns without launching its finish kernel
 bool uocr_finish_defer(uocr_ctx* ctx, const FinishDesc& d);
 void uocr_finish_defer_free(uocr_ctx* ctx);
+
+// ---- the descriptors as their producers fill them: one [nblocks][ncols] matrix unless a builder says otherwise
+inline FinishDesc finish_desc(int kind, const float* partial, int nblocks, int ncols, float* dw, float* db, int use_bias,
+                              int accumulate, float unscale) {
+    FinishDesc fd{};
+    fd.kind = kind;
+    fd.partial = partial;
+    fd.nblocks = nblocks;
+    fd.ncols = fd.group_cols = ncols;
+    fd.row_stride = (size_t)ncols;
+    fd.dw = dw, fd.db = db;
+    fd.use_bias = use_bias, fd.accumulate = accumulate;
+    fd.unscale = unscale;
+    return fd;
+}
+inline FinishDesc finish_cols(const float* partial, int nblocks, int ncols, int ndw, float* dw, float* db, int use_bias,
+                              int accumulate, float unscale) {
+    FinishDesc fd = finish_desc(FIN_COLS, partial, nblocks, ncols, dw, db, use_bias, accumulate, unscale);
+    fd.p[0] = ndw;
+    return fd;
+}
+// five tap rows of NP columns: NW of dw, then NB of db
+inline FinishDesc finish_taprows(const float* partial, int nblocks, int NP, int NW, int NB, float* dw, float* db,
+                                 int use_bias, int accumulate, float unscale) {
+    FinishDesc fd = finish_desc(FIN_TAPROWS, partial, nblocks, 5 * NP, dw, db, use_bias, accumulate, unscale);
+    fd.p[0] = NP, fd.p[1] = NW, fd.p[2] = NB;
+    return fd;
+}
+// ngroups matrices [nblocks][NP] one after the other; p: NP, NW, KW, CIN, COUT, KYR, COB
+inline FinishDesc finish_fast(const float* partial, int nblocks, int ngroups, const int (&p)[7], float* dw, float* db,
+                              int use_bias, int accumulate, float unscale) {
+    FinishDesc fd = finish_desc(FIN_FAST, partial, nblocks, ngroups * p[0], dw, db, use_bias, accumulate, unscale);
+    fd.group_cols = p[0];
+    fd.group_stride = (size_t)nblocks * p[0];
+    fd.row_stride = (size_t)p[0];
+    for (int i = 0; i < 7; ++i) fd.p[i] = p[i];
+    return fd;
+}
+inline FinishDesc finish_pair(const float* partial, int nblocks, int ncols, float* dw1, float* db1, float* dw2, float* db2,
+                              int use_b1, int use_b2, int accumulate, float unscale) {
+    FinishDesc fd = finish_desc(FIN_PAIR, partial, nblocks, ncols, dw1, db1, use_b1, accumulate, unscale);
+    fd.dw2 = dw2, fd.db2 = db2;
+    fd.use_bias2 = use_b2;
+    return fd;
+}
+
+// the end of a weight-gradient launcher: the finish is recorded when a deferred group is open and takes it, else
+// launch_own() launches the producer's own finish kernel
+template <class F>
+int uocr_finish(uocr_ctx* ctx, const FinishDesc& fd, F&& launch_own) {
+    if (uocr_finish_defer(ctx, fd)) return UOCR_OK;
+    launch_own();
+    UOCR_LAUNCH_CHECK(ctx);
+    return UOCR_OK;
+}

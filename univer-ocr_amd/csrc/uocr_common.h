@@ -154,6 +154,40 @@ static inline void uocr_note_split(uocr_ctx* ctx, long long blocks, long long it
     ctx->split_items = items;
 }
 
+// blocks of `kernel` (`threads` threads, no dynamic LDS) that one CU holds, asked once per `cache` (the caller's static
+// int, 0 = not asked yet).  A failed query is an error, never "one block": a persistent kernel sized that way would
+// quietly run several times slower.
+template <typename K>
+static inline int uocr_resident_blocks(uocr_ctx* ctx, K kernel, int threads, int* cache, int* out) {
+    if (*cache == 0) {
+        int nb = 0;
+        UOCR_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, 0));
+        *cache = nb > 0 ? nb : 1;
+    }
+    *out = *cache;
+    return UOCR_OK;
+}
+// grid of a persistent 256-thread kernel whose blocks walk t = blockIdx.x, += gridDim.x over ntiles tiles: one block per
+// tile up to the budgeted cu_count * resident blocks * slots_per_resident; reports the split
+template <typename K>
+static inline int uocr_persistent_grid(uocr_ctx* ctx, K kernel, long ntiles, int slots_per_resident, int* cache,
+                                       int* grid) {
+    UOCR_REQUIRE(ctx, ntiles < (1l << 31));
+    int resident = 0;
+    const int rc = uocr_resident_blocks(ctx, kernel, 256, cache, &resident);
+    if (rc != UOCR_OK) return rc;
+    const long cap = uocr_budget(ctx, (long)ctx->cu_count * resident * slots_per_resident);
+    *grid = (int)(ntiles < cap ? ntiles : cap);
+    uocr_note_split(ctx, *grid, ntiles);
+    return UOCR_OK;
+}
+// tiles of one column strip per block, the fewest with which tiles_x * ceil(tiles_y / per_block) * n blocks fit the budget
+static inline int uocr_tiles_per_block(int tiles_x, int tiles_y, int n, long budget) {
+    int per_block = 1;
+    while (per_block < tiles_y && (size_t)tiles_x * ((tiles_y + per_block - 1) / per_block) * n > (size_t)budget) ++per_block;
+    return per_block;
+}
+
 // what a pair launch chose (uocr_ctx_last_pair; kernel 1-5 as in univer_hip.h), noted once the launch was accepted
 static inline void uocr_note_pair(uocr_ctx* ctx, int kernel, int g, int mode, int pf, int nw, int blocks_x, int bands,
                                   int band_h) {
@@ -308,6 +342,7 @@ __device__ __forceinline__ void st4(_Float16* p, float4 v) {
 static inline bool uocr_aligned_act(const void* p, int dtype) {
     return (reinterpret_cast<uintptr_t>(p) & (UOCR_DTYPE_BASE(dtype) == UOCR_F16 ? 7u : 15u)) == 0;
 }
+static inline bool uocr_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // d act(x) / dx expressed through the activation OUTPUT y (leaky: alpha > 0 so sign(y) == sign(x))
 template <typename T>
