@@ -451,6 +451,48 @@ int uocr_line_crop(uocr_ctx* ctx, int dtype, int n_entries, const void* const* s
  * call) -- tests size their inputs from it */
 int uocr_ctx_last_line_crop(uocr_ctx* ctx, int* elements_per_block, int* store_bytes, int* entries_per_launch, int* launches);
 
+/* ---- paragraph rotation (interpreter/interpreter.py:188-231, :319-347: the rotation search of ParagraphCrop) ----
+ * ndimage.rotate(.., angle, axes=(2, 1), reshape=True) of one paragraph, evaluated per output pixel.  The HOST computes
+ * what scipy computes in Python -- the matrix M = {c, s, -s, c}, the shape of the rotated plane and the offset
+ * (in_shape - 1) / 2 - M @ ((out_shape - 1) / 2) -- and passes them; the device never evaluates a cosine.  Output pixel
+ * (oy, ox) has the source coordinate cy = offset[0] + oy * M[0] + ox * M[1], cx = offset[1] + oy * M[2] + ox * M[3] in
+ * float64, every product and sum rounded on its own in this order; outside [0, ch - 1] x [0, cw - 1] (inclusive) it is 0.
+ * Order 0 reads (floor(cy + 0.5), floor(cx + 0.5)); order 1 is bilinear over floor(c), floor(c) + 1 without prefilter,
+ * and the neighbour at index n (reachable only with weight 0) is not read.
+ *
+ * Probe i of the extent call: the half-open extent {y0, y1, x0, x1} (find_objects) of the set pixels of the order-0
+ * rotation of labels[box] == label_id[i], {0, 0, 0, 0} when none is set; no rotated array is written.  labels: int32
+ * (n, h, w) as written by the labelling call above, image `image_index` of it.  HOST arrays of n_probes entries:
+ * label_id, box (4 ints per probe: y0, x0, ch, cw), matrix (4 doubles), offset (2 doubles), out_shape (2 ints: the
+ * rotated plane).  extent: DEVICE int32 (n_probes, 4), every element written.
+ * UOCR_ERR_ARG for null pointers, n, h, w < 1, image_index outside [0, n), label_id < 1, a box that is empty or not
+ * inside the image, a non-positive out_shape, a matrix or offset that is not finite and n_probes < 0; nothing is written
+ * on any error; n_probes = 0 is UOCR_OK and launches nothing.  One zero fill, then two kernels per 28 probes; vector
+ * integer atomics only: bit-identical run to run.  No workspace.  Asynchronous and capturable. */
+int uocr_rotated_extent(uocr_ctx* ctx, const int* labels, int n, int h, int w, int image_index, int n_probes,
+                        const int* label_id, const int* box, const double* matrix, const double* offset,
+                        const int* out_shape, int* extent);
+/* Entry i: the order-1 rotation of (image * (labels == label_id))[box], cut to the region {ry0, rx0, rh, rw} of the
+ * rotated plane (:340-346) and placed in out[i]: (1, out_h, out_w, c) at row (out_h - rh) / 2, column (out_w - rw) / 2 with
+ * zeros around it -- make_divisible_by's frame in the same pass, as the masked crop above does it.  EVERY element of out
+ * is written; nothing outside the box is read; a masked-out neighbour contributes 0.  Coordinates, weights and the
+ * four-term sum (value * wy * wx, row-major) are float64 for every dtype, the result is rounded once to `dtype`.
+ * image[i]: (n, h, w, c) in `dtype`, labels[i]: int32 (n, h, w).  HOST arrays of n_entries entries: image, labels, dims
+ * (4 ints per entry: n, h, w, c), image_index, label_id, box (4: y0, x0, ch, cw), matrix (4 doubles), offset (2 doubles),
+ * plane (2 ints: the rotated plane the region lies in), region (4), out, out_shape (2: out_h, out_w).
+ * UOCR_ERR_ARG for null pointers, pointers off their element's alignment, dims < 1, image_index outside [0, n),
+ * label_id < 1, a box that is empty or not inside the image, a region that is empty or not inside the plane, an output
+ * smaller than the region, a matrix or offset that is not finite and n_entries < 0; UOCR_ERR_DTYPE for an unknown dtype;
+ * nothing is written on any error; n_entries = 0 is UOCR_OK and launches nothing.  One launch per 28 entries, no
+ * workspace, no atomics.  Asynchronous and capturable. */
+int uocr_rotate_crop(uocr_ctx* ctx, int dtype, int n_entries, const void* const* image, const int* const* labels,
+                     const int* dims, const int* image_index, const int* label_id, const int* box, const double* matrix,
+                     const double* offset, const int* plane, const int* region, void* const* out, const int* out_shape);
+/* sizes the last extent or rotated-crop call on this ctx used: output rows per block of a probe, output pixels per
+ * block of an entry, probes / entries per launch, kernels launched (all 0 before the first call) -- tests size their
+ * inputs from it */
+int uocr_ctx_last_rotate(uocr_ctx* ctx, int* rows_per_band, int* pixels_per_block, int* entries_per_launch, int* launches);
+
 /* ---- data parallel over the GPUs of one node: RCCL over xGMI ------------------------------------
  * The reference has no multi-GPU path; BASELINE.json adds one to the step loop my_model/trainer.py:213-233
  * -> nn/model_system.py:104-118 -> nn/models.py:250-254: between compute_loss_and_gradients and update_grads

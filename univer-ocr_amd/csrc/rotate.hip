@@ -1,0 +1,303 @@
+// Paragraph rotation: the device form of the rotation search and the rotated crops of the reference's ParagraphCrop stage
+// (interpreter/interpreter.py:188-231 rotate_array / FindObjectHeightInRotated._func, :319-347
+// CropAndRotateSingleParagraph._func).  Both kernels evaluate ndimage.rotate(.., axes=(2, 1), reshape=True,
+// mode='constant', cval=0) per OUTPUT pixel; the matrix, the offset and the shape of the rotated plane come from the host,
+// which computes them as scipy does in Python (nn/ops.py: rotation_geometry) -- the device never evaluates a cosine:
+//   coordinate  cy = offset[0] + oy * M[0][0] + ox * M[0][1], cx = offset[1] + oy * M[1][0] + ox * M[1][1] in float64,
+//               every product and every sum rounded on its own, in this order (no fused multiply-add)
+//   bounds      cy outside [0, ih - 1] or cx outside [0, iw - 1] (both inclusive): the pixel is 0 at either order
+//   order 0     reads (floor(cy + 0.5), floor(cx + 0.5))
+//   order 1     bilinear over floor(c) and floor(c) + 1, weights 1 - t and 1 - (1 - t) with t = c - floor(c), no
+//               prefilter; the four terms (value * wy) * wx are added row-major; the neighbour at index n is reachable only
+//               at c == n - 1, where its weight is 0, and is not read
+// rotated_extent   a PROBE asks for the half-open extent (find_objects, :230 / :341) of the set pixels of the order-0
+//                  rotation of labels[box] == id.  No rotated array is written: a block takes RT_BAND output rows of one
+//                  probe, a wave 64 consecutive pixels of a row at a time; it ballots, keeps its row and column range in
+//                  registers, and one lane folds them into the probe's four ints with vector atomic max (the lower ends
+//                  are stored as size - index, so that one zero fill initialises all four).  A second, tiny kernel turns
+//                  the four into y0, y1, x0, x1.  The gathers are scattered, but a box of labels sits in L2: the kernel is
+//                  bound by launch and synchronisation latency, not by bandwidth.
+// rotate_crop      an ENTRY is one (array, paragraph) pair: the order-1 rotation of (image * (labels == id))[box], cut to
+//                  a region of the rotated plane and centred in make_divisible_by's zero frame, one thread per output
+//                  pixel looping over the channels (NHWC stores of neighbouring threads are contiguous).  Coordinates,
+//                  weights and the sum are float64 for every dtype; the result is rounded once.
+// All probes / entries of a call travel together, RT_ENTRIES per launch, in a by-value kernel argument (no device
+// allocation, no host synchronisation: asynchronous and capturable).  Integer atomics only: bit-identical run to run.
+// hipcc-flags: -ffp-contract=off
+#include "uocr_common.h"
+
+namespace {
+
+constexpr int RT_NT = 256;          // threads per block: 4 waves; rotate_crop: output pixels per block
+constexpr int RT_BAND = 8;          // rotated_extent: output rows per block
+constexpr int RT_ENTRIES = 28;      // probes / entries per launch (the descriptor is a kernel argument: 4 KB at most)
+
+struct RTProbe {
+    const int* lab;                 // label of the box's first pixel
+    double m[4], off[2];
+    int pitch, id, ch, cw;          // row pitch of the labels, label id, the box: the input plane of the rotation
+    int out_h, out_w;               // the rotated plane
+};
+struct RTBatch {
+    RTProbe probe[RT_ENTRIES];
+    int block_first[RT_ENTRIES + 1];   // first block of probe i in the grid
+    int n;
+    int* extent;                    // four ints per probe of this launch
+};
+struct RCEntry {
+    const void* src;                // element (y0, x0, 0) of the image: the box's first element
+    const int* lab;
+    void* out;
+    double m[4], off[2];
+    int pitch, c, id, ch, cw;
+    int ry0, rx0, rh, rw;           // the region of the rotated plane
+    int py, px, out_h, out_w;       // where the region sits in the output, the output
+};
+struct RCBatch {
+    RCEntry entry[RT_ENTRIES];
+    int block_first[RT_ENTRIES + 1];
+    int n;
+};
+static_assert(sizeof(RTBatch) <= 4096 && sizeof(RCBatch) <= 4096, "the descriptor travels as a kernel argument");
+
+// the probe / entry whose blocks [first[i], first[i + 1]) contain block b (block-uniform; those without blocks are passed over)
+__device__ __forceinline__ int rt_entry_of(const int* first, int n, int b) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first[mid] <= b) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// (offset + oy * m0) + ox * m1, each operation rounded on its own
+__device__ __forceinline__ double rt_coord(double off, double m0, double m1, int oy, int ox) {
+    return __dadd_rn(__dadd_rn(off, __dmul_rn((double)oy, m0)), __dmul_rn((double)ox, m1));
+}
+
+// scipy's constant mode: inside means 0 <= c <= n - 1 (false for a NaN)
+__device__ __forceinline__ bool rt_inside(double c, int n) { return c >= 0.0 && c <= (double)(n - 1); }
+
+__global__ __launch_bounds__(RT_NT) void rotated_extent(const RTBatch b) {
+    const int i = rt_entry_of(b.block_first, b.n, blockIdx.x);
+    const RTProbe& p = b.probe[i];
+    const int row0 = (blockIdx.x - b.block_first[i]) * RT_BAND;
+    const int rows = p.out_h - row0 < RT_BAND ? p.out_h - row0 : RT_BAND;
+    const int segs = (p.out_w + 63) / 64;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int y_lo = INT32_MAX, y_hi = -1, x_lo = INT32_MAX, x_hi = -1;      // (wave-uniform)
+    for (int item = wave; item < rows * segs; item += RT_NT / 64) {
+        const int oy = row0 + item / segs, seg0 = (item % segs) * 64, ox = seg0 + lane;
+        bool set = false;
+        if (ox < p.out_w) {
+            const double cy = rt_coord(p.off[0], p.m[0], p.m[1], oy, ox), cx = rt_coord(p.off[1], p.m[2], p.m[3], oy, ox);
+            if (rt_inside(cy, p.ch) && rt_inside(cx, p.cw)) {
+                int sy = (int)__dadd_rn(cy, 0.5), sx = (int)__dadd_rn(cx, 0.5);   // (>= 0: the conversion is the floor)
+                sy = sy < p.ch ? sy : p.ch - 1, sx = sx < p.cw ? sx : p.cw - 1;   // (never taken: n - 1 + 0.5 floors to n - 1)
+                set = p.lab[(size_t)sy * p.pitch + sx] == p.id;
+            }
+        }
+        const unsigned long long mask = __ballot(set);
+        if (mask) {
+            const int first = seg0 + __ffsll((long long)mask) - 1, last = seg0 + 63 - __clzll((long long)mask);
+            y_lo = oy < y_lo ? oy : y_lo, y_hi = oy > y_hi ? oy : y_hi;
+            x_lo = first < x_lo ? first : x_lo, x_hi = last > x_hi ? last : x_hi;
+        }
+    }
+    if (lane == 0 && y_hi >= 0) {
+        int* e = b.extent + 4 * i;                                     // zero = nothing set; lower ends as size - index
+        atomicMax(e + 0, p.out_h - y_lo);
+        atomicMax(e + 1, y_hi + 1);
+        atomicMax(e + 2, p.out_w - x_lo);
+        atomicMax(e + 3, x_hi + 1);
+    }
+}
+
+__global__ void rotated_extent_finish(const RTBatch b) {
+    const int i = threadIdx.x;
+    if (i >= b.n) return;
+    int* e = b.extent + 4 * i;
+    if (e[1] > 0) e[0] = b.probe[i].out_h - e[0], e[2] = b.probe[i].out_w - e[2];    // (else all four are 0 already)
+}
+
+template <typename T>
+__global__ __launch_bounds__(RT_NT) void rotate_crop(const RCBatch b) {
+    const int i = rt_entry_of(b.block_first, b.n, blockIdx.x);
+    const RCEntry& e = b.entry[i];
+    const size_t o = (size_t)(blockIdx.x - b.block_first[i]) * RT_NT + threadIdx.x;
+    if (o >= (size_t)e.out_h * e.out_w) return;
+    const int oy = (int)(o / e.out_w), ox = (int)(o % e.out_w);
+    const int c = e.c;
+    T* out = (T*)e.out + o * c;
+    const int ry = oy - e.py, rx = ox - e.px;
+    bool inside = ry >= 0 && ry < e.rh && rx >= 0 && rx < e.rw;
+    double cy = 0.0, cx = 0.0;
+    if (inside) {
+        cy = rt_coord(e.off[0], e.m[0], e.m[1], e.ry0 + ry, e.rx0 + rx);
+        cx = rt_coord(e.off[1], e.m[2], e.m[3], e.ry0 + ry, e.rx0 + rx);
+        inside = rt_inside(cy, e.ch) && rt_inside(cx, e.cw);
+    }
+    if (!inside) {
+        for (int k = 0; k < c; ++k) out[k] = T(0.0f);
+        return;
+    }
+    const double fy = floor(cy), fx = floor(cx);
+    const int iy = (int)fy, ix = (int)fx;
+    double wy[2], wx[2];
+    wy[0] = 1.0 - (cy - fy), wy[1] = 1.0 - wy[0];
+    wx[0] = 1.0 - (cx - fx), wx[1] = 1.0 - wx[0];
+    // the four neighbours, row-major: read only inside the box and where the label is the paragraph's
+    bool take[4];
+    size_t at[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int y = iy + (j >> 1), x = ix + (j & 1);
+        take[j] = y < e.ch && x < e.cw;
+        at[j] = take[j] ? (size_t)y * e.pitch + x : 0;
+        take[j] = take[j] && e.lab[at[j]] == e.id;
+    }
+    const T* src = (const T*)e.src;
+    for (int k = 0; k < c; ++k) {
+        double t = 0.0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (take[j]) t += ((double)src[at[j] * c + k] * wy[j >> 1]) * wx[j & 1];
+        out[k] = (T)t;
+    }
+}
+
+inline bool rt_finite(const double* v, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!(v[i] - v[i] == 0.0)) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int uocr_rotated_extent(uocr_ctx* ctx, const int* labels, int n, int h, int w, int image_index, int n_probes,
+                        const int* label_id, const int* box, const double* matrix, const double* offset,
+                        const int* out_shape, int* extent) {
+    UOCR_CHECK_CTX(ctx);
+    UOCR_REQUIRE(ctx, n_probes >= 0);
+    if (n_probes == 0) return UOCR_OK;                             // nothing to do, whatever else was passed
+    UOCR_REQUIRE(ctx, labels && label_id && box && matrix && offset && out_shape && extent);
+    UOCR_REQUIRE(ctx, n >= 1 && h >= 1 && w >= 1 && image_index >= 0 && image_index < n);
+    UOCR_REQUIRE(ctx, reinterpret_cast<uintptr_t>(extent) % sizeof(int) == 0);
+    if ((long long)h * w > INT32_MAX) UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "image of %d x %d pixels: linear indices must fit int32", h, w);
+    // everything is checked before the first launch: an error leaves the extents as they were
+    for (int first = 0; first < n_probes; first += RT_ENTRIES) {
+        long long blocks = 0;
+        for (int i = first; i < n_probes && i < first + RT_ENTRIES; ++i) {
+            const int *bx = box + 4 * i, *os = out_shape + 2 * i;
+            UOCR_REQUIRE(ctx, label_id[i] >= 1);
+            UOCR_REQUIRE(ctx, bx[0] >= 0 && bx[1] >= 0 && bx[2] >= 1 && bx[3] >= 1 && bx[2] <= h - bx[0] && bx[3] <= w - bx[1]);
+            UOCR_REQUIRE(ctx, os[0] >= 1 && os[1] >= 1);
+            UOCR_REQUIRE(ctx, rt_finite(matrix + 4 * i, 4) && rt_finite(offset + 2 * i, 2));
+            blocks += (os[0] + RT_BAND - 1) / RT_BAND;
+        }
+        if (blocks > INT32_MAX) UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "probes %d..: too many blocks for one grid", first);
+    }
+    UOCR_HIP(ctx, hipMemsetAsync(extent, 0, (size_t)n_probes * 4 * sizeof(int), ctx->stream));
+    const int* lab = labels + (size_t)image_index * h * w;
+    int launches = 0;
+    for (int first = 0; first < n_probes; first += RT_ENTRIES) {
+        RTBatch b;
+        memset(&b, 0, sizeof(b));
+        b.n = n_probes - first < RT_ENTRIES ? n_probes - first : RT_ENTRIES;
+        b.extent = extent + 4 * (size_t)first;
+        for (int i = 0; i < b.n; ++i) {
+            const int s = first + i;
+            RTProbe& p = b.probe[i];
+            p.lab = lab + (size_t)box[4 * s] * w + box[4 * s + 1];
+            memcpy(p.m, matrix + 4 * s, sizeof(p.m));
+            memcpy(p.off, offset + 2 * s, sizeof(p.off));
+            p.pitch = w, p.id = label_id[s], p.ch = box[4 * s + 2], p.cw = box[4 * s + 3];
+            p.out_h = out_shape[2 * s], p.out_w = out_shape[2 * s + 1];
+            b.block_first[i + 1] = b.block_first[i] + (p.out_h + RT_BAND - 1) / RT_BAND;
+        }
+        hipLaunchKernelGGL(rotated_extent, dim3((unsigned)b.block_first[b.n]), dim3(RT_NT), 0, ctx->stream, b);
+        UOCR_LAUNCH_CHECK(ctx);
+        hipLaunchKernelGGL(rotated_extent_finish, dim3(1), dim3(64), 0, ctx->stream, b);
+        UOCR_LAUNCH_CHECK(ctx);
+        launches += 2;
+    }
+    ctx->rt_band = RT_BAND, ctx->rt_block = RT_NT, ctx->rt_entries = RT_ENTRIES, ctx->rt_launches = launches;
+    return UOCR_OK;
+}
+
+int uocr_rotate_crop(uocr_ctx* ctx, int dtype, int n_entries, const void* const* image, const int* const* labels,
+                     const int* dims, const int* image_index, const int* label_id, const int* box, const double* matrix,
+                     const double* offset, const int* plane, const int* region, void* const* out, const int* out_shape) {
+    UOCR_CHECK_CTX(ctx);
+    UOCR_REQUIRE(ctx, n_entries >= 0);
+    if (n_entries == 0) return UOCR_OK;                            // nothing to do, whatever else was passed
+    UOCR_REQUIRE(ctx, image && labels && dims && image_index && label_id && box && matrix && offset && plane && region && out && out_shape);
+    const int base = UOCR_DTYPE_BASE(dtype);
+    if (base != UOCR_F32 && base != UOCR_F64 && base != UOCR_F16) UOCR_FAIL(ctx, UOCR_ERR_DTYPE, "unknown dtype %d", dtype);
+    const size_t elem = base == UOCR_F64 ? 8 : base == UOCR_F32 ? 4 : 2;
+    // everything is checked before the first launch: an error leaves every output as it was
+    for (int first = 0; first < n_entries; first += RT_ENTRIES) {
+        long long blocks = 0;
+        for (int i = first; i < n_entries && i < first + RT_ENTRIES; ++i) {
+            const int *d = dims + 4 * i, *bx = box + 4 * i, *pl = plane + 2 * i, *rg = region + 4 * i, *os = out_shape + 2 * i;
+            UOCR_REQUIRE(ctx, image[i] && labels[i] && out[i]);
+            UOCR_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(image[i]) | reinterpret_cast<uintptr_t>(out[i])) % elem == 0);
+            UOCR_REQUIRE(ctx, reinterpret_cast<uintptr_t>(labels[i]) % sizeof(int) == 0);
+            UOCR_REQUIRE(ctx, d[0] >= 1 && d[1] >= 1 && d[2] >= 1 && d[3] >= 1);
+            UOCR_REQUIRE(ctx, image_index[i] >= 0 && image_index[i] < d[0] && label_id[i] >= 1);
+            UOCR_REQUIRE(ctx, bx[0] >= 0 && bx[1] >= 0 && bx[2] >= 1 && bx[3] >= 1 && bx[2] <= d[1] - bx[0] && bx[3] <= d[2] - bx[1]);
+            UOCR_REQUIRE(ctx, pl[0] >= 1 && pl[1] >= 1);
+            UOCR_REQUIRE(ctx, rg[0] >= 0 && rg[1] >= 0 && rg[2] >= 1 && rg[3] >= 1 && rg[2] <= pl[0] - rg[0] && rg[3] <= pl[1] - rg[1]);
+            UOCR_REQUIRE(ctx, os[0] >= rg[2] && os[1] >= rg[3]);
+            UOCR_REQUIRE(ctx, rt_finite(matrix + 4 * i, 4) && rt_finite(offset + 2 * i, 2));
+            if ((long long)d[1] * d[2] > INT32_MAX)
+                UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "entry %d: image of %d x %d pixels: linear indices must fit int32", i, d[1], d[2]);
+            blocks += ((long long)os[0] * os[1] + RT_NT - 1) / RT_NT;
+        }
+        if (blocks > INT32_MAX) UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "entries %d..: too many blocks for one grid", first);
+    }
+    int launches = 0;
+    for (int first = 0; first < n_entries; first += RT_ENTRIES) {
+        RCBatch b;
+        memset(&b, 0, sizeof(b));
+        b.n = n_entries - first < RT_ENTRIES ? n_entries - first : RT_ENTRIES;
+        for (int i = 0; i < b.n; ++i) {
+            const int s = first + i;
+            const int *d = dims + 4 * s, *bx = box + 4 * s, *rg = region + 4 * s, *os = out_shape + 2 * s;
+            RCEntry& e = b.entry[i];
+            const size_t pixel = ((size_t)image_index[s] * d[1] + bx[0]) * d[2] + bx[1];
+            e.src = (const char*)image[s] + pixel * d[3] * elem;
+            e.lab = labels[s] + pixel;
+            e.out = out[s];
+            memcpy(e.m, matrix + 4 * s, sizeof(e.m));
+            memcpy(e.off, offset + 2 * s, sizeof(e.off));
+            e.pitch = d[2], e.c = d[3], e.id = label_id[s], e.ch = bx[2], e.cw = bx[3];
+            e.ry0 = rg[0], e.rx0 = rg[1], e.rh = rg[2], e.rw = rg[3];
+            e.out_h = os[0], e.out_w = os[1];
+            e.py = (e.out_h - e.rh) / 2, e.px = (e.out_w - e.rw) / 2;
+            b.block_first[i + 1] = b.block_first[i] + (int)(((long long)e.out_h * e.out_w + RT_NT - 1) / RT_NT);
+        }
+        UOCR_DISPATCH_STORAGE(ctx, dtype, {
+            hipLaunchKernelGGL(rotate_crop<T>, dim3((unsigned)b.block_first[b.n]), dim3(RT_NT), 0, ctx->stream, b);
+            UOCR_LAUNCH_CHECK(ctx);
+        });
+        launches += 1;
+    }
+    ctx->rt_band = RT_BAND, ctx->rt_block = RT_NT, ctx->rt_entries = RT_ENTRIES, ctx->rt_launches = launches;
+    return UOCR_OK;
+}
+
+int uocr_ctx_last_rotate(uocr_ctx* ctx, int* rows_per_band, int* pixels_per_block, int* entries_per_launch, int* launches) {
+    UOCR_CHECK_CTX(ctx);
+    UOCR_REQUIRE(ctx, rows_per_band && pixels_per_block && entries_per_launch && launches);
+    *rows_per_band = ctx->rt_band;
+    *pixels_per_block = ctx->rt_block;
+    *entries_per_launch = ctx->rt_entries;
+    *launches = ctx->rt_launches;
+    return UOCR_OK;
+}
+
+}  // extern "C"

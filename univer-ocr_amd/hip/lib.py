@@ -131,6 +131,11 @@ _PROTOS = {
     'uocr_ctx_last_char_label': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     'uocr_line_crop': [_ctx, _i, _i, C.POINTER(_vp)] + [C.POINTER(_i)] * 10 + [C.POINTER(_vp), C.POINTER(_i)],
     'uocr_ctx_last_line_crop': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
+    'uocr_rotated_extent': [_ctx, _vp, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_d), C.POINTER(_d),
+                            C.POINTER(_i), _vp],
+    'uocr_rotate_crop': [_ctx, _i, _i, C.POINTER(_vp), C.POINTER(_vp)] + [C.POINTER(_i)] * 4 + [C.POINTER(_d)] * 2 +
+                        [C.POINTER(_i)] * 2 + [C.POINTER(_vp), C.POINTER(_i)],
+    'uocr_ctx_last_rotate': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     'uocr_dp_init': [_ctx, _i, _i, _vp],
     'uocr_dp_info': [_ctx, C.POINTER(_i), C.POINTER(_i)],
     'uocr_dp_allreduce_sum': [_ctx, _vp, _sz, _i],

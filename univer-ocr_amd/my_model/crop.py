@@ -7,6 +7,19 @@ rotation angle `_func` (:314-348) hands the crops back unchanged, so that is the
 labelling, the boxes and the crops are kernels of libuniver_hip.so (nn/ops.py: label_components, masked_crop); the only
 thing the host reads is the component table (64 bytes per paragraph).  There is no worker pool.
 
+CropAndRotateParagraphs is the same stage with the reference's default, `find_rotation=True` (:319-347).  Per paragraph
+the reference runs a ternary search over 0..180 degrees for the angle at which the order-0 rotation of the component's
+mask is lowest -- 13 rounds of two probes at EPS = 1, each probe a full ndimage.rotate and a find_objects on a worker
+process -- rotates the mask once more for the region its pixels cover, rotates every companion crop at order 1 and cuts
+it to that region; an angle outside [EPS, 180 - EPS] means "not rotated".  Here a probe is four ints: the kernel behind
+nn/ops.py: rotated_extent asks of every pixel of the would-be rotated plane whether it is set and keeps the extent, no
+rotated array is written.  `search_angle` restates the search on the host; all paragraphs of a page walk through it in
+lock step, so a round is ONE call holding both probes of every paragraph, one more call gets the regions at the final
+angles, and ONE rotate_crop call produces all arrays of all rotated paragraphs, make_divisible_by's frame included: 14
+extent calls and 1 crop call per page, whatever the number of paragraphs, 16 bytes read back per probe.  The geometry
+(matrix, offset, shape of the rotated plane) is computed on the host as scipy computes it (nn/ops.py:
+rotation_geometry).  Unrotated paragraphs go through masked_crop as in CropParagraphs.
+
 LabelChars is the reference's LabelChar (interpreter/interpreter.py:524-571): the `char` layer tag of every cropped line
 -- bit layers first, then letter_spacing -- becomes the (W, N_CHARS) one-hot labels the Char net trains on.  Per line:
 threshold at (mean + max) / 2 of the whole array, read every pixel's bits as a class number (least significant bit
@@ -78,7 +91,8 @@ class CropParagraphs:
         if find_rotation:
             raise NotImplementedError(
                 'CropParagraphs(find_rotation=True): the rotation search (interpreter.py:316-333, a ternary search over '
-                'ndimage.rotate of the paragraph mask) has no device kernel; use find_rotation=False')
+                'ndimage.rotate of the paragraph mask) is not part of this class: use CropAndRotateParagraphs, or '
+                'find_rotation=False')
         self.max_components = max_components
 
     def __call__(self, mask, arrays, divisible_by=None):
@@ -96,6 +110,93 @@ class CropParagraphs:
         components = ops.label_components(mask, 'mean', self.max_components)
         paragraphs = int(components.count[0])
         return [[ops.masked_crop(a, components, 0, k, divisible_by) for k in range(1, paragraphs + 1)] for a in arrays]
+
+
+def search_steps(eps=1.0):
+    """The ternary search of CropAndRotateSingleParagraph._func (interpreter.py:321-336) as a generator: it yields the two
+    probe angles (a, b) of a round, is sent their heights (height_a, height_b), and returns the angle -- None outside
+    [eps, 180 - eps] -- through StopIteration.  The interval shrinks to two thirds per round whatever the heights: 13
+    rounds at eps = 1."""
+    low, high = 0.0, 180.0
+    while high - low > eps:
+        a = low + (high - low) / 3
+        b = high - (high - low) / 3
+        height_a, height_b = yield a, b
+        if height_a < height_b:
+            high = b
+        else:
+            low = a
+    angle = (high + low) / 2
+    return angle if eps <= angle <= 180.0 - eps else None
+
+
+def search_angle(height_of, eps=1.0):
+    """interpreter.py:321-336 for one paragraph: height_of(angle) is the height of the paragraph's mask rotated by
+    `angle` degrees at order 0 (FindObjectHeightInRotated._func, :228-231).  Returns the angle in degrees, or None."""
+    steps = search_steps(eps)
+    try:
+        a, b = next(steps)
+        while True:
+            a, b = steps.send((height_of(a), height_of(b)))
+    except StopIteration as done:
+        return done.value
+
+
+class CropAndRotateParagraphs:
+    def __init__(self, find_rotation=True, eps=1.0, max_components=4096):
+        self.find_rotation, self.eps, self.max_components = find_rotation, eps, max_components
+
+    def find_angles(self, components, paragraphs):
+        """the reference's angle (degrees, or None) of paragraphs 1..`paragraphs` of image 0: all searches in lock step,
+        one rotated_extent call per round.  A probe without a set pixel has height 0 (the reference raises there)."""
+        searches = [search_steps(self.eps) for _ in range(paragraphs)]
+        angles, probes = [None] * paragraphs, {}
+        for p, steps in enumerate(searches):
+            try:
+                probes[p] = next(steps)
+            except StopIteration as done:
+                angles[p] = done.value
+        while probes:
+            order = sorted(probes)
+            extents = ops.rotated_extent(components, 0, [(p + 1, angle) for p in order for angle in probes[p]])
+            heights = [int(y1 - y0) for y0, y1, _, _ in extents]
+            for i, p in enumerate(order):
+                try:
+                    probes[p] = searches[p].send((heights[2 * i], heights[2 * i + 1]))
+                except StopIteration as done:
+                    angles[p] = done.value
+                    del probes[p]
+        return angles
+
+    def __call__(self, mask, arrays, divisible_by=None):
+        """mask: (1, H, W, 1) DeviceArray, arrays: list of (1, H, W, C) DeviceArrays.  Returns
+        result[array_id][paragraph_id] as CropParagraphs does, every paragraph turned by its angle (self.angles[p]
+        afterwards: degrees, or None for a paragraph cut upright).  A paragraph whose rotated mask has no set pixel --
+        the reference raises there -- is cut upright too."""
+        mask = ops.as_device(mask)
+        if mask.ndim != 4 or mask.shape[0] != 1 or mask.shape[3] != 1:
+            raise ValueError(f'CropAndRotateParagraphs: the mask must have shape (1, H, W, 1), got {mask.shape} '
+                             f'(the reference labels one page at a time, datasets.py:18,39)')
+        arrays = [ops.as_device(a) for a in arrays]
+        for a in arrays:
+            if a.ndim != 4 or a.shape[:3] != mask.shape[:3]:
+                raise ValueError(f'CropAndRotateParagraphs: array {a.shape} does not match the mask {mask.shape}')
+        components = ops.label_components(mask, 'mean', self.max_components)
+        paragraphs = int(components.count[0])
+        angles = self.find_angles(components, paragraphs) if self.find_rotation else [None] * paragraphs
+        rotated = [p for p in range(paragraphs) if angles[p] is not None]
+        regions = {}
+        if rotated:
+            extents = ops.rotated_extent(components, 0, [(p + 1, angles[p]) for p in rotated])
+            regions = {p: tuple(int(v) for v in extent) for p, extent in zip(rotated, extents) if extent[1] > extent[0]}
+        for p in rotated:
+            if p not in regions:
+                angles[p] = None
+        self.angles = angles
+        turned = iter(ops.rotate_crop([(a, components, 0, p + 1, angles[p], regions[p]) for a in arrays for p in sorted(regions)],
+                                      divisible_by) if regions else [])
+        return [[next(turned) if p in regions else ops.masked_crop(a, components, 0, p + 1, divisible_by)
+                 for p in range(paragraphs)] for a in arrays]
 
 
 class CropLines:

@@ -9,11 +9,12 @@ channel counts, kernel sizes and losses, so `model_weights.json` files are inter
               dense 512->1024->128->162, softmax cross-entropy                     (:250-304)
 
 Every conv carries L2(0.01) (model.py:36-39).  Of the stages that sit between the nets in the
-reference's model system (host code, interpreter/), ParagraphCrop without the rotation search, LineCrop and
-CharLabel run on the device (my_model/crop.py): TRAIN_LINE is `make_model_system(mode=Modes.TRAIN_LINE)`, and
-`make_train_char_system` assembles [ParagraphCrop, LineCrop, CharLabel, Char], the reference's TRAIN_CHAR system.
-PredToText and the rotation search have no device form yet, and `make_model_system` says so for the modes that need
-them; the TRAIN_CHAR and TRAIN_ALL members of `Modes` are not routed to the new system yet and say where it is.
+reference's model system (host code, interpreter/), ParagraphCrop, LineCrop and CharLabel run on the device
+(my_model/crop.py): TRAIN_LINE is `make_model_system(mode=Modes.TRAIN_LINE)`, and `make_train_char_system` assembles
+[ParagraphCrop, LineCrop, CharLabel, Char], the reference's TRAIN_CHAR system.  Both take `find_rotation=True` for the
+reference's default ParagraphCrop, the one with the rotation search (CropAndRotateParagraphs); their own default stays
+the upright crop.  PredToText has no device form yet, and `make_model_system` says so for the mode that needs it; the
+TRAIN_CHAR and TRAIN_ALL members of `Modes` are not routed to the new system yet and say where it is.
 """
 from enum import Enum
 
@@ -297,7 +298,7 @@ _MISSING_STAGE = {
                   'make_train_char_context_maker',
     'TRAIN_ALL': 'the nets have not been chained through the device ParagraphCrop / LineCrop / CharLabel stages yet '
                  '(TRAIN_CHAR alone is make_train_char_system)',
-    'PREDICT': 'the rotation search of ParagraphCrop (find_rotation=True) and PredToText',
+    'PREDICT': 'PredToText (the rotation search of ParagraphCrop is my_model/crop.py: CropAndRotateParagraphs)',
 }
 
 
@@ -341,7 +342,7 @@ def make_context_maker(mode=Modes.PREDICT):
 
 
 def make_model_system(input_shape, optimizer=None, progress_tracker=None, weights=None, mode=Modes.PREDICT,
-                      char_input_shape=None):
+                      char_input_shape=None, find_rotation=False):
     """model.py:486-717 for the device-resident modes.  Returns (model_system, models, names).
 
     TRAIN_LINE is the system [ParagraphCrop, Line] (names ['ParagraphCrop', 'Line']): the crop stage labels
@@ -349,9 +350,13 @@ def make_model_system(input_shape, optimizer=None, progress_tracker=None, weight
     multiples of 16 (make_divisible_by) and files them as context['cropped_monochrome'] / ['cropped_line']; the Line net
     then takes one step per paragraph through a LineSelector and files line_pred[paragraph].  That equals the reference's
     TRAIN_LINE system (model.py:585-593) built with find_rotation=False, minus its move_to_gpu component: no array
-    visits the host between the stages (the crop stage reads back the component table only)."""
+    visits the host between the stages (the crop stage reads back the component table only).  find_rotation=True (TRAIN_LINE
+    only) puts CropAndRotateParagraphs in the ParagraphCrop slot: the reference's default, every paragraph turned by the
+    angle of its rotation search."""
     if mode is Modes.TRAIN_LINE:
-        return _make_train_line_system(input_shape, optimizer, progress_tracker, weights)
+        return _make_train_line_system(input_shape, optimizer, progress_tracker, weights, find_rotation)
+    if find_rotation:
+        raise ValueError(f'find_rotation=True: {mode.name} has no ParagraphCrop stage')
     plan = {
         Modes.TRAIN_MONOCHROME: ['Monochrome'],
         Modes.TRAIN_PARAGRAPH: ['Paragraph'],
@@ -378,9 +383,13 @@ def make_model_system(input_shape, optimizer=None, progress_tracker=None, weight
     return ModelSystem(components), models, list(plan[mode])
 
 
-def _make_train_line_system(input_shape, optimizer, progress_tracker, weights):
-    from .crop import CropParagraphs
-    crop_paragraphs = CropParagraphs(find_rotation=False)
+def _paragraph_crop_stage(find_rotation):
+    from .crop import CropAndRotateParagraphs, CropParagraphs
+    return CropAndRotateParagraphs(find_rotation=True) if find_rotation else CropParagraphs(find_rotation=False)
+
+
+def _make_train_line_system(input_shape, optimizer, progress_tracker, weights, find_rotation=False):
+    crop_paragraphs = _paragraph_crop_stage(find_rotation)
 
     @track_function('ParagraphCrop', 'forward', progress_tracker)
     def paragraph_crop(context):
@@ -395,7 +404,8 @@ def _make_train_line_system(input_shape, optimizer, progress_tracker, weights):
         model.set_weights(weights)
     line = ModelComponent('Line', model, LineSelector('cropped_monochrome', 'cropped_line', 'line_pred'),
                           delist_result=True)
-    return ModelSystem([RawFunctionComponent(paragraph_crop), line]), {'Line': model}, ['ParagraphCrop', 'Line']
+    return (ModelSystem([RawFunctionComponent(paragraph_crop, crop_paragraphs), line]), {'Line': model},
+            ['ParagraphCrop', 'Line'])
 
 
 def make_train_char_context_maker():
@@ -409,8 +419,9 @@ def make_train_char_context_maker():
     return make_context
 
 
-def make_train_char_system(input_shape, optimizer=None, progress_tracker=None, weights=None):
-    """model.py:632-645: the reference's TRAIN_CHAR system built with find_rotation=False, minus its rename and move
+def make_train_char_system(input_shape, optimizer=None, progress_tracker=None, weights=None, find_rotation=False):
+    """model.py:632-645: the reference's TRAIN_CHAR system built with find_rotation=False (or, with find_rotation=True,
+    as the reference builds it: CropAndRotateParagraphs in the ParagraphCrop slot), minus its rename and move
     components -- no array visits the host between the stages.  Returns (model_system, {'Char': model},
     ['ParagraphCrop', 'LineCrop', 'CharLabel', 'Char']).
       ParagraphCrop  labels context['paragraph_pred'], cuts context['monochrome_pred'], ['line'] and ['char'] to every
@@ -420,8 +431,7 @@ def make_train_char_system(input_shape, optimizer=None, progress_tracker=None, w
       CharLabel      context['char_labels'][p][l] from cropped_2_char
       Char           one step per line through a CharSelector; predictions at context['char_pred'][p][l]
     input_shape is the Char net's, (batch, *, width, channels): its height is CHAR_INPUT_HEIGHT."""
-    from .crop import CropParagraphs
-    crop_paragraphs = CropParagraphs(find_rotation=False)
+    crop_paragraphs = _paragraph_crop_stage(find_rotation)
 
     @track_function('ParagraphCrop', 'forward', progress_tracker)
     def paragraph_crop(context):
@@ -436,6 +446,6 @@ def make_train_char_system(input_shape, optimizer=None, progress_tracker=None, w
         model.set_weights(weights)
     char = ModelComponent('Char', model, CharSelector('cropped_2_monochrome', 'char_labels', 'char_pred'),
                           delist_result=True)
-    components = [RawFunctionComponent(paragraph_crop), make_line_crop_component(progress_tracker),
+    components = [RawFunctionComponent(paragraph_crop, crop_paragraphs), make_line_crop_component(progress_tracker),
                   make_char_label_component(progress_tracker), char]
     return ModelSystem(components), {'Char': model}, ['ParagraphCrop', 'LineCrop', 'CharLabel', 'Char']

@@ -195,6 +195,15 @@ class Runtime:
         self.call('uocr_ctx_last_line_crop', *[C.byref(x) for x in v])
         return tuple(x.value for x in v)
 
+    def last_rotate(self):
+        """(output rows per block of a probe, output pixels per block of an entry, probes / entries per launch, kernel
+        launches) of the most recent uocr_rotated_extent or uocr_rotate_crop call on the current lane
+        (uocr_ctx_last_rotate); all 0 before the first."""
+        import ctypes as C
+        v = [C.c_int() for _ in range(4)]
+        self.call('uocr_ctx_last_rotate', *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
     def set_loss_snapshot(self, arena):
         """From now on the fused optimizer tails launched on the CURRENT lane end by copying `arena`'s slots into the next
         row of its ring (LossArena.arm); None switches it off."""

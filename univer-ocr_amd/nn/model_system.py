@@ -80,10 +80,10 @@ class BaseComponent:
 
 
 class RawFunctionComponent(BaseComponent):
-    """A host stage: the same `func(context)` in every mode."""
+    """A host stage: the same `func(context)` in every mode.  `stage`: the object behind func, for whoever asks."""
 
-    def __init__(self, func):
-        self.func = func
+    def __init__(self, func, stage=None):
+        self.func, self.stage = func, stage
 
     def __call__(self, context):
         self.func(context)

@@ -596,6 +596,98 @@ def masked_crop(array, components, image_index, k, divisible_by=None):
     return out
 
 
+# ---- paragraph rotation (interpreter/interpreter.py:188-231, :319-347: the rotation search of ParagraphCrop) ----------
+def rotation_geometry(ih, iw, angle):
+    """What ndimage.rotate(.., angle, axes=(2, 1), reshape=True) computes in Python before it reaches its C loop, for an
+    input plane of ih x iw: (M, offset, out_shape) -- M the 2 x 2 float64 matrix [[c, s], [-s, c]], out_shape the
+    (rows, columns) of the rotated plane, offset the float64 pair (in_shape - 1) / 2 - M @ ((out_shape - 1) / 2).  Output
+    pixel (oy, ox) reads the source coordinate offset + M @ (oy, ox).  The angle is in degrees."""
+    c, s = np.cos(np.deg2rad(angle)), np.sin(np.deg2rad(angle))
+    M = np.array([[c, s], [-s, c]])
+    out_shape = (np.ptp(M @ [[0, 0, ih, ih], [0, iw, 0, iw]], axis=1) + 0.5).astype(int)
+    offset = (np.array([ih, iw]) - 1) / 2 - M @ ((out_shape - 1) / 2)
+    return M, offset, (int(out_shape[0]), int(out_shape[1]))
+
+
+def _box_of(components, image_index, k, who):
+    boxes = components.boxes[image_index]
+    if not 1 <= k <= len(boxes):
+        raise ValueError(f'{who}: image {image_index} has components 1..{len(boxes)}, not {k}')
+    y0, y1, x0, x1 = (int(v) for v in boxes[k - 1])
+    return y0, x0, y1 - y0, x1 - x0
+
+
+def _flat(values, ctype):
+    values = [v for group in values for v in group]
+    return (ctype * len(values))(*values)
+
+
+def rotated_extent(components, image_index, probes):
+    """The half-open extents (y0, y1, x0, x1) -- ndimage.find_objects -- of the set pixels of
+    ndimage.rotate(labels[box] == k, angle, axes=(2, 1), order=0, reshape=True) for every probe (k, angle) of `probes`: k a
+    component (1-based) of image `image_index`, the box its bounding box.  Returns an int32 (len(probes), 4) host array,
+    (0, 0, 0, 0) where no pixel is set; the height FindObjectHeightInRotated._func (interpreter.py:228-231) returns is
+    y1 - y0.  ONE uocr_rotated_extent call (none for an empty list); no rotated array exists anywhere, the host reads 16
+    bytes per probe."""
+    import ctypes as C
+    probes = [(int(k), float(angle)) for k, angle in probes]
+    if not probes:
+        return np.zeros((0, 4), np.int32)
+    n, h, w = components.labels.shape
+    boxes = [_box_of(components, image_index, k, 'rotated_extent') for k, _ in probes]
+    geometry = [rotation_geometry(bh, bw, angle) for (_, _, bh, bw), (_, angle) in zip(boxes, probes)]
+    extent = CP.empty((len(probes), 4), np.int32)
+    _rt().call('uocr_rotated_extent', components.labels.ptr, n, h, w, int(image_index), len(probes),
+               (C.c_int * len(probes))(*[k for k, _ in probes]), _flat(boxes, C.c_int),
+               _flat([M.reshape(-1).tolist() for M, _, _ in geometry], C.c_double),
+               _flat([offset.tolist() for _, offset, _ in geometry], C.c_double),
+               _flat([shape for _, _, shape in geometry], C.c_int), extent.ptr)
+    return extent.numpy().copy()
+
+
+def rotate_crop(entries, divisible_by=None):
+    """rotate_array(.., angle)[:, region_y, region_x, :] of interpreter.py:343-346 for a flat list of entries (array,
+    components, image_index, k, angle, region): the order-1 rotation by `angle` degrees of array * (labels == k) cut to
+    component k's box, cut to region = (y0, y1, x0, x1) of the rotated plane (what rotated_extent returned for (k,
+    angle)).  divisible_by=(y, x) also adds make_divisible_by's zero frame, as masked_crop does.  ONE uocr_rotate_crop
+    call for all entries, whatever their sizes and channel counts (none for an empty list); returns the (1, h, w, C)
+    DeviceArrays in the entries' order and dtype."""
+    import ctypes as C
+    entries = [(a, comp, int(index), int(k), float(angle), tuple(int(v) for v in region))
+               for a, comp, index, k, angle, region in entries]
+    if not entries:
+        return []
+    for a, comp, index, k, angle, region in entries:
+        if not isinstance(a, DeviceArray) or a.ndim != 4:
+            raise ValueError(f'rotate_crop: expected (N, H, W, C) device arrays, got {getattr(a, "shape", type(a))}')
+        if comp.labels.shape != a.shape[:3]:
+            raise ValueError(f'rotate_crop: labels {comp.labels.shape} do not belong to an array of shape {a.shape}')
+    code = entries[0][0].code & 0xff
+    if any(a.code & 0xff != code for a, *_ in entries):
+        raise ValueError('rotate_crop: the arrays of one call share a dtype, got ' +
+                         ', '.join(sorted({str(a.dtype) for a, *_ in entries})))
+    boxes = [_box_of(comp, index, k, 'rotate_crop') for _, comp, index, k, _, _ in entries]
+    geometry = [rotation_geometry(bh, bw, e[4]) for (_, _, bh, bw), e in zip(boxes, entries)]
+    regions, shapes = [], []
+    for (*_, (y0, y1, x0, x1)), (_, _, plane) in zip(entries, geometry):
+        if not (0 <= y0 < y1 <= plane[0] and 0 <= x0 < x1 <= plane[1]):
+            raise ValueError(f'rotate_crop: the region [{y0}, {y1}) x [{x0}, {x1}) is empty or not inside the rotated plane {plane}')
+        rh, rw = y1 - y0, x1 - x0
+        regions.append((y0, x0, rh, rw))
+        shapes.append((rh, rw) if divisible_by is None else
+                      (rh + divisible_by[0] - rh % divisible_by[0], rw + divisible_by[1] - rw % divisible_by[1]))
+    n = len(entries)
+    outs = [CP.empty((1, oh, ow, e[0].shape[3]), e[0].dtype) for e, (oh, ow) in zip(entries, shapes)]
+    _rt().call('uocr_rotate_crop', code, n, (C.c_void_p * n)(*[e[0].ptr for e in entries]),
+               (C.c_void_p * n)(*[e[1].labels.ptr for e in entries]), _flat([e[0].shape for e in entries], C.c_int),
+               (C.c_int * n)(*[e[2] for e in entries]), (C.c_int * n)(*[e[3] for e in entries]), _flat(boxes, C.c_int),
+               _flat([M.reshape(-1).tolist() for M, _, _ in geometry], C.c_double),
+               _flat([offset.tolist() for _, offset, _ in geometry], C.c_double),
+               _flat([plane for _, _, plane in geometry], C.c_int), _flat(regions, C.c_int),
+               (C.c_void_p * n)(*[a.ptr for a in outs]), _flat(shapes, C.c_int))
+    return outs
+
+
 # ---- char labels (interpreter/interpreter.py:547-571: CharLabel) -----------------------------------------------------
 def char_label(lines, bits, n_chars, want_ids=False):
     """The (W, n_chars) one-hot labels of every line of `lines`, a flat list of (1, H, W, C) DeviceArrays whose first
