@@ -18,7 +18,7 @@
 //                        byte per pixel, votes per column by a direct scan and writes its cols x n_chars block of the
 //                        labels, zeros and ones together, as 16-byte stores
 // The tensor crosses HBM twice.  No atomics: results are bit-identical run to run.
-#include "uocr_common.h"
+#include "entry_batch.h"
 
 namespace {
 
@@ -45,23 +45,6 @@ struct CLBatch {
 };
 static_assert(sizeof(CLBatch) <= 4096, "the descriptor travels as a kernel argument");
 
-template <typename T>
-struct CLVec {
-    static constexpr int N = 16 / sizeof(T);
-    using type = T __attribute__((ext_vector_type(16 / sizeof(T))));
-};
-
-// the line whose blocks [first[i], first[i + 1]) contain block b (block-uniform)
-__device__ __forceinline__ int cl_line_of(const int* first, int n, int b) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (first[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // block-wide max for CL_NT threads; valid in thread 0.  Contains barriers.
 __device__ __forceinline__ double cl_block_max(double mx, double* smax /* >= CL_NT / 64 */) {
     mx = wave_reduce_max(mx);
@@ -78,19 +61,17 @@ template <typename T>
 __global__ __launch_bounds__(CL_NT) void char_label_stats(const CLBatch b, double* __restrict__ partial) {
     __shared__ double smem[17];
     __shared__ double smax[CL_NT / 64];
-    using V = typename CLVec<T>::type;
-    constexpr int VEC = CLVec<T>::N;
+    using V = typename EBVec<T>::type;
+    constexpr int VEC = EBVec<T>::N;
     const int tid = threadIdx.x;
-    const int line = cl_line_of(b.stat_first, b.n, blockIdx.x);
+    const int line = eb_entry_of(b.stat_first, b.n, blockIdx.x);
     const int chunk = blockIdx.x - b.stat_first[line];
     const size_t count = (size_t)b.line[line].h * b.line[line].w * b.c;
     const size_t first = (size_t)chunk * CL_CHUNK;
     const int n = (int)(count - first < (size_t)CL_CHUNK ? count - first : (size_t)CL_CHUNK);
     const T* p = (const T*)b.line[line].x + first;
-    int head = (int)(((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) / sizeof(T));   // elements up to a 16-byte border
-    head = head < n ? head : n;
-    const int nvec = (n - head) / VEC, tail = n - head - nvec * VEC;
-    double sum = 0.0, mx = -INFINITY;
+    const auto [head, nvec, tail] = eb_split(p, n);
+    double mx = -INFINITY, sum = 0.0;
     if (tid < head) {
         const double v = (double)p[tid];
         sum += v;
@@ -129,10 +110,10 @@ __global__ __launch_bounds__(CL_NT) void char_label_vote(const CLBatch b, const 
     __shared__ unsigned long long stage[CL_STAGE_WORDS + 1];   // (+1: the decode reads two bytes per pixel)
     __shared__ unsigned char codes[CL_MAX_H * CL_COLS];
     __shared__ int win[CL_COLS];
-    using V = typename CLVec<T>::type;
-    constexpr int VEC = CLVec<T>::N;
+    using V = typename EBVec<T>::type;
+    constexpr int VEC = EBVec<T>::N;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int line = cl_line_of(b.tile_first, b.n, blockIdx.x);
+    const int line = eb_entry_of(b.tile_first, b.n, blockIdx.x);
     const int tile = blockIdx.x - b.tile_first[line];
     const int h = b.line[line].h, w = b.line[line].w, c = b.c, bits = b.bits, n_chars = b.n_chars;
     const int x0 = tile * CL_COLS, ncols = w - x0 < CL_COLS ? w - x0 : CL_COLS;
@@ -218,9 +199,7 @@ __global__ __launch_bounds__(CL_NT) void char_label_vote(const CLBatch b, const 
     // the tile's rows of the labels are one contiguous range of ncols * n_chars elements
     T* out = (T*)b.line[line].labels + (size_t)x0 * n_chars;
     const int n = ncols * n_chars;
-    int head = (int)(((16 - (reinterpret_cast<uintptr_t>(out) & 15)) & 15) / sizeof(T));
-    head = head < n ? head : n;
-    const int nvec = (n - head) / VEC, tail = n - head - nvec * VEC;
+    const auto [head, nvec, tail] = eb_split(out, n);
     if (tid < head) out[tid] = (T)(win[tid / n_chars] == tid % n_chars ? 1.0f : 0.0f);
     V* ov = reinterpret_cast<V*>(out + head);
     for (int i = tid; i < nvec; i += CL_NT) {
@@ -253,17 +232,18 @@ int uocr_char_label(uocr_ctx* ctx, int dtype, int n_lines, const void* const* x,
     UOCR_REQUIRE(ctx, n_lines >= 0);
     if (n_lines == 0) return UOCR_OK;                              // nothing to do, whatever else was passed
     UOCR_REQUIRE(ctx, x && h && w && labels);
-    const int base = UOCR_DTYPE_BASE(dtype);
-    if (base != UOCR_F32 && base != UOCR_F64 && base != UOCR_F16) UOCR_FAIL(ctx, UOCR_ERR_DTYPE, "unknown dtype %d", dtype);
+    const size_t elem = eb_storage_elem(ctx, dtype);
+    if (!elem) return UOCR_ERR_DTYPE;
     UOCR_REQUIRE(ctx, bits >= 1 && bits <= 8);
     UOCR_REQUIRE(ctx, c >= bits && c <= CL_MAX_C);
     UOCR_REQUIRE(ctx, n_chars >= 1 && n_chars <= (1 << bits));
-    const size_t elem = base == UOCR_F64 ? 8 : base == UOCR_F32 ? 4 : 2;
+    const auto stat_blocks = [&](int i) { return ((long long)h[i] * w[i] * c + CL_CHUNK - 1) / CL_CHUNK; };
+    const auto tile_blocks = [&](int i) { return (w[i] + CL_COLS - 1) / CL_COLS; };
     // everything is checked before the first launch: an error leaves every output as it was
     long long max_stat_blocks = 0;
     for (int first = 0; first < n_lines; first += CL_LINES) {
-        long long stat_blocks = 0, tile_blocks = 0;
-        for (int i = first; i < n_lines && i < first + CL_LINES; ++i) {
+        const int count = eb_group_size(n_lines, first, CL_LINES);
+        for (int i = first; i < first + count; ++i) {
             UOCR_REQUIRE(ctx, x[i] && labels[i] && (!ids || ids[i]));
             UOCR_REQUIRE(ctx, h[i] >= 1 && w[i] >= 1);
             UOCR_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(x[i]) | reinterpret_cast<uintptr_t>(labels[i])) % elem == 0);
@@ -271,13 +251,11 @@ int uocr_char_label(uocr_ctx* ctx, int dtype, int n_lines, const void* const* x,
             if (h[i] > CL_MAX_H)
                 UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "line %d is %d rows high: the vote kernel holds at most %d rows", i, h[i],
                           CL_MAX_H);
-            const long long count = (long long)h[i] * w[i] * c;
-            stat_blocks += (count + CL_CHUNK - 1) / CL_CHUNK;
-            tile_blocks += (w[i] + CL_COLS - 1) / CL_COLS;
         }
-        if (stat_blocks > INT32_MAX || tile_blocks > INT32_MAX)
+        const long long group = eb_group_blocks(first, count, stat_blocks);
+        if (group < 0 || eb_group_blocks(first, count, tile_blocks) < 0)
             UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "lines %d..: too many blocks for one grid", first);
-        max_stat_blocks = stat_blocks > max_stat_blocks ? stat_blocks : max_stat_blocks;
+        max_stat_blocks = group > max_stat_blocks ? group : max_stat_blocks;
     }
     // workspace: (sum, max) per statistics block of one launch; the launch pairs of a call follow each other on the stream
     if (int rc = uocr_need_workspace(ctx, 2 * (size_t)max_stat_blocks * sizeof(double))) return rc;
@@ -286,14 +264,14 @@ int uocr_char_label(uocr_ctx* ctx, int dtype, int n_lines, const void* const* x,
     for (int first = 0; first < n_lines; first += CL_LINES) {
         CLBatch b;
         memset(&b, 0, sizeof(b));
-        b.n = n_lines - first < CL_LINES ? n_lines - first : CL_LINES;
+        b.n = eb_group_size(n_lines, first, CL_LINES);
+        eb_block_first(first, b.n, b.stat_first, stat_blocks);
+        eb_block_first(first, b.n, b.tile_first, tile_blocks);
         b.c = c, b.bits = bits, b.n_chars = n_chars;
         for (int i = 0; i < b.n; ++i) {
             const int s = first + i;
             b.line[i].x = x[s], b.line[i].labels = labels[s], b.line[i].ids = ids ? ids[s] : nullptr;
             b.line[i].h = h[s], b.line[i].w = w[s];
-            b.stat_first[i + 1] = b.stat_first[i] + (int)(((long long)h[s] * w[s] * c + CL_CHUNK - 1) / CL_CHUNK);
-            b.tile_first[i + 1] = b.tile_first[i] + (w[s] + CL_COLS - 1) / CL_COLS;
         }
         UOCR_DISPATCH_STORAGE(ctx, dtype, {
             hipLaunchKernelGGL(char_label_stats<T>, dim3((unsigned)b.stat_first[b.n]), dim3(CL_NT), 0, ctx->stream, b,

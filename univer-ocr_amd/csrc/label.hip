@@ -22,7 +22,7 @@
 //   7. label_relabel   final labels; box / area / coordinate sums: runs of equal label inside a wave are combined (a
 //                      segmented reduction along the row), full-width runs of consecutive rows too, one atomic per
 //                      field and flush -- never one per pixel
-#include "uocr_common.h"
+#include "entry_batch.h"
 
 // float64 forms of the activation accessors of uocr_common.h (8 / 16 bytes per access)
 __device__ __forceinline__ double ld1(const double* p) { return *p; }
@@ -430,8 +430,7 @@ int uocr_label_components(uocr_ctx* ctx, int dtype, const void* x, int n, int h,
     UOCR_REQUIRE(ctx, n >= 0 && h >= 0 && w >= 0 && max_components >= 0);
     UOCR_REQUIRE(ctx, thresh_mode == UOCR_THRESH_MEAN || thresh_mode == UOCR_THRESH_MEAN_MAX ||
                           thresh_mode == UOCR_THRESH_VALUE);
-    const int base = UOCR_DTYPE_BASE(dtype);
-    if (base != UOCR_F32 && base != UOCR_F64 && base != UOCR_F16) UOCR_FAIL(ctx, UOCR_ERR_DTYPE, "unknown dtype %d", dtype);
+    if (!eb_storage_elem(ctx, dtype)) return UOCR_ERR_DTYPE;
     if ((long long)h * w > (long long)INT32_MAX - LCHUNK)
         UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "image of %d x %d pixels: linear indices must fit int32", h, w);
     if (n == 0 || h == 0 || w == 0) return UOCR_OK;
@@ -500,8 +499,7 @@ int uocr_masked_crop(uocr_ctx* ctx, int dtype, const void* image, const int* lab
     UOCR_REQUIRE(ctx, image_index >= 0 && image_index < n && label_id >= 1);
     UOCR_REQUIRE(ctx, y0 >= 0 && x0 >= 0 && ch <= h - y0 && cw <= w - x0);
     UOCR_REQUIRE(ctx, out_h >= ch && out_w >= cw);
-    const int base = UOCR_DTYPE_BASE(dtype);
-    if (base != UOCR_F32 && base != UOCR_F64 && base != UOCR_F16) UOCR_FAIL(ctx, UOCR_ERR_DTYPE, "unknown dtype %d", dtype);
+    if (!eb_storage_elem(ctx, dtype)) return UOCR_ERR_DTYPE;
     const size_t out_pixels = (size_t)out_h * out_w;
     if (out_pixels == 0 || c == 0) return UOCR_OK;
     const size_t blocks = (out_pixels + LNT - 1) / LNT;

@@ -16,7 +16,7 @@
 // a by-value kernel argument (no device allocation, no copy, no host synchronisation: asynchronous and capturable).
 // No atomics, no workspace.
 // hipcc-flags: -ffp-contract=off
-#include "uocr_common.h"
+#include "entry_batch.h"
 
 namespace {
 
@@ -39,23 +39,6 @@ struct LCBatch {
     int n;
 };
 static_assert(sizeof(LCBatch) <= 4096, "the descriptor travels as a kernel argument");
-
-template <typename T>
-struct LCVec {
-    static constexpr int N = 16 / sizeof(T);
-    using type = T __attribute__((ext_vector_type(16 / sizeof(T))));
-};
-
-// the entry whose blocks [first[i], first[i + 1]) contain block b (block-uniform; entries without blocks are passed over)
-__device__ __forceinline__ int lc_entry_of(const int* first, int n, int b) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (first[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // ndimage.zoom at order 0: the input index output index j reads, or -1 where scipy writes its constant 0
 __device__ __forceinline__ int lc_zoom_index(int j, double z, int n_in) {
@@ -109,18 +92,16 @@ __device__ __forceinline__ void lc_gather(const LCEntry& e, size_t q, T* v) {
 
 template <typename T>
 __global__ __launch_bounds__(LC_NT) void line_crop_gather(const LCBatch b) {
-    using V = typename LCVec<T>::type;
-    constexpr int VEC = LCVec<T>::N;
+    using V = typename EBVec<T>::type;
+    constexpr int VEC = EBVec<T>::N;
     const int tid = threadIdx.x;
-    const int i = lc_entry_of(b.block_first, b.n, blockIdx.x);
+    const int i = eb_entry_of(b.block_first, b.n, blockIdx.x);
     const LCEntry& e = b.entry[i];
     const size_t count = (size_t)e.zoom_h * e.out_w * e.c;
     const size_t first = (size_t)(blockIdx.x - b.block_first[i]) * LC_CHUNK;
     const int n = (int)(count - first < (size_t)LC_CHUNK ? count - first : (size_t)LC_CHUNK);
     T* out = (T*)e.out + first;
-    int head = (int)(((16 - (reinterpret_cast<uintptr_t>(out) & 15)) & 15) / sizeof(T));   // elements up to a 16-byte border
-    head = head < n ? head : n;
-    const int nvec = (n - head) / VEC, tail = n - head - nvec * VEC;
+    const auto [head, nvec, tail] = eb_split(out, n);
     if (tid < head) {
         T v;
         lc_gather<T, 1>(e, first + tid, &v);
@@ -154,13 +135,13 @@ int uocr_line_crop(uocr_ctx* ctx, int dtype, int n_entries, const void* const* s
     UOCR_REQUIRE(ctx, n_entries >= 0);
     if (n_entries == 0) return UOCR_OK;                            // nothing to do, whatever else was passed
     UOCR_REQUIRE(ctx, src && src_h && src_w && c && y0 && x0 && box_h && box_w && quarter_turns && zoom_h && zoom_w && out && out_w);
-    const int base = UOCR_DTYPE_BASE(dtype);
-    if (base != UOCR_F32 && base != UOCR_F64 && base != UOCR_F16) UOCR_FAIL(ctx, UOCR_ERR_DTYPE, "unknown dtype %d", dtype);
-    const size_t elem = base == UOCR_F64 ? 8 : base == UOCR_F32 ? 4 : 2;
+    const size_t elem = eb_storage_elem(ctx, dtype);
+    if (!elem) return UOCR_ERR_DTYPE;
+    const auto blocks = [&](int i) { return ((long long)zoom_h[i] * out_w[i] * c[i] + LC_CHUNK - 1) / LC_CHUNK; };
     // everything is checked before the first launch: an error leaves every output as it was
     for (int first = 0; first < n_entries; first += LC_ENTRIES) {
-        long long blocks = 0;
-        for (int i = first; i < n_entries && i < first + LC_ENTRIES; ++i) {
+        const int count = eb_group_size(n_entries, first, LC_ENTRIES);
+        for (int i = first; i < first + count; ++i) {
             UOCR_REQUIRE(ctx, src[i] && (out[i] || out_w[i] == 0));   // (an output without elements has no address)
             UOCR_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(src[i]) | reinterpret_cast<uintptr_t>(out[i])) % elem == 0);
             UOCR_REQUIRE(ctx, c[i] >= 1 && src_h[i] >= 1 && src_w[i] >= 1);
@@ -171,15 +152,16 @@ int uocr_line_crop(uocr_ctx* ctx, int dtype, int n_entries, const void* const* s
             const long long span = (long long)out_w[i] * c[i];
             if (span > INT32_MAX || span * zoom_h[i] / LC_CHUNK > INT32_MAX)
                 UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "entry %d: %d x %d x %d is too large an output", i, zoom_h[i], out_w[i], c[i]);
-            blocks += (span * zoom_h[i] + LC_CHUNK - 1) / LC_CHUNK;
         }
-        if (blocks > INT32_MAX) UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "entries %d..: too many blocks for one grid", first);
+        if (eb_group_blocks(first, count, blocks) < 0)
+            UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "entries %d..: too many blocks for one grid", first);
     }
     int launches = 0;
     for (int first = 0; first < n_entries; first += LC_ENTRIES) {
         LCBatch b;
         memset(&b, 0, sizeof(b));
-        b.n = n_entries - first < LC_ENTRIES ? n_entries - first : LC_ENTRIES;
+        b.n = eb_group_size(n_entries, first, LC_ENTRIES);
+        eb_block_first(first, b.n, b.block_first, blocks);
         for (int i = 0; i < b.n; ++i) {
             const int s = first + i;
             LCEntry& e = b.entry[i];
@@ -193,7 +175,6 @@ int uocr_line_crop(uocr_ctx* ctx, int dtype, int n_entries, const void* const* s
             // which reads index 0 just as ratio 0 does)
             e.zy = e.zoom_h > 1 ? (double)(e.rot_h - 1) / (double)(e.zoom_h - 1) : 0.0;
             e.zx = e.zoom_w > 1 ? (double)(e.rot_w - 1) / (double)(e.zoom_w - 1) : 0.0;
-            b.block_first[i + 1] = b.block_first[i] + (int)(((long long)e.zoom_h * e.out_w * e.c + LC_CHUNK - 1) / LC_CHUNK);
         }
         if (b.block_first[b.n] == 0) continue;                     // (outputs without elements)
         UOCR_DISPATCH_STORAGE(ctx, dtype, {

@@ -24,7 +24,7 @@
 // All probes / entries of a call travel together, RT_ENTRIES per launch, in a by-value kernel argument (no device
 // allocation, no host synchronisation: asynchronous and capturable).  Integer atomics only: bit-identical run to run.
 // hipcc-flags: -ffp-contract=off
-#include "uocr_common.h"
+#include "entry_batch.h"
 
 namespace {
 
@@ -60,17 +60,6 @@ struct RCBatch {
 };
 static_assert(sizeof(RTBatch) <= 4096 && sizeof(RCBatch) <= 4096, "the descriptor travels as a kernel argument");
 
-// the probe / entry whose blocks [first[i], first[i + 1]) contain block b (block-uniform; those without blocks are passed over)
-__device__ __forceinline__ int rt_entry_of(const int* first, int n, int b) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (first[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // (offset + oy * m0) + ox * m1, each operation rounded on its own
 __device__ __forceinline__ double rt_coord(double off, double m0, double m1, int oy, int ox) {
     return __dadd_rn(__dadd_rn(off, __dmul_rn((double)oy, m0)), __dmul_rn((double)ox, m1));
@@ -80,7 +69,7 @@ __device__ __forceinline__ double rt_coord(double off, double m0, double m1, int
 __device__ __forceinline__ bool rt_inside(double c, int n) { return c >= 0.0 && c <= (double)(n - 1); }
 
 __global__ __launch_bounds__(RT_NT) void rotated_extent(const RTBatch b) {
-    const int i = rt_entry_of(b.block_first, b.n, blockIdx.x);
+    const int i = eb_entry_of(b.block_first, b.n, blockIdx.x);
     const RTProbe& p = b.probe[i];
     const int row0 = (blockIdx.x - b.block_first[i]) * RT_BAND;
     const int rows = p.out_h - row0 < RT_BAND ? p.out_h - row0 : RT_BAND;
@@ -123,7 +112,7 @@ __global__ void rotated_extent_finish(const RTBatch b) {
 
 template <typename T>
 __global__ __launch_bounds__(RT_NT) void rotate_crop(const RCBatch b) {
-    const int i = rt_entry_of(b.block_first, b.n, blockIdx.x);
+    const int i = eb_entry_of(b.block_first, b.n, blockIdx.x);
     const RCEntry& e = b.entry[i];
     const size_t o = (size_t)(blockIdx.x - b.block_first[i]) * RT_NT + threadIdx.x;
     if (o >= (size_t)e.out_h * e.out_w) return;
@@ -167,10 +156,15 @@ __global__ __launch_bounds__(RT_NT) void rotate_crop(const RCBatch b) {
     }
 }
 
-inline bool rt_finite(const double* v, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!(v[i] - v[i] == 0.0)) return false;
-    return true;
+// matrix and offset of entry i are numbers (inf * 0 and NaN * 0 are NaN)
+inline bool rt_finite(const double* matrix, const double* offset, int i) {
+    const double *m = matrix + 4 * i, *o = offset + 2 * i;
+    return m[0] * 0.0 + m[1] * 0.0 + m[2] * 0.0 + m[3] * 0.0 + o[0] * 0.0 + o[1] * 0.0 == 0.0;
+}
+
+// the box (y0, x0, height, width) is not empty and lies inside h x w
+inline bool rt_box_inside(const int* bx, int h, int w) {
+    return bx[0] >= 0 && bx[1] >= 0 && bx[2] >= 1 && bx[3] >= 1 && bx[2] <= h - bx[0] && bx[3] <= w - bx[1];
 }
 
 }  // namespace
@@ -188,17 +182,17 @@ int uocr_rotated_extent(uocr_ctx* ctx, const int* labels, int n, int h, int w, i
     UOCR_REQUIRE(ctx, reinterpret_cast<uintptr_t>(extent) % sizeof(int) == 0);
     if ((long long)h * w > INT32_MAX) UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "image of %d x %d pixels: linear indices must fit int32", h, w);
     // everything is checked before the first launch: an error leaves the extents as they were
+    const auto blocks = [&](int i) { return (out_shape[2 * i] + RT_BAND - 1) / RT_BAND; };
     for (int first = 0; first < n_probes; first += RT_ENTRIES) {
-        long long blocks = 0;
-        for (int i = first; i < n_probes && i < first + RT_ENTRIES; ++i) {
-            const int *bx = box + 4 * i, *os = out_shape + 2 * i;
+        const int count = eb_group_size(n_probes, first, RT_ENTRIES);
+        for (int i = first; i < first + count; ++i) {
             UOCR_REQUIRE(ctx, label_id[i] >= 1);
-            UOCR_REQUIRE(ctx, bx[0] >= 0 && bx[1] >= 0 && bx[2] >= 1 && bx[3] >= 1 && bx[2] <= h - bx[0] && bx[3] <= w - bx[1]);
-            UOCR_REQUIRE(ctx, os[0] >= 1 && os[1] >= 1);
-            UOCR_REQUIRE(ctx, rt_finite(matrix + 4 * i, 4) && rt_finite(offset + 2 * i, 2));
-            blocks += (os[0] + RT_BAND - 1) / RT_BAND;
+            UOCR_REQUIRE(ctx, rt_box_inside(box + 4 * i, h, w));
+            UOCR_REQUIRE(ctx, out_shape[2 * i] >= 1 && out_shape[2 * i + 1] >= 1);
+            UOCR_REQUIRE(ctx, rt_finite(matrix, offset, i));
         }
-        if (blocks > INT32_MAX) UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "probes %d..: too many blocks for one grid", first);
+        if (eb_group_blocks(first, count, blocks) < 0)
+            UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "probes %d..: too many blocks for one grid", first);
     }
     UOCR_HIP(ctx, hipMemsetAsync(extent, 0, (size_t)n_probes * 4 * sizeof(int), ctx->stream));
     const int* lab = labels + (size_t)image_index * h * w;
@@ -206,7 +200,8 @@ int uocr_rotated_extent(uocr_ctx* ctx, const int* labels, int n, int h, int w, i
     for (int first = 0; first < n_probes; first += RT_ENTRIES) {
         RTBatch b;
         memset(&b, 0, sizeof(b));
-        b.n = n_probes - first < RT_ENTRIES ? n_probes - first : RT_ENTRIES;
+        b.n = eb_group_size(n_probes, first, RT_ENTRIES);
+        eb_block_first(first, b.n, b.block_first, blocks);
         b.extent = extent + 4 * (size_t)first;
         for (int i = 0; i < b.n; ++i) {
             const int s = first + i;
@@ -216,7 +211,6 @@ int uocr_rotated_extent(uocr_ctx* ctx, const int* labels, int n, int h, int w, i
             memcpy(p.off, offset + 2 * s, sizeof(p.off));
             p.pitch = w, p.id = label_id[s], p.ch = box[4 * s + 2], p.cw = box[4 * s + 3];
             p.out_h = out_shape[2 * s], p.out_w = out_shape[2 * s + 1];
-            b.block_first[i + 1] = b.block_first[i] + (p.out_h + RT_BAND - 1) / RT_BAND;
         }
         hipLaunchKernelGGL(rotated_extent, dim3((unsigned)b.block_first[b.n]), dim3(RT_NT), 0, ctx->stream, b);
         UOCR_LAUNCH_CHECK(ctx);
@@ -235,35 +229,36 @@ int uocr_rotate_crop(uocr_ctx* ctx, int dtype, int n_entries, const void* const*
     UOCR_REQUIRE(ctx, n_entries >= 0);
     if (n_entries == 0) return UOCR_OK;                            // nothing to do, whatever else was passed
     UOCR_REQUIRE(ctx, image && labels && dims && image_index && label_id && box && matrix && offset && plane && region && out && out_shape);
-    const int base = UOCR_DTYPE_BASE(dtype);
-    if (base != UOCR_F32 && base != UOCR_F64 && base != UOCR_F16) UOCR_FAIL(ctx, UOCR_ERR_DTYPE, "unknown dtype %d", dtype);
-    const size_t elem = base == UOCR_F64 ? 8 : base == UOCR_F32 ? 4 : 2;
+    const size_t elem = eb_storage_elem(ctx, dtype);
+    if (!elem) return UOCR_ERR_DTYPE;
+    const auto blocks = [&](int i) { return ((long long)out_shape[2 * i] * out_shape[2 * i + 1] + RT_NT - 1) / RT_NT; };
     // everything is checked before the first launch: an error leaves every output as it was
     for (int first = 0; first < n_entries; first += RT_ENTRIES) {
-        long long blocks = 0;
-        for (int i = first; i < n_entries && i < first + RT_ENTRIES; ++i) {
+        const int count = eb_group_size(n_entries, first, RT_ENTRIES);
+        for (int i = first; i < first + count; ++i) {
             const int *d = dims + 4 * i, *bx = box + 4 * i, *pl = plane + 2 * i, *rg = region + 4 * i, *os = out_shape + 2 * i;
             UOCR_REQUIRE(ctx, image[i] && labels[i] && out[i]);
             UOCR_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(image[i]) | reinterpret_cast<uintptr_t>(out[i])) % elem == 0);
             UOCR_REQUIRE(ctx, reinterpret_cast<uintptr_t>(labels[i]) % sizeof(int) == 0);
             UOCR_REQUIRE(ctx, d[0] >= 1 && d[1] >= 1 && d[2] >= 1 && d[3] >= 1);
             UOCR_REQUIRE(ctx, image_index[i] >= 0 && image_index[i] < d[0] && label_id[i] >= 1);
-            UOCR_REQUIRE(ctx, bx[0] >= 0 && bx[1] >= 0 && bx[2] >= 1 && bx[3] >= 1 && bx[2] <= d[1] - bx[0] && bx[3] <= d[2] - bx[1]);
+            UOCR_REQUIRE(ctx, rt_box_inside(bx, d[1], d[2]));
             UOCR_REQUIRE(ctx, pl[0] >= 1 && pl[1] >= 1);
-            UOCR_REQUIRE(ctx, rg[0] >= 0 && rg[1] >= 0 && rg[2] >= 1 && rg[3] >= 1 && rg[2] <= pl[0] - rg[0] && rg[3] <= pl[1] - rg[1]);
+            UOCR_REQUIRE(ctx, rt_box_inside(rg, pl[0], pl[1]));
             UOCR_REQUIRE(ctx, os[0] >= rg[2] && os[1] >= rg[3]);
-            UOCR_REQUIRE(ctx, rt_finite(matrix + 4 * i, 4) && rt_finite(offset + 2 * i, 2));
+            UOCR_REQUIRE(ctx, rt_finite(matrix, offset, i));
             if ((long long)d[1] * d[2] > INT32_MAX)
                 UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "entry %d: image of %d x %d pixels: linear indices must fit int32", i, d[1], d[2]);
-            blocks += ((long long)os[0] * os[1] + RT_NT - 1) / RT_NT;
         }
-        if (blocks > INT32_MAX) UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "entries %d..: too many blocks for one grid", first);
+        if (eb_group_blocks(first, count, blocks) < 0)
+            UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "entries %d..: too many blocks for one grid", first);
     }
     int launches = 0;
     for (int first = 0; first < n_entries; first += RT_ENTRIES) {
         RCBatch b;
         memset(&b, 0, sizeof(b));
-        b.n = n_entries - first < RT_ENTRIES ? n_entries - first : RT_ENTRIES;
+        b.n = eb_group_size(n_entries, first, RT_ENTRIES);
+        eb_block_first(first, b.n, b.block_first, blocks);
         for (int i = 0; i < b.n; ++i) {
             const int s = first + i;
             const int *d = dims + 4 * s, *bx = box + 4 * s, *rg = region + 4 * s, *os = out_shape + 2 * s;
@@ -278,7 +273,6 @@ int uocr_rotate_crop(uocr_ctx* ctx, int dtype, int n_entries, const void* const*
             e.ry0 = rg[0], e.rx0 = rg[1], e.rh = rg[2], e.rw = rg[3];
             e.out_h = os[0], e.out_w = os[1];
             e.py = (e.out_h - e.rh) / 2, e.px = (e.out_w - e.rw) / 2;
-            b.block_first[i + 1] = b.block_first[i] + (int)(((long long)e.out_h * e.out_w + RT_NT - 1) / RT_NT);
         }
         UOCR_DISPATCH_STORAGE(ctx, dtype, {
             hipLaunchKernelGGL(rotate_crop<T>, dim3((unsigned)b.block_first[b.n]), dim3(RT_NT), 0, ctx->stream, b);

@@ -86,6 +86,21 @@ def line_boxes(top_boxes, bottom_boxes, top_ids, bottom_ids):
     return result
 
 
+def label_page(who, mask, arrays, max_components):
+    """What both paragraph stages do first: mask and arrays go to the device and are checked (`who`: the stage's name in
+    the messages), the mask is labelled at its mean (label_layer).  Returns (arrays, components, number of paragraphs)."""
+    mask = ops.as_device(mask)
+    if mask.ndim != 4 or mask.shape[0] != 1 or mask.shape[3] != 1:
+        raise ValueError(f'{who}: the mask must have shape (1, H, W, 1), got {mask.shape} '
+                         f'(the reference labels one page at a time, datasets.py:18,39)')
+    arrays = [ops.as_device(a) for a in arrays]
+    for a in arrays:
+        if a.ndim != 4 or a.shape[:3] != mask.shape[:3]:
+            raise ValueError(f'{who}: array {a.shape} does not match the mask {mask.shape}')
+    components = ops.label_components(mask, 'mean', max_components)
+    return arrays, components, int(components.count[0])
+
+
 class CropParagraphs:
     def __init__(self, find_rotation=False, max_components=4096):
         if find_rotation:
@@ -99,16 +114,7 @@ class CropParagraphs:
         """mask: (1, H, W, 1) DeviceArray, arrays: list of (1, H, W, C) DeviceArrays.  Returns
         result[array_id][paragraph_id], paragraphs in scipy's label order.  divisible_by=(y, x) adds the zero frame of
         make_divisible_by (my_model/model.py:26-34), which the reference applies to every crop right after this stage."""
-        mask = ops.as_device(mask)
-        if mask.ndim != 4 or mask.shape[0] != 1 or mask.shape[3] != 1:
-            raise ValueError(f'CropParagraphs: the mask must have shape (1, H, W, 1), got {mask.shape} '
-                             f'(the reference labels one page at a time, datasets.py:18,39)')
-        arrays = [ops.as_device(a) for a in arrays]
-        for a in arrays:
-            if a.ndim != 4 or a.shape[:3] != mask.shape[:3]:
-                raise ValueError(f'CropParagraphs: array {a.shape} does not match the mask {mask.shape}')
-        components = ops.label_components(mask, 'mean', self.max_components)
-        paragraphs = int(components.count[0])
+        arrays, components, paragraphs = label_page('CropParagraphs', mask, arrays, self.max_components)
         return [[ops.masked_crop(a, components, 0, k, divisible_by) for k in range(1, paragraphs + 1)] for a in arrays]
 
 
@@ -150,39 +156,26 @@ class CropAndRotateParagraphs:
         """the reference's angle (degrees, or None) of paragraphs 1..`paragraphs` of image 0: all searches in lock step,
         one rotated_extent call per round.  A probe without a set pixel has height 0 (the reference raises there)."""
         searches = [search_steps(self.eps) for _ in range(paragraphs)]
-        angles, probes = [None] * paragraphs, {}
-        for p, steps in enumerate(searches):
-            try:
-                probes[p] = next(steps)
-            except StopIteration as done:
-                angles[p] = done.value
-        while probes:
+        angles, probes, order, heights = [None] * paragraphs, {}, range(paragraphs), None
+        while True:
+            for i, p in enumerate(order):      # every search still running gets its two heights (None: it starts)
+                try:
+                    probes[p] = searches[p].send(heights and (heights[2 * i], heights[2 * i + 1]))
+                except StopIteration as done:
+                    angles[p] = done.value
+                    probes.pop(p, None)
+            if not probes:
+                return angles
             order = sorted(probes)
             extents = ops.rotated_extent(components, 0, [(p + 1, angle) for p in order for angle in probes[p]])
             heights = [int(y1 - y0) for y0, y1, _, _ in extents]
-            for i, p in enumerate(order):
-                try:
-                    probes[p] = searches[p].send((heights[2 * i], heights[2 * i + 1]))
-                except StopIteration as done:
-                    angles[p] = done.value
-                    del probes[p]
-        return angles
 
     def __call__(self, mask, arrays, divisible_by=None):
         """mask: (1, H, W, 1) DeviceArray, arrays: list of (1, H, W, C) DeviceArrays.  Returns
         result[array_id][paragraph_id] as CropParagraphs does, every paragraph turned by its angle (self.angles[p]
         afterwards: degrees, or None for a paragraph cut upright).  A paragraph whose rotated mask has no set pixel --
         the reference raises there -- is cut upright too."""
-        mask = ops.as_device(mask)
-        if mask.ndim != 4 or mask.shape[0] != 1 or mask.shape[3] != 1:
-            raise ValueError(f'CropAndRotateParagraphs: the mask must have shape (1, H, W, 1), got {mask.shape} '
-                             f'(the reference labels one page at a time, datasets.py:18,39)')
-        arrays = [ops.as_device(a) for a in arrays]
-        for a in arrays:
-            if a.ndim != 4 or a.shape[:3] != mask.shape[:3]:
-                raise ValueError(f'CropAndRotateParagraphs: array {a.shape} does not match the mask {mask.shape}')
-        components = ops.label_components(mask, 'mean', self.max_components)
-        paragraphs = int(components.count[0])
+        arrays, components, paragraphs = label_page('CropAndRotateParagraphs', mask, arrays, self.max_components)
         angles = self.find_angles(components, paragraphs) if self.find_rotation else [None] * paragraphs
         rotated = [p for p in range(paragraphs) if angles[p] is not None]
         regions = {}

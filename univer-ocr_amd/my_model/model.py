@@ -165,6 +165,16 @@ def make_char(input_shape, optimizer=None):
 NET_MAKERS = {'Monochrome': make_monochrome, 'Paragraph': make_paragraph, 'Line': make_line, 'Char': make_char}
 
 
+def _make_net(name, input_shape, optimizer, progress_tracker, weights):
+    """the net `name` of NET_MAKERS with its progress tracker attached and `weights` set (None: neither)"""
+    model = NET_MAKERS[name](input_shape, optimizer)
+    if progress_tracker is not None:
+        model.init_progress_tracker(progress_tracker, name)
+    if weights is not None:
+        model.set_weights(weights)
+    return model
+
+
 def _map_nested(func, value):
     """`func` on every array of a (possibly nested) list / dict structure."""
     if isinstance(value, list):
@@ -206,6 +216,24 @@ def make_char_label_component(progress_tracker=None, source='cropped_2_char', ta
     return RawFunctionComponent(char_label)
 
 
+def make_paragraph_crop_component(find_rotation=False, progress_tracker=None, sources=('monochrome_pred', 'line'),
+                                  targets=('cropped_monochrome', 'cropped_line')):
+    """model.py:552-576 (make_paragraph_crop_component) as a device component: the stage labels context['paragraph_pred']
+    and cuts every context[source] to every paragraph, padded to multiples of 16: context[target][paragraph]
+    (my_model/crop.py: CropParagraphs; with find_rotation=True CropAndRotateParagraphs, the reference's default)."""
+    from .crop import CropAndRotateParagraphs, CropParagraphs
+    crop_paragraphs = CropAndRotateParagraphs(find_rotation=True) if find_rotation else CropParagraphs(find_rotation=False)
+    if len(sources) != len(targets):
+        raise ValueError(f'make_paragraph_crop_component: {len(sources)} sources for {len(targets)} targets')
+
+    @track_function('ParagraphCrop', 'forward', progress_tracker)
+    def paragraph_crop(context):
+        crops = crop_paragraphs(context['paragraph_pred'], [context[source] for source in sources], divisible_by=(16, 16))
+        context.update(zip(targets, crops))
+
+    return RawFunctionComponent(paragraph_crop, crop_paragraphs)
+
+
 def make_line_crop_component(progress_tracker=None, mask='cropped_line', sources=('cropped_monochrome', 'cropped_char'),
                              targets=('cropped_2_monochrome', 'cropped_2_char')):
     """model.py:595-612 (make_line_crop_component) as a device component: context[mask][paragraph] is the paragraph's
@@ -220,9 +248,7 @@ def make_line_crop_component(progress_tracker=None, mask='cropped_line', sources
 
     @track_function('LineCrop', 'forward', progress_tracker)
     def line_crop(context):
-        results = crop_lines(context[mask], [context[source] for source in sources])
-        for target, result in zip(targets, results):
-            context[target] = result
+        context.update(zip(targets, crop_lines(context[mask], [context[source] for source in sources])))
 
     return RawFunctionComponent(line_crop)
 
@@ -312,11 +338,16 @@ class Modes(Enum):
     TRAIN_PAGE = 6        # this backend: all four nets on device-resident page / line batches
 
 
+def _context_maker(mapping):
+    """dataset layers -> context dict {label: the layer `tag` on the device} for mapping = {label: tag}"""
+    def make_context(dataset_get_func, args=(), kwargs={}):
+        layers = dataset_get_func(*args, layer_tags=sorted(set(mapping.values())), **kwargs)
+        return {label: CP.copy(layers[tag]) for label, tag in mapping.items()}
+    return make_context
+
+
 def make_context_maker(mode=Modes.PREDICT):
     """model.py:412-483: dataset layers -> context dict with every array moved to the device."""
-    def to_gpu(arr):
-        return CP.copy(arr)
-
     wanted = {
         Modes.TRAIN_MONOCHROME: {'monochrome_X': 'image', 'monochrome_y': 'monochrome'},
         Modes.TRAIN_PARAGRAPH: {'paragraph_X': 'monochrome', 'paragraph_y': 'paragraph'},
@@ -332,13 +363,7 @@ def make_context_maker(mode=Modes.PREDICT):
         raise NotImplementedError(
             f'{mode.name} has no context maker here: {_MISSING_STAGE[mode.name]} '
             f'(the device stages are in my_model/crop.py)')
-    mapping = wanted[mode]
-
-    def make_context(dataset_get_func, args=(), kwargs={}):
-        tags = sorted(set(mapping.values()))
-        layers = dataset_get_func(*args, layer_tags=tags, **kwargs)
-        return {label: to_gpu(layers[tag]) for label, tag in mapping.items()}
-    return make_context
+    return _context_maker(wanted[mode])
 
 
 def make_model_system(input_shape, optimizer=None, progress_tracker=None, weights=None, mode=Modes.PREDICT,
@@ -371,11 +396,7 @@ def make_model_system(input_shape, optimizer=None, progress_tracker=None, weight
         shape = input_shape
         if name == 'Char':
             shape = char_input_shape or (input_shape[0], CHAR_INPUT_HEIGHT, 64, 1)
-        model = NET_MAKERS[name](shape, optimizer)
-        if progress_tracker is not None:
-            model.init_progress_tracker(progress_tracker, name)
-        if weights is not None:
-            model.set_weights(weights)
+        model = _make_net(name, shape, optimizer, progress_tracker, weights)
         key = name.lower()
         components.append(ModelComponent(name, model, StringSelector(f'{key}_X', f'{key}_y', f'{key}_pred'),
                                          delist_result=True))
@@ -383,40 +404,18 @@ def make_model_system(input_shape, optimizer=None, progress_tracker=None, weight
     return ModelSystem(components), models, list(plan[mode])
 
 
-def _paragraph_crop_stage(find_rotation):
-    from .crop import CropAndRotateParagraphs, CropParagraphs
-    return CropAndRotateParagraphs(find_rotation=True) if find_rotation else CropParagraphs(find_rotation=False)
-
-
 def _make_train_line_system(input_shape, optimizer, progress_tracker, weights, find_rotation=False):
-    crop_paragraphs = _paragraph_crop_stage(find_rotation)
-
-    @track_function('ParagraphCrop', 'forward', progress_tracker)
-    def paragraph_crop(context):
-        crops = crop_paragraphs(context['paragraph_pred'], [context['monochrome_pred'], context['line']],
-                                divisible_by=(16, 16))
-        context['cropped_monochrome'], context['cropped_line'] = crops
-
-    model = make_line(input_shape, optimizer)
-    if progress_tracker is not None:
-        model.init_progress_tracker(progress_tracker, 'Line')
-    if weights is not None:
-        model.set_weights(weights)
+    model = _make_net('Line', input_shape, optimizer, progress_tracker, weights)
     line = ModelComponent('Line', model, LineSelector('cropped_monochrome', 'cropped_line', 'line_pred'),
                           delist_result=True)
-    return (ModelSystem([RawFunctionComponent(paragraph_crop, crop_paragraphs), line]), {'Line': model},
+    return (ModelSystem([make_paragraph_crop_component(find_rotation, progress_tracker), line]), {'Line': model},
             ['ParagraphCrop', 'Line'])
 
 
 def make_train_char_context_maker():
     """model.py:449-459 (the TRAIN_CHAR context) for `make_train_char_system`: the layers monochrome, paragraph, line and
     char of one page, moved to the device (the reference keeps them on the host for its host stages)."""
-    mapping = {'monochrome_pred': 'monochrome', 'paragraph_pred': 'paragraph', 'line': 'line', 'char': 'char'}
-
-    def make_context(dataset_get_func, args=(), kwargs={}):
-        layers = dataset_get_func(*args, layer_tags=sorted(mapping.values()), **kwargs)
-        return {label: CP.copy(layers[tag]) for label, tag in mapping.items()}
-    return make_context
+    return _context_maker({'monochrome_pred': 'monochrome', 'paragraph_pred': 'paragraph', 'line': 'line', 'char': 'char'})
 
 
 def make_train_char_system(input_shape, optimizer=None, progress_tracker=None, weights=None, find_rotation=False):
@@ -431,21 +430,11 @@ def make_train_char_system(input_shape, optimizer=None, progress_tracker=None, w
       CharLabel      context['char_labels'][p][l] from cropped_2_char
       Char           one step per line through a CharSelector; predictions at context['char_pred'][p][l]
     input_shape is the Char net's, (batch, *, width, channels): its height is CHAR_INPUT_HEIGHT."""
-    crop_paragraphs = _paragraph_crop_stage(find_rotation)
-
-    @track_function('ParagraphCrop', 'forward', progress_tracker)
-    def paragraph_crop(context):
-        crops = crop_paragraphs(context['paragraph_pred'], [context['monochrome_pred'], context['line'], context['char']],
-                                divisible_by=(16, 16))
-        context['cropped_monochrome'], context['cropped_line'], context['cropped_char'] = crops
-
-    model = make_char(input_shape, optimizer)
-    if progress_tracker is not None:
-        model.init_progress_tracker(progress_tracker, 'Char')
-    if weights is not None:
-        model.set_weights(weights)
+    paragraph_crop = make_paragraph_crop_component(find_rotation, progress_tracker, ('monochrome_pred', 'line', 'char'),
+                                                   ('cropped_monochrome', 'cropped_line', 'cropped_char'))
+    model = _make_net('Char', input_shape, optimizer, progress_tracker, weights)
     char = ModelComponent('Char', model, CharSelector('cropped_2_monochrome', 'char_labels', 'char_pred'),
                           delist_result=True)
-    components = [RawFunctionComponent(paragraph_crop, crop_paragraphs), make_line_crop_component(progress_tracker),
+    components = [paragraph_crop, make_line_crop_component(progress_tracker),
                   make_char_label_component(progress_tracker), char]
     return ModelSystem(components), {'Char': model}, ['ParagraphCrop', 'LineCrop', 'CharLabel', 'Char']

@@ -4,6 +4,7 @@ This is the seam that replaces the reference's per-layer `_forward_gpu/_backward
 (layers/layers.py:169-197) and its CuPy expressions.  Output shapes follow the reference's
 get_output_shapes; arrays returned are always NEW allocations, as in the reference.
 """
+import ctypes as C
 import math
 
 import numpy as np
@@ -18,6 +19,27 @@ ACT_CODES = {None: hiplib.ACT_NONE, 'relu': hiplib.ACT_RELU, 'leaky': hiplib.ACT
 
 def _rt():
     return CP.runtime()
+
+
+def _ints(values):
+    return (C.c_int * len(values))(*values)
+
+
+def _pointers(arrays):
+    return (C.c_void_p * len(arrays))(*[a.ptr for a in arrays])
+
+
+def _flat(groups, ctype):
+    values = [v for group in groups for v in group]
+    return (ctype * len(values))(*values)
+
+
+def _shared_code(arrays, who, what):
+    """the storage dtype code of a call: the one all its arrays have"""
+    code = arrays[0].code & 0xff
+    if any(a.code & 0xff != code for a in arrays):
+        raise ValueError(f'{who}: the arrays of one call share {what}, got ' + ', '.join(sorted({str(a.dtype) for a in arrays})))
+    return code
 
 
 def _same_dtype(*arrays, grad=None):
@@ -464,7 +486,6 @@ def adam_step(w, g, v, a, lr, beta1, beta2, eps):
 
 
 def _range_args(ranges):
-    import ctypes as C
     n = len(ranges)
     lo = (C.c_longlong * max(n, 1))(*[r[1] for r in ranges])
     hi = (C.c_longlong * max(n, 1))(*[r[2] for r in ranges])
@@ -582,14 +603,8 @@ def masked_crop(array, components, image_index, k, divisible_by=None):
     n, h, w, c = array.shape
     if components.labels.shape != (n, h, w):
         raise ValueError(f'masked_crop: labels {components.labels.shape} do not belong to an array of shape {array.shape}')
-    boxes = components.boxes[image_index]
-    if not 1 <= k <= len(boxes):
-        raise ValueError(f'masked_crop: image {image_index} has components 1..{len(boxes)}, not {k}')
-    y0, y1, x0, x1 = (int(v) for v in boxes[k - 1])
-    ch, cw = y1 - y0, x1 - x0
-    out_h, out_w = ch, cw
-    if divisible_by is not None:
-        out_h, out_w = ch + divisible_by[0] - ch % divisible_by[0], cw + divisible_by[1] - cw % divisible_by[1]
+    y0, x0, ch, cw = _box_of(components, image_index, k, 'masked_crop')
+    out_h, out_w = _framed(ch, cw, divisible_by)
     out = CP.empty((1, out_h, out_w, c), array.dtype)
     _rt().call('uocr_masked_crop', array.code & 0xff, array.ptr, components.labels.ptr, n, h, w, c, int(image_index), int(k),
                y0, x0, ch, cw, out.ptr, out_h, out_w)
@@ -613,13 +628,20 @@ def _box_of(components, image_index, k, who):
     boxes = components.boxes[image_index]
     if not 1 <= k <= len(boxes):
         raise ValueError(f'{who}: image {image_index} has components 1..{len(boxes)}, not {k}')
-    y0, y1, x0, x1 = (int(v) for v in boxes[k - 1])
+    y0, y1, x0, x1 = boxes[k - 1].tolist()
     return y0, x0, y1 - y0, x1 - x0
 
 
-def _flat(values, ctype):
-    values = [v for group in values for v in group]
-    return (ctype * len(values))(*values)
+def _framed(h, w, divisible_by):
+    """h x w in make_divisible_by's zero frame (my_model/model.py:26-34: at least one row and column; None: no frame)"""
+    d = divisible_by
+    return (h, w) if d is None else (h + d[0] - h % d[0], w + d[1] - w % d[1])
+
+
+def _geometry_args(geometry):
+    """matrices, offsets and plane shapes of a list of rotation_geometry results: the three arguments of the kernels"""
+    return (_flat([M.reshape(-1).tolist() for M, _, _ in geometry], C.c_double),
+            _flat([offset.tolist() for _, offset, _ in geometry], C.c_double), _flat([shape for _, _, shape in geometry], C.c_int))
 
 
 def rotated_extent(components, image_index, probes):
@@ -629,7 +651,6 @@ def rotated_extent(components, image_index, probes):
     (0, 0, 0, 0) where no pixel is set; the height FindObjectHeightInRotated._func (interpreter.py:228-231) returns is
     y1 - y0.  ONE uocr_rotated_extent call (none for an empty list); no rotated array exists anywhere, the host reads 16
     bytes per probe."""
-    import ctypes as C
     probes = [(int(k), float(angle)) for k, angle in probes]
     if not probes:
         return np.zeros((0, 4), np.int32)
@@ -638,10 +659,7 @@ def rotated_extent(components, image_index, probes):
     geometry = [rotation_geometry(bh, bw, angle) for (_, _, bh, bw), (_, angle) in zip(boxes, probes)]
     extent = CP.empty((len(probes), 4), np.int32)
     _rt().call('uocr_rotated_extent', components.labels.ptr, n, h, w, int(image_index), len(probes),
-               (C.c_int * len(probes))(*[k for k, _ in probes]), _flat(boxes, C.c_int),
-               _flat([M.reshape(-1).tolist() for M, _, _ in geometry], C.c_double),
-               _flat([offset.tolist() for _, offset, _ in geometry], C.c_double),
-               _flat([shape for _, _, shape in geometry], C.c_int), extent.ptr)
+               _ints([k for k, _ in probes]), _flat(boxes, C.c_int), *_geometry_args(geometry), extent.ptr)
     return extent.numpy().copy()
 
 
@@ -652,7 +670,6 @@ def rotate_crop(entries, divisible_by=None):
     angle)).  divisible_by=(y, x) also adds make_divisible_by's zero frame, as masked_crop does.  ONE uocr_rotate_crop
     call for all entries, whatever their sizes and channel counts (none for an empty list); returns the (1, h, w, C)
     DeviceArrays in the entries' order and dtype."""
-    import ctypes as C
     entries = [(a, comp, int(index), int(k), float(angle), tuple(int(v) for v in region))
                for a, comp, index, k, angle, region in entries]
     if not entries:
@@ -662,29 +679,20 @@ def rotate_crop(entries, divisible_by=None):
             raise ValueError(f'rotate_crop: expected (N, H, W, C) device arrays, got {getattr(a, "shape", type(a))}')
         if comp.labels.shape != a.shape[:3]:
             raise ValueError(f'rotate_crop: labels {comp.labels.shape} do not belong to an array of shape {a.shape}')
-    code = entries[0][0].code & 0xff
-    if any(a.code & 0xff != code for a, *_ in entries):
-        raise ValueError('rotate_crop: the arrays of one call share a dtype, got ' +
-                         ', '.join(sorted({str(a.dtype) for a, *_ in entries})))
-    boxes = [_box_of(comp, index, k, 'rotate_crop') for _, comp, index, k, _, _ in entries]
-    geometry = [rotation_geometry(bh, bw, e[4]) for (_, _, bh, bw), e in zip(boxes, entries)]
+    arrays, components, index, ks, angles, _ = zip(*entries)
+    code = _shared_code(arrays, 'rotate_crop', 'a dtype')
+    boxes = [_box_of(comp, i, k, 'rotate_crop') for comp, i, k in zip(components, index, ks)]
+    geometry = [rotation_geometry(bh, bw, angle) for (_, _, bh, bw), angle in zip(boxes, angles)]
     regions, shapes = [], []
     for (*_, (y0, y1, x0, x1)), (_, _, plane) in zip(entries, geometry):
         if not (0 <= y0 < y1 <= plane[0] and 0 <= x0 < x1 <= plane[1]):
             raise ValueError(f'rotate_crop: the region [{y0}, {y1}) x [{x0}, {x1}) is empty or not inside the rotated plane {plane}')
-        rh, rw = y1 - y0, x1 - x0
-        regions.append((y0, x0, rh, rw))
-        shapes.append((rh, rw) if divisible_by is None else
-                      (rh + divisible_by[0] - rh % divisible_by[0], rw + divisible_by[1] - rw % divisible_by[1]))
-    n = len(entries)
-    outs = [CP.empty((1, oh, ow, e[0].shape[3]), e[0].dtype) for e, (oh, ow) in zip(entries, shapes)]
-    _rt().call('uocr_rotate_crop', code, n, (C.c_void_p * n)(*[e[0].ptr for e in entries]),
-               (C.c_void_p * n)(*[e[1].labels.ptr for e in entries]), _flat([e[0].shape for e in entries], C.c_int),
-               (C.c_int * n)(*[e[2] for e in entries]), (C.c_int * n)(*[e[3] for e in entries]), _flat(boxes, C.c_int),
-               _flat([M.reshape(-1).tolist() for M, _, _ in geometry], C.c_double),
-               _flat([offset.tolist() for _, offset, _ in geometry], C.c_double),
-               _flat([plane for _, _, plane in geometry], C.c_int), _flat(regions, C.c_int),
-               (C.c_void_p * n)(*[a.ptr for a in outs]), _flat(shapes, C.c_int))
+        regions.append((y0, x0, y1 - y0, x1 - x0))
+        shapes.append(_framed(y1 - y0, x1 - x0, divisible_by))
+    outs = [CP.empty((1, oh, ow, a.shape[3]), a.dtype) for a, (oh, ow) in zip(arrays, shapes)]
+    _rt().call('uocr_rotate_crop', code, len(entries), _pointers(arrays), _pointers([comp.labels for comp in components]),
+               _flat([a.shape for a in arrays], C.c_int), _ints(index), _ints(ks), _flat(boxes, C.c_int), *_geometry_args(geometry),
+               _flat(regions, C.c_int), _pointers(outs), _flat(shapes, C.c_int))
     return outs
 
 
@@ -701,19 +709,15 @@ def char_label(lines, bits, n_chars, want_ids=False):
             raise ValueError(f'char_label: expected (1, H, W, C) device arrays, got {getattr(a, "shape", type(a))}')
     if not lines:
         return ([], []) if want_ids else []
-    code, c = lines[0].code & 0xff, lines[0].shape[3]
-    for a in lines:
-        if a.code & 0xff != code or a.shape[3] != c:
-            raise ValueError('char_label: the lines of one call share dtype and channel count, got ' +
-                             ', '.join(f'{x.shape} {x.dtype}' for x in lines))
-    import ctypes as C
-    n = len(lines)
+    code, c = _shared_code(lines, 'char_label', 'dtype and channel count'), lines[0].shape[3]
+    if any(a.shape[3] != c for a in lines):
+        raise ValueError('char_label: the lines of one call share dtype and channel count, got ' +
+                         ', '.join(f'{a.shape} {a.dtype}' for a in lines))
     labels = [CP.empty((a.shape[2], n_chars), a.dtype) for a in lines]
     ids = [CP.empty((a.shape[2],), np.int32) for a in lines] if want_ids else None
-    pointers = lambda arrays: (C.c_void_p * n)(*[a.ptr for a in arrays])
-    _rt().call('uocr_char_label', code, n, pointers(lines), (C.c_int * n)(*[a.shape[1] for a in lines]),
-               (C.c_int * n)(*[a.shape[2] for a in lines]), int(c), int(bits), int(n_chars), pointers(labels),
-               pointers(ids) if want_ids else None)
+    _rt().call('uocr_char_label', code, len(lines), _pointers(lines), _ints([a.shape[1] for a in lines]),
+               _ints([a.shape[2] for a in lines]), int(c), int(bits), int(n_chars), _pointers(labels),
+               _pointers(ids) if want_ids else None)
     return (labels, ids) if want_ids else labels
 
 
@@ -746,21 +750,13 @@ def line_crop(entries, zoomed_height=32, minimal_width=8):
             raise ValueError(f'line_crop: quarter_turns must be 0, 1, 2 or 3, got {turns}')
     if not entries:
         return []
-    code = entries[0][0].code & 0xff
-    if any(a.code & 0xff != code for a, *_ in entries):
-        raise ValueError('line_crop: the arrays of one call share a dtype, got ' +
-                         ', '.join(sorted({str(a.dtype) for a, *_ in entries})))
-    import ctypes as C
-    n = len(entries)
-    shapes = [line_crop_shape(bh, bw, turns, zoomed_height, minimal_width) for _, _, _, bh, bw, turns in entries]
-    outs = [CP.empty((1, zh, ow, a.shape[3]), a.dtype) for (a, *_), (zh, _, ow) in zip(entries, shapes)]
-    pointers = lambda arrays: (C.c_void_p * n)(*[a.ptr for a in arrays])
-    ints = lambda values: (C.c_int * n)(*values)
-    _rt().call('uocr_line_crop', code, n, pointers([e[0] for e in entries]), ints([e[0].shape[1] for e in entries]),
-               ints([e[0].shape[2] for e in entries]), ints([e[0].shape[3] for e in entries]), ints([e[1] for e in entries]),
-               ints([e[2] for e in entries]), ints([e[3] for e in entries]), ints([e[4] for e in entries]),
-               ints([e[5] for e in entries]), ints([s[0] for s in shapes]), ints([s[1] for s in shapes]), pointers(outs),
-               ints([s[2] for s in shapes]))
+    arrays, y0, x0, box_h, box_w, turns = zip(*entries)
+    code = _shared_code(arrays, 'line_crop', 'a dtype')
+    zoom_h, zoom_w, out_w = zip(*[line_crop_shape(bh, bw, t, zoomed_height, minimal_width) for bh, bw, t in zip(box_h, box_w, turns)])
+    outs = [CP.empty((1, zh, ow, a.shape[3]), a.dtype) for a, zh, ow in zip(arrays, zoom_h, out_w)]
+    _rt().call('uocr_line_crop', code, len(entries), _pointers(arrays), *(_ints([a.shape[d] for a in arrays]) for d in (1, 2, 3)),
+               _ints(y0), _ints(x0), _ints(box_h), _ints(box_w), _ints(turns), _ints(zoom_h), _ints(zoom_w), _pointers(outs),
+               _ints(out_w))
     return outs
 
 
