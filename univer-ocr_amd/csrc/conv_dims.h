@@ -6,6 +6,13 @@ struct ConvDims {
     int n, h, w, cin, cout, kh, kw, sh, sw, ph, pw, oh, ow;
 };
 
+// 5x5 / stride s / padding 2 with output = ceil(size / s): the shape of every small-channel conv of the page nets
+// (s = 1: the same-size convs, s = 2: the encoder convs)
+inline bool conv_is5x5_pad2(const ConvDims& d, int stride) {
+    return d.kh == 5 && d.kw == 5 && d.sh == stride && d.sw == stride && d.ph == 2 && d.pw == 2 &&
+           d.oh == (d.h + stride - 1) / stride && d.ow == (d.w + stride - 1) / stride;
+}
+
 // optional epilogue of backward-data: dx *= act'(y) evaluated from the activation OUTPUT y that is
 // this conv's input tensor (same shape as dx).  Folds the backward pass of a preceding fused
 // conv+LeakyReLU/Sigmoid into this kernel's store (act = UOCR_ACT_NONE: plain dx).

@@ -51,15 +51,6 @@ __device__ __forceinline__ void store_vec(TA* __restrict__ p, const float (&v)[C
     }
 }
 
-__device__ __forceinline__ float act_apply(float v, int act, float alpha) {
-    switch (act) {
-        case UOCR_ACT_RELU: return v * (v >= 0.f ? 1.f : 0.f);
-        case UOCR_ACT_LEAKY: return v * ((v >= 0.f ? 1.f : 0.f) + alpha * (v < 0.f ? 1.f : 0.f));
-        case UOCR_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
-        default: return v;
-    }
-}
-
 struct FastDims {
     int n, h, w, oh, ow, ph, pw;
 };

@@ -27,24 +27,6 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
-using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
-using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
-
-__device__ __forceinline__ f32x4 mfma16(f16x4 a, f16x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ float act_apply(float v, int act, float alpha) {
-    switch (act) {
-        case UOCR_ACT_RELU: return v * (v >= 0.f ? 1.f : 0.f);
-        case UOCR_ACT_LEAKY: return v * ((v >= 0.f ? 1.f : 0.f) + alpha * (v < 0.f ? 1.f : 0.f));
-        case UOCR_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
-        default: return v;
-    }
-}
-
 // smallest row stride (halves, a multiple of 4) >= need whose dword count is == target (mod mod)
 constexpr int pick_stride(int need, int mod, int target) {
     int rs = round_up(need, 4);
@@ -52,22 +34,14 @@ constexpr int pick_stride(int need, int mod, int target) {
     return rs;
 }
 
+// the geometry of conv_toeplitz.h (tile height aimed at: 32 rows, 16 at stride 2) + what binary16 elements decide
 template <int C_, int COUT_, int KH_, int KW_, int S_, int MODE_, int DY_ = 0>
-struct Geo {
-    static constexpr int C = C_, COUT = COUT_, KH = KH_, KW = KW_, S = S_, MODE = MODE_;
-    static constexpr int U = (MODE == M_UPFWD || MODE == M_S2DGRAD) ? 2 : 1;   // output pixels per position and axis
-    static constexpr int NCO = U * U * COUT;                   // result rows per position: (phase, co)
-    static constexpr int DY = DY_ ? DY_ : 16 / NCO;            // position rows of one MFMA chain (fewer: zero rows)
-    static constexpr int ROWS = (DY - 1) * S + KH;             // window rows of one chain
-    static constexpr int IB = (ROWS + 3) / 4;                  // row quads
+struct Geo : ToeplitzGeo<C_, COUT_, KH_, KW_, S_, MODE_, (S_ == 1 ? 32 : 16), DY_> {
+    using T = ToeplitzGeo<C_, COUT_, KH_, KW_, S_, MODE_, (S_ == 1 ? 32 : 16), DY_>;
+    using T::C, T::S, T::KW, T::IB, T::IH;
     static constexpr int Q = (KW * C + 3) / 4;                 // 4-half chunks per window row
     static constexpr int NM = IB * Q;                          // MFMAs per chain
     static constexpr int BC = 64;                              // output columns of a block tile (4 chains)
-    static constexpr int BRT = S == 1 ? 32 : 16;
-    static constexpr int RPW = BRT / (4 * DY) > 0 ? BRT / (4 * DY) : 1;  // chains (row bands) per wave
-    static constexpr int BR = 4 * RPW * DY;                    // output rows of a block tile
-    static constexpr int IH = (BR - 1) * S + KH;               // staged input rows
-    static constexpr int IHA = (BR - DY) * S + 4 * IB;         // rows a chain may address (the rest stays zero)
     // one channel, stride 1: a chunk starts at any pixel, i.e. at any 2-byte offset -- the tile holds PAIR WORDS
     // (word[c] = (x[c], x[c+1])), a chunk is the words c and c + 2 (one ds_read2_b32)
     static constexpr bool PAIRW = C == 1 && S == 1;
@@ -81,8 +55,7 @@ struct Geo {
     static constexpr int RS = (S == 2 && C > 1) ? pick_stride(UW * 8, 4, 2) : pick_stride(UW * 8, 64, C == 4 ? 32 : 16);
     static constexpr int RPP = 256 / UW;                       // tile rows staged per pass of the block
     static constexpr int NPASS = (IH + RPP - 1) / RPP;
-    static constexpr int NW = (MODE == M_UPDGRAD || MODE == M_UPFWD || MODE == M_S2DGRAD ? 25 : KH * KW) * C * COUT;
-    static_assert(RPW >= 1 && 16 % NCO == 0 && DY * NCO <= 16 && (C == 1 || C == 2 || C == 4) && UW <= 256, "unsupported geometry");
+    static_assert(UW <= 256, "unsupported geometry");
 };
 
 template <class G>
@@ -371,33 +344,23 @@ __global__ __launch_bounds__(256) void conv_h16_kernel(const _Float16* __restric
 }
 
 template <class G>
-int launch_h16(uocr_ctx* ctx, const void* in, const void* w, const void* bias, void* out, const void* mask_y, int n,
-               int h_in, int w_in, int h_out, int w_out, int ph, int pw, float pad, int use_bias, int act, float alpha,
-               int mask_act, float mask_alpha) {
+int launch_h16(uocr_ctx* ctx, const ToeplitzCall& c) {
     static int resident = 0;                             // blocks of this kernel one CU holds
-    const int hp = (h_out + G::U - 1) / G::U, wp = (w_out + G::U - 1) / G::U;      // the position grid
-    const int tiles_x = (wp + G::BC - 1) / G::BC, tiles_y = (hp + G::BR - 1) / G::BR;
-    const long ntiles = (long)n * tiles_y * tiles_x;
-    UOCR_REQUIRE(ctx, (long)h_in * w_in * G::C < (1l << 31));
+    ToeplitzTiles t;
+    int rc = toeplitz_tiles<G>(ctx, c, &t);
+    if (rc != UOCR_OK) return rc;
     // 4 x the resident blocks: when other lanes hold part of the CUs only some blocks of a launch are resident and
     // the rest start late -- with exactly one block per slot the late ones still own 1/grid of the tiles each (measured
     // in the three-lane step: 6.66 -> 6.75 k pages/s; alone the kernels do not care)
     int grid = 0;
-    const int rc = uocr_persistent_grid(ctx, conv_h16_kernel<G>, ntiles, 4, &resident, &grid);
+    rc = uocr_persistent_grid(ctx, conv_h16_kernel<G>, t.ntiles, 4, &resident, &grid);
     if (rc != UOCR_OK) return rc;
-    hipLaunchKernelGGL(conv_h16_kernel<G>, dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)in, (const float*)w,
-                       (const float*)bias, (_Float16*)out, (const _Float16*)mask_y, h_in, w_in, h_out, w_out, ph, pw,
-                       tiles_x, tiles_y, (int)ntiles, pad, use_bias, act, alpha, mask_act, mask_alpha);
+    hipLaunchKernelGGL(conv_h16_kernel<G>, dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)c.in, (const float*)c.w,
+                       (const float*)c.bias, (_Float16*)c.out, (const _Float16*)c.mask_y, c.h_in, c.w_in, c.h_out, c.w_out,
+                       c.ph, c.pw, t.tiles_x, t.tiles_y, (int)t.ntiles, c.pad, c.use_bias, c.act, c.alpha, c.mask_act,
+                       c.mask_alpha);
     UOCR_LAUNCH_CHECK(ctx);
     return UOCR_OK;
-}
-
-inline bool same5x5(const ConvDims& d) {
-    return d.kh == 5 && d.kw == 5 && d.sh == 1 && d.sw == 1 && d.ph == 2 && d.pw == 2 && d.oh == d.h && d.ow == d.w;
-}
-inline bool half5x5(const ConvDims& d) {                 // the encoder convs: 5x5 / stride 2 / padding 2
-    return d.kh == 5 && d.kw == 5 && d.sh == 2 && d.sw == 2 && d.ph == 2 && d.pw == 2 && d.oh == (d.h + 1) / 2 &&
-           d.ow == (d.w + 1) / 2;
 }
 
 }  // namespace
@@ -408,41 +371,33 @@ inline bool half5x5(const ConvDims& d) {                 // the encoder convs: 5
 // cores nothing to win -- so the others stay on conv_fast.hip / conv_up.hip.
 bool uocr_conv_h16_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d, int which) {
     if (UOCR_DTYPE_BASE(dtype) != UOCR_F16 || !ctx->opt_fast || !ctx->opt_h16 || d.n > 65535) return false;
-    if (same5x5(d)) return (d.cin == 4 && (d.cout == 2 || d.cout == 4)) || (d.cin == 1 && d.cout == 1 && which == 0);
-    if (half5x5(d)) return (d.cin == 4 && d.cout == 4) || (d.cin == 1 && d.cout == 4 && which == 1);
+    if (conv_is5x5_pad2(d, 1)) return (d.cin == 4 && (d.cout == 2 || d.cout == 4)) || (d.cin == 1 && d.cout == 1 && which == 0);
+    if (conv_is5x5_pad2(d, 2)) return (d.cin == 4 && d.cout == 4) || (d.cin == 1 && d.cout == 4 && which == 1);   // (encoder)
     return false;
 }
 
 int uocr_conv_fwd_h16(uocr_ctx* ctx, const void* x, const void* w, const void* b, void* y, const ConvDims& d,
                       double pad_value, int use_bias, int act, double act_alpha) {
-    auto run = [&](auto geo) {
-        using G = decltype(geo);
-        return launch_h16<G>(ctx, x, w, b, y, nullptr, d.n, d.h, d.w, d.oh, d.ow, d.ph, d.pw, (float)pad_value, use_bias,
-                             act, (float)act_alpha, UOCR_ACT_NONE, 0.f);
-    };
-    if (d.sh == 2) return run(Geo<4, 4, 5, 5, 2, M_FWD>{});
-    if (d.cin == 1) return run(Geo<1, 1, 5, 5, 1, M_FWD>{});
-    if (d.cout == 2) return run(Geo<4, 2, 5, 5, 1, M_FWD>{});
-    return run(Geo<4, 4, 5, 5, 1, M_FWD>{});
+    const ToeplitzCall c = toeplitz_fwd_call(x, w, b, y, d.n, d.h, d.w, d.oh, d.ow, d.ph, d.pw, pad_value, use_bias, act,
+                                             act_alpha);
+    if (d.sh == 2) return launch_h16<Geo<4, 4, 5, 5, 2, M_FWD>>(ctx, c);
+    if (d.cin == 1) return launch_h16<Geo<1, 1, 5, 5, 1, M_FWD>>(ctx, c);
+    if (d.cout == 2) return launch_h16<Geo<4, 2, 5, 5, 1, M_FWD>>(ctx, c);
+    return launch_h16<Geo<4, 4, 5, 5, 1, M_FWD>>(ctx, c);
 }
 
 int uocr_conv_dgrad_h16(uocr_ctx* ctx, const void* dy, const void* w, void* dx, const ConvDims& d,
                         const ActMask& mask) {
-    const int mact = mask.y ? mask.act : UOCR_ACT_NONE;
     // stride 2: a 3x3 window over dy per 2x2 block of dx;  stride 1: a forward conv over dy with flipped taps
     // (padding kh - 1 - ph)
-    auto run = [&](auto geo, int ph, int pw) {
-        using G = decltype(geo);
-        return launch_h16<G>(ctx, dy, w, nullptr, dx, mask.y, d.n, d.oh, d.ow, d.h, d.w, ph, pw, 0.f, 0, UOCR_ACT_NONE, 0.f,
-                             mact, (float)mask.alpha);
-    };
+    const int ph = d.sh == 2 ? 1 : d.kh - 1 - d.ph, pw = d.sh == 2 ? 1 : d.kw - 1 - d.pw;
+    const ToeplitzCall c = toeplitz_dgrad_call(dy, w, dx, d.n, d.oh, d.ow, d.h, d.w, ph, pw, mask.y, mask.act, mask.alpha);
     if (d.sh == 2) {
-        if (d.cin == 4) return run(Geo<4, 4, 3, 3, 1, M_S2DGRAD>{}, 1, 1);
-        return run(Geo<4, 1, 3, 3, 1, M_S2DGRAD>{}, 1, 1);
+        if (d.cin == 4) return launch_h16<Geo<4, 4, 3, 3, 1, M_S2DGRAD>>(ctx, c);
+        return launch_h16<Geo<4, 1, 3, 3, 1, M_S2DGRAD>>(ctx, c);
     }
-    const int ph = d.kh - 1 - d.ph, pw = d.kw - 1 - d.pw;
-    if (d.cout == 2) return run(Geo<2, 4, 5, 5, 1, M_DGRAD>{}, ph, pw);
-    return run(Geo<4, 4, 5, 5, 1, M_DGRAD>{}, ph, pw);
+    if (d.cout == 2) return launch_h16<Geo<2, 4, 5, 5, 1, M_DGRAD>>(ctx, c);
+    return launch_h16<Geo<4, 4, 5, 5, 1, M_DGRAD>>(ctx, c);
 }
 
 // Upsample2D(2) + conv 5x5 / padding 2, 4 -> 4 channels, on the low-res grid (conv_up.hip)
@@ -452,13 +407,12 @@ bool uocr_upconv_h16_eligible(uocr_ctx* ctx, int dtype, int cin, int cout) {
 
 int uocr_upconv_fwd_h16(uocr_ctx* ctx, const void* x_low, const void* w, const void* b, void* y, int n, int hl, int wl,
                         int use_bias, int act, double act_alpha) {
-    return launch_h16<Geo<4, 4, 3, 3, 1, M_UPFWD>>(ctx, x_low, w, b, y, nullptr, n, hl, wl, 2 * hl, 2 * wl, 1, 1, 0.f,
-                                                   use_bias, act, (float)act_alpha, UOCR_ACT_NONE, 0.f);
+    return launch_h16<Geo<4, 4, 3, 3, 1, M_UPFWD>>(
+        ctx, toeplitz_fwd_call(x_low, w, b, y, n, hl, wl, 2 * hl, 2 * wl, 1, 1, 0.0, use_bias, act, act_alpha));
 }
 
 int uocr_upconv_dgrad_h16(uocr_ctx* ctx, const void* dy, const void* w, void* dx_low, int n, int hl, int wl,
                           const void* mask_y, int mask_act, double mask_alpha) {
-    return launch_h16<Geo<4, 4, 6, 6, 2, M_UPDGRAD>>(ctx, dy, w, nullptr, dx_low, mask_y, n, 2 * hl, 2 * wl, hl, wl, 2, 2,
-                                                     0.f, 0, UOCR_ACT_NONE, 0.f, mask_y ? mask_act : UOCR_ACT_NONE,
-                                                     (float)mask_alpha);
+    return launch_h16<Geo<4, 4, 6, 6, 2, M_UPDGRAD>>(
+        ctx, toeplitz_dgrad_call(dy, w, dx_low, n, 2 * hl, 2 * wl, hl, wl, 2, 2, mask_y, mask_act, mask_alpha));
 }

@@ -20,18 +20,11 @@
 // hipcc-flags: -mllvm -amdgpu-mfma-vgpr-form=1
 #include "finish_group.h"
 #include "up_phase.h"
-#include "conv_dims.h"
+#include "conv_wgrad_planes.h"
+#include "mfma.h"
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
-using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
-using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
-
-__device__ __forceinline__ f32x4 mfma16(f16x4 a, f16x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
-}
 __device__ __forceinline__ uint32_t lo_pair(uint32_t a, uint32_t b) { return (a & 0xFFFFu) | (b << 16); }
 __device__ __forceinline__ uint32_t hi_pair(uint32_t a, uint32_t b) { return (a >> 16) | (b & 0xFFFF0000u); }
 __device__ __forceinline__ f16x4 read8(const _Float16* p) { return *reinterpret_cast<const f16x4*>(p); }
@@ -594,20 +587,9 @@ __global__ __launch_bounds__(256) void wgrad_h16_up1_kernel(const _Float16* __re
 // the shift s in {-1, 0, +1} moves to the dy operand: with Q = X + s, N = (co, sx = 1 - s) reads dy[Q + sx - 1]
 // (pair words) and M = (parity, ty, ci) reads its plane at Q (aligned): 10 * CI rows -> 3 MFMAs (CI = 4) or 1 (CI = 1)
 // per 16 positions; (odd plane, sx = 0) would be tx = 5 and is dropped; a row of ones yields db.
+// The tile S2 (x plane strides in halves, dy in pair words) is conv_wgrad_planes.h's; the operand-row maps and the
+// scatter into red are the same text as in conv_t32w.hip.
 // ------------------------------------------------------------------------------------------------------------
-template <int CI, int CO>
-struct S2 {
-    static constexpr int BR = 8, BC = 64;            // positions (Y, Q) per tile
-    static constexpr int XR = 2 * BR + 3;            // x rows of a tile
-    static constexpr int XRS = 72;                   // plane row stride (halves): 68 used
-    static constexpr int XP = XR * XRS + 8;          // plane stride (halves)
-    static constexpr int DRS = 72;                   // dy plane row stride (pair words)
-    static constexpr int DP = BR * DRS + 8;          // dy plane stride (words)
-    static constexpr int NT = (10 * CI + 1 + 15) / 16;   // M tiles (the ones row included)
-    static constexpr int NV = 25 * CI * CO + CO;
-    static constexpr int XU = 17;                    // x staging units (8 pixels) per row: 136 >= 132 pixels
-};
-
 template <int CI, int CO>
 __global__ __launch_bounds__(256) void wgrad_h16_s2_kernel(const _Float16* __restrict__ x,
                                                            const _Float16* __restrict__ dy,
@@ -778,15 +760,13 @@ __global__ __launch_bounds__(256) void wgrad_h16_s2_kernel(const _Float16* __res
         }
     }
     __syncthreads();
-    for (int i = tid; i < G::NV; i += 256)
-        partial[(size_t)blockIdx.x * G::NV + i] = red[0][i] + red[1][i] + red[2][i] + red[3][i];
+    write_partials(red, partial);
 }
 
 }  // namespace
 
 bool uocr_conv_wgrad_h16_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d) {
-    return UOCR_DTYPE_BASE(dtype) == UOCR_F16 && ctx->opt_fast && ctx->opt_h16 && d.kh == 5 && d.kw == 5 && d.sh == 1 &&
-           d.sw == 1 && d.ph == 2 && d.pw == 2 && d.oh == d.h && d.ow == d.w &&
+    return UOCR_DTYPE_BASE(dtype) == UOCR_F16 && ctx->opt_fast && ctx->opt_h16 && conv_is5x5_pad2(d, 1) &&
            ((d.cin == 4 && d.cout == 2) || (d.cin == 1 && d.cout == 1)) && (long)d.h * d.w * 4 < (1l << 31);
 }
 
@@ -846,8 +826,7 @@ int uocr_upconv_wgrad_h16(uocr_ctx* ctx, const void* x_low, const void* dy, floa
 
 // dw / db of the 5x5 / stride 2 / padding 2 encoder convs (4 -> 4, 1 -> 4, 1 -> 1)
 bool uocr_conv_wgrad_s2_h16_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d) {
-    return UOCR_DTYPE_BASE(dtype) == UOCR_F16 && ctx->opt_fast && ctx->opt_h16 && d.kh == 5 && d.kw == 5 && d.sh == 2 &&
-           d.sw == 2 && d.ph == 2 && d.pw == 2 && d.oh == (d.h + 1) / 2 && d.ow == (d.w + 1) / 2 &&
+    return UOCR_DTYPE_BASE(dtype) == UOCR_F16 && ctx->opt_fast && ctx->opt_h16 && conv_is5x5_pad2(d, 2) &&
            ((d.cin == 4 && d.cout == 4) || (d.cin == 1 && (d.cout == 4 || d.cout == 1))) &&
            (long)d.h * d.w * d.cin < (1l << 31);
 }
@@ -858,8 +837,8 @@ int launch_s2(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw,
               double pad_value, int use_bias, int accumulate) {
     using G = S2<CI, CO>;
     static int cache = 0;
-    const int tiles_x = (d.ow + 2 + G::BC - 1) / G::BC, tiles_y = (d.oh + G::BR - 1) / G::BR;   // Q runs over [-1, ow]
-    const long ntiles = (long)d.n * tiles_y * tiles_x;
+    int tiles_x, tiles_y;
+    const long ntiles = s2_tiles<CI, CO>(d, &tiles_x, &tiles_y);
     int grid = 0;
     int rc = uocr_persistent_grid(ctx, wgrad_h16_s2_kernel<CI, CO>, ntiles, 1, &cache, &grid);
     if (rc != UOCR_OK) return rc;

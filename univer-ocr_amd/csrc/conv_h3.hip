@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "conv_dims.h"
+#include "mfma.h"
 
 // Outcome (profiles/r03_h3_experiment.txt): 35.2 -> 29.4 us alone on 32 x 256 x 512, page step 0.845 -> 0.838 ms (inside
 // the run-to-run spread), oracle tolerance 1e-5 held on every shape -- but the float32 path's bit-exact properties do not
@@ -32,18 +33,9 @@
 
 namespace {
 
-using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
-using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
-
 constexpr int G = 4, COLS = 16 * G, OWN = COLS - 4;      // computed / owned columns of a strip
 constexpr int LROW = COLS + 4;                           // pixels per LDS row (the last group reads 4 past the loaded ones)
 
-__device__ __forceinline__ f32x4 mfma16(f16x4 a, f16x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
-}
 template <int ACT>
 __device__ __forceinline__ float act_apply(float v, float alpha) {
     if constexpr (ACT == UOCR_ACT_RELU) return fmaxf(v, 0.f);
@@ -174,9 +166,8 @@ __global__ __launch_bounds__(256) void conv_h3_fwd_kernel(const float* __restric
 }  // namespace
 
 bool uocr_conv_h3_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d) {
-    return ctx->opt_h3 && UOCR_DTYPE_BASE(dtype) == UOCR_F32 && d.kh == 5 && d.kw == 5 && d.cin == 4 && d.cout == 2 &&
-           d.sh == 1 && d.sw == 1 && d.ph == 2 && d.pw == 2 && d.oh == d.h && d.ow == d.w && d.n <= 65535 &&
-           (size_t)d.w * 16 < 0x7FFFFFFFu;
+    return ctx->opt_h3 && UOCR_DTYPE_BASE(dtype) == UOCR_F32 && conv_is5x5_pad2(d, 1) && d.cin == 4 && d.cout == 2 &&
+           d.n <= 65535 && (size_t)d.w * 16 < 0x7FFFFFFFu;
 }
 
 int uocr_conv_fwd_h3(uocr_ctx* ctx, const void* x, const void* w, const void* b, void* y, const ConvDims& d,

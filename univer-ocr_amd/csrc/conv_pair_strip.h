@@ -1,13 +1,12 @@
 // Shared by the strip kernels of the fused Monochrome block (conv_pair_strip.hip: float32, conv_pair_strip_h.hip:
-// binary16 storage): LDS layouts, MFMA helpers, the partial-sum layout and the finish launch.  Not part of the C ABI.
+// binary16 storage): LDS layouts, the MFMA ordering helper, the partial-sum layout and the finish launch.  Not part of the C ABI.
 #pragma once
 #include <type_traits>
 
+#include "mfma.h"
 #include "uocr_common.h"
 
 namespace pair_strip {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int CH = 16;
 constexpr int XROW = 80;      // floats per (ring slot, group) of the x ring: copies tx = 0, 1, 2, ones, dump
@@ -35,10 +34,6 @@ struct Strip {
     static constexpr int COLS = 16 * G;              // computed columns per wave
 };
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 template <int P>
 using phase_t = std::integral_constant<int, P>;
 
@@ -49,7 +44,6 @@ __device__ __forceinline__ void mfma_round() { __builtin_amdgcn_sched_barrier(0x
 
 // partial[block][PAIR_NPART]: dW1^T (16 rows: taps 0..8, row 9 = db1) x 16 channels, dW2^T likewise, db2
 constexpr int PAIR_NPART = 2 * 256 + 1;
-
 
 }  // namespace pair_strip
 

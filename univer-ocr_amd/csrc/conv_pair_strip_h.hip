@@ -24,10 +24,6 @@ using namespace pair_strip;
 // and the freshly loaded row is the new second register.  The LDS rings hold the shifted copies as binary16 (the
 // weight-gradient operand = 4 consecutive positions = one ds_read_b64), the transpose scratch holds d_a1 as
 // [position][channel] binary16 with 48-byte rows (ds_read_b64 conflict-free).
-using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
-using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
-using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
-
 constexpr int XROWH = 80;      // halves per (ring slot, group) of the x ring: copies tx = 0, 1, 2, ones, dump
 constexpr int GROWH = 64;
 constexpr int TSTH = 24;       // halves per position row of the transpose scratch (48 B)
@@ -43,9 +39,6 @@ struct StripH {
     static constexpr int COLS = 16 * G;
 };
 
-__device__ __forceinline__ f32x4 mfma16(f16x4 a, f16x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
-}
 __device__ __forceinline__ f16x4 halves4(uint32_t lo, uint32_t hi) {
     const u32x2 v = {lo, hi};
     return __builtin_bit_cast(f16x4, v);
@@ -395,7 +388,6 @@ __global__ __launch_bounds__(512) void pair_strip_bwd_h_kernel(const _Float16* _
 constexpr int TWST = 20;                   // halves per channel row of the [channel][position] image (40 B)
 constexpr int TWSZ = 16 * TWST;
 using fp16x4_lds = __fp16 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-using f32x2 = __attribute__((ext_vector_type(2))) float;
 // two float32 -> one register of two binary16 (round to nearest even: v_cvt_pk_f16_f32)
 __device__ __forceinline__ uint32_t cvt2h(float a, float b) {
     const f32x2 v = {a, b};

@@ -26,40 +26,17 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ float act_apply(float v, int act, float alpha) {
-    switch (act) {
-        case UOCR_ACT_RELU: return v * (v >= 0.f ? 1.f : 0.f);
-        case UOCR_ACT_LEAKY: return v * ((v >= 0.f ? 1.f : 0.f) + alpha * (v < 0.f ? 1.f : 0.f));
-        case UOCR_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
-        default: return v;
-    }
-}
-
+// the geometry of conv_toeplitz.h + what float32 elements decide.  Tile height aimed at: 16 rows -- a block lives for
+// several tiles (prologue paid once, the next tile's loads in flight under the chains), so small tiles cost little and
+// 32 x 256 x 512 gives 4096 of them to spread over the slots
 template <int C_, int COUT_, int KH_, int KW_, int S_, int MODE_, int DY_ = 0>
-struct Geo {
-    static constexpr int C = C_, COUT = COUT_, KH = KH_, KW = KW_, S = S_, MODE = MODE_;
-    static constexpr int U = (MODE == M_UPFWD || MODE == M_S2DGRAD) ? 2 : 1;   // output pixels per position and axis
-    static constexpr int NCO = U * U * COUT;                   // result rows per position: (phase, co)
-    static constexpr int DY = DY_ ? DY_ : 16 / NCO;            // position rows of one MFMA chain
-    static constexpr int ROWS = (DY - 1) * S + KH;             // window rows of one chain
-    static constexpr int IB = (ROWS + 3) / 4;                  // row quads
+struct Geo : ToeplitzGeo<C_, COUT_, KH_, KW_, S_, MODE_, 16, DY_> {
+    using T = ToeplitzGeo<C_, COUT_, KH_, KW_, S_, MODE_, 16, DY_>;
+    using T::C, T::S, T::KW, T::IB, T::IH;
     static constexpr int Q = KW * C;                           // floats per window row
     static constexpr int NM = IB * Q;                          // MFMAs per chain
     static constexpr int BC = S == 1 ? 64 : 32;                // position columns of a block tile
     static constexpr int NCG = BC / 16;                        // chains per row band
-    // target tile height.  16: a block lives for several tiles (prologue paid once, the next tile's loads in flight
-    // under the chains), so small tiles cost little and 32 x 256 x 512 gives 4096 of them to spread over the slots
-    static constexpr int BRT = 16;
-    static constexpr int RPW = BRT / (4 * DY) > 0 ? BRT / (4 * DY) : 1;   // row bands per wave
-    static constexpr int BR = 4 * RPW * DY;                    // position rows of a block tile
-    static constexpr int IH = (BR - 1) * S + KH;               // staged input rows
-    static constexpr int IHA = (BR - DY) * S + 4 * IB;         // rows a chain may address (the rest stays zero)
     static constexpr int PXU = 4 / C;                          // pixels per 16-byte staging unit
     static constexpr int UW = ((BC - 1) * S * C + Q + 3) / 4;  // staging units per tile row
     // row stride in floats (a multiple of 4: 16-byte staging writes).  The 16 lanes of a k-group read 16 / 8 / 4
@@ -68,8 +45,7 @@ struct Geo {
     static constexpr int RS = C == 1 ? round_up(UW * 4 - 16, 64) + 16 : C == 2 ? round_up(UW * 4 - 32, 64) + 32 : UW * 4;
     static constexpr int RPP = 256 / UW;                       // tile rows staged per pass of the block
     static constexpr int NPASS = (IH + RPP - 1) / RPP;
-    static constexpr int NW = (MODE == M_UPDGRAD || MODE == M_UPFWD || MODE == M_S2DGRAD ? 25 : KH * KW) * C * COUT;
-    static_assert(16 % NCO == 0 && DY * NCO <= 16 && 4 % C == 0 && UW <= 256 && RS >= UW * 4, "unsupported geometry");
+    static_assert(UW <= 256 && RS >= UW * 4, "unsupported geometry");
     static_assert(RS % 4 == 0, "16-byte staging writes");
 };
 
@@ -345,22 +321,21 @@ __global__ __launch_bounds__(256) void conv_t32_kernel(const float* __restrict__
 
 // one instantiation: its residency, its grid and the launch
 template <class G, int ACT, int MASK, int BIAS>
-int launch_t32_kinds(uocr_ctx* ctx, const void* in, const void* w, const void* bias, void* out, const void* mask_y, int n,
-                     int h_in, int w_in, int h_out, int w_out, int ph, int pw, float pad, int use_bias, int act,
-                     float alpha, int mask_act, float mask_alpha) {
+int launch_t32_kinds(uocr_ctx* ctx, const ToeplitzCall& c) {
     static int resident = 0;                             // blocks of this kernel one CU holds
-    const int hp = (h_out + G::U - 1) / G::U, wp = (w_out + G::U - 1) / G::U;      // the position grid
-    const int tiles_x = (wp + G::BC - 1) / G::BC, tiles_y = (hp + G::BR - 1) / G::BR;
-    const long ntiles = (long)n * tiles_y * tiles_x;
-    UOCR_REQUIRE(ctx, (long)h_in * w_in * G::C < (1l << 31) && (long)(G::BR * G::U + 1) * w_out * G::COUT < (1l << 29));
+    ToeplitzTiles t;
+    int rc = toeplitz_tiles<G>(ctx, c, &t);
+    if (rc != UOCR_OK) return rc;
+    UOCR_REQUIRE(ctx, (long)(G::BR * G::U + 1) * c.w_out * G::COUT < (1l << 29));
     // one block per resident slot: at 32 x 256 x 512 a block walks two or three tiles, with its prologue paid once and
     // the next tile's loads under the chains of the current one
     int grid = 0;
-    const int rc = uocr_persistent_grid(ctx, conv_t32_kernel<G, ACT, MASK, BIAS>, ntiles, 1, &resident, &grid);
+    rc = uocr_persistent_grid(ctx, conv_t32_kernel<G, ACT, MASK, BIAS>, t.ntiles, 1, &resident, &grid);
     if (rc != UOCR_OK) return rc;
-    hipLaunchKernelGGL((conv_t32_kernel<G, ACT, MASK, BIAS>), dim3(grid), dim3(256), 0, ctx->stream, (const float*)in,
-                       (const float*)w, (const float*)bias, (float*)out, (const float*)mask_y, h_in, w_in, h_out, w_out, ph,
-                       pw, tiles_x, tiles_y, (int)ntiles, pad, use_bias, act, alpha, mask_act, mask_alpha);
+    hipLaunchKernelGGL((conv_t32_kernel<G, ACT, MASK, BIAS>), dim3(grid), dim3(256), 0, ctx->stream, (const float*)c.in,
+                       (const float*)c.w, (const float*)c.bias, (float*)c.out, (const float*)c.mask_y, c.h_in, c.w_in,
+                       c.h_out, c.w_out, c.ph, c.pw, t.tiles_x, t.tiles_y, (int)t.ntiles, c.pad, c.use_bias, c.act, c.alpha,
+                       c.mask_act, c.mask_alpha);
     UOCR_LAUNCH_CHECK(ctx);
     return UOCR_OK;
 }
@@ -369,29 +344,14 @@ int launch_t32_kinds(uocr_ctx* ctx, const void* in, const void* w, const void* b
 // here, once per launch; a pair the nets do not use, a forward conv without bias and "act_dispatch" = 0 take the
 // instantiation with the dynamic tags.
 template <class G, int SIDE>
-int launch_t32(uocr_ctx* ctx, const void* in, const void* w, const void* bias, void* out, const void* mask_y, int n,
-               int h_in, int w_in, int h_out, int w_out, int ph, int pw, float pad, int use_bias, int act, float alpha,
-               int mask_act, float mask_alpha) {
-    return uocr_act_tags<SIDE>(ctx, act, mask_act, [&](auto kinds) {
+int launch_t32(uocr_ctx* ctx, const ToeplitzCall& c) {
+    return uocr_act_tags<SIDE>(ctx, c.act, c.mask_act, [&](auto kinds) {
         using K = decltype(kinds);
         if constexpr (!K::dynamic) {
-            if ((use_bias != 0) == (SIDE == 0))
-                return launch_t32_kinds<G, K::act, K::mask, SIDE == 0>(ctx, in, w, bias, out, mask_y, n, h_in, w_in, h_out,
-                                                                        w_out, ph, pw, pad, use_bias, act, alpha, mask_act,
-                                                                        mask_alpha);
+            if ((c.use_bias != 0) == (SIDE == 0)) return launch_t32_kinds<G, K::act, K::mask, SIDE == 0>(ctx, c);
         }
-        return launch_t32_kinds<G, UOCR_ACT_DYN, UOCR_ACT_DYN, UOCR_ACT_DYN>(ctx, in, w, bias, out, mask_y, n, h_in, w_in,
-                                                                            h_out, w_out, ph, pw, pad, use_bias, act, alpha,
-                                                                            mask_act, mask_alpha);
+        return launch_t32_kinds<G, UOCR_ACT_DYN, UOCR_ACT_DYN, UOCR_ACT_DYN>(ctx, c);
     });
-}
-
-inline bool same5x5(const ConvDims& d) {
-    return d.kh == 5 && d.kw == 5 && d.sh == 1 && d.sw == 1 && d.ph == 2 && d.pw == 2 && d.oh == d.h && d.ow == d.w;
-}
-inline bool half5x5(const ConvDims& d) {                 // the encoder convs: 5x5 / stride 2 / padding 2
-    return d.kh == 5 && d.kw == 5 && d.sh == 2 && d.sw == 2 && d.ph == 2 && d.pw == 2 && d.oh == (d.h + 1) / 2 &&
-           d.ow == (d.w + 1) / 2;
 }
 
 }  // namespace
@@ -401,7 +361,7 @@ inline bool half5x5(const ConvDims& d) {                 // the encoder convs: 5
 // The default library holds only what is on by default (bit 2: backward-data of the 4-channel layers); the other forms --
 // measured slower in the page step, DESIGN.md section 5 -- are built with UOCR_BUILD_EXPERIMENTS=1 ./build.sh.
 bool uocr_conv_t32_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d, int which) {
-    if (dtype != UOCR_F32 || !ctx->opt_fast || d.n > 65535 || !same5x5(d)) return false;
+    if (dtype != UOCR_F32 || !ctx->opt_fast || d.n > 65535 || !conv_is5x5_pad2(d, 1)) return false;
     const int built = ctx->opt_t32 & UOCR_T32_BUILT;
     if (d.cin == 4 && (d.cout == 2 || d.cout == 4)) return built & (1 << which);
     if (d.cin == 1 && d.cout == 1) return built & (8 << which);
@@ -410,34 +370,27 @@ bool uocr_conv_t32_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d, int whi
 
 int uocr_conv_fwd_t32(uocr_ctx* ctx, const void* x, const void* w, const void* b, void* y, const ConvDims& d,
                       double pad_value, int use_bias, int act, double act_alpha) {
-    auto run = [&](auto geo) {
-        using G = decltype(geo);
-        return launch_t32<G, 0>(ctx, x, w, b, y, nullptr, d.n, d.h, d.w, d.oh, d.ow, d.ph, d.pw, (float)pad_value, use_bias,
-                             act, (float)act_alpha, UOCR_ACT_NONE, 0.f);
-    };
 #ifdef UOCR_EXPERIMENTS
-    if (d.cin == 1) return run(Geo<1, 1, 5, 5, 1, M_FWD>{});
-    if (d.cout == 2) return run(Geo<4, 2, 5, 5, 1, M_FWD>{});
-    return run(Geo<4, 4, 5, 5, 1, M_FWD>{});
+    const ToeplitzCall c = toeplitz_fwd_call(x, w, b, y, d.n, d.h, d.w, d.oh, d.ow, d.ph, d.pw, pad_value, use_bias, act,
+                                             act_alpha);
+    if (d.cin == 1) return launch_t32<Geo<1, 1, 5, 5, 1, M_FWD>, 0>(ctx, c);
+    if (d.cout == 2) return launch_t32<Geo<4, 2, 5, 5, 1, M_FWD>, 0>(ctx, c);
+    return launch_t32<Geo<4, 4, 5, 5, 1, M_FWD>, 0>(ctx, c);
 #else
-    (void)run;
     UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "conv_t32 forward: library built without UOCR_BUILD_EXPERIMENTS");
 #endif
 }
 
 int uocr_conv_dgrad_t32(uocr_ctx* ctx, const void* dy, const void* w, void* dx, const ConvDims& d,
                         const ActMask& mask) {
-    const int mact = mask.y ? mask.act : UOCR_ACT_NONE;
-    auto run = [&](auto geo) {                           // a forward conv over dy with flipped taps: padding kh - 1 - ph
-        using G = decltype(geo);
-        return launch_t32<G, 1>(ctx, dy, w, nullptr, dx, mask.y, d.n, d.oh, d.ow, d.h, d.w, d.kh - 1 - d.ph,
-                             d.kw - 1 - d.pw, 0.f, 0, UOCR_ACT_NONE, 0.f, mact, (float)mask.alpha);
-    };
+    // a forward conv over dy with flipped taps: padding kh - 1 - ph
+    const ToeplitzCall c = toeplitz_dgrad_call(dy, w, dx, d.n, d.oh, d.ow, d.h, d.w, d.kh - 1 - d.ph, d.kw - 1 - d.pw,
+                                               mask.y, mask.act, mask.alpha);
 #ifdef UOCR_EXPERIMENTS
-    if (d.cin == 1) return run(Geo<1, 1, 5, 5, 1, M_DGRAD>{});
+    if (d.cin == 1) return launch_t32<Geo<1, 1, 5, 5, 1, M_DGRAD>, 1>(ctx, c);
 #endif
-    if (d.cout == 2) return run(Geo<2, 4, 5, 5, 1, M_DGRAD>{});
-    return run(Geo<4, 4, 5, 5, 1, M_DGRAD>{});
+    if (d.cout == 2) return launch_t32<Geo<2, 4, 5, 5, 1, M_DGRAD>, 1>(ctx, c);
+    return launch_t32<Geo<4, 4, 5, 5, 1, M_DGRAD>, 1>(ctx, c);
 }
 
 // backward-data of Upsample2D(2) + conv 5x5 / padding 2 (4 -> 4 or 1 -> 1 channels) on the low-res grid
@@ -452,11 +405,8 @@ int uocr_upconv_dgrad_t32(uocr_ctx* ctx, const void* dy, const void* w, void* dx
 #ifndef UOCR_EXPERIMENTS
     UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "upconv_t32: library built without UOCR_BUILD_EXPERIMENTS");
 #else
-    const int mact = mask_y ? mask_act : UOCR_ACT_NONE;
-    if (ch == 1)
-        return launch_t32<Geo<1, 1, 6, 6, 2, M_UPDGRAD, 4>, 1>(ctx, dy, w, nullptr, dx_low, mask_y, n, 2 * hl, 2 * wl, hl, wl,
-                                                             2, 2, 0.f, 0, UOCR_ACT_NONE, 0.f, mact, (float)mask_alpha);
-    return launch_t32<Geo<4, 4, 6, 6, 2, M_UPDGRAD>, 1>(ctx, dy, w, nullptr, dx_low, mask_y, n, 2 * hl, 2 * wl, hl, wl, 2, 2,
-                                                     0.f, 0, UOCR_ACT_NONE, 0.f, mact, (float)mask_alpha);
+    const ToeplitzCall c = toeplitz_dgrad_call(dy, w, dx_low, n, 2 * hl, 2 * wl, hl, wl, 2, 2, mask_y, mask_act, mask_alpha);
+    if (ch == 1) return launch_t32<Geo<1, 1, 6, 6, 2, M_UPDGRAD, 4>, 1>(ctx, c);
+    return launch_t32<Geo<4, 4, 6, 6, 2, M_UPDGRAD>, 1>(ctx, c);
 #endif
 }

@@ -20,19 +20,14 @@
 // The vector kernels they would replace (conv_fast.hip) give every thread all taps of one pixel (25-400 FMAs and as
 // many shuffles / LDS reads per pixel) or make five passes over x and dy.
 // hipcc-flags: -mllvm -amdgpu-mfma-vgpr-form=1
-#include "conv_dims.h"
+#include "conv_wgrad_planes.h"
+#include "mfma.h"
 
 // Off by default and slower in the page step: built only with UOCR_BUILD_EXPERIMENTS=1 ./build.sh
 // (-DUOCR_EXPERIMENTS); the default library answers "not eligible".
 #ifdef UOCR_EXPERIMENTS
 
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // four consecutive floats at a 4-byte aligned LDS address
 __device__ __forceinline__ float4 read4_unaligned(const float* p) { return make_float4(p[0], p[1], p[2], p[3]); }
@@ -76,21 +71,9 @@ __global__ __launch_bounds__(256) void wgrad_t32_finish(const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// stride 2
+// stride 2: the tile S2 (plane strides in floats) is conv_wgrad_planes.h's; the operand-row maps and the scatter into
+// red are the same text as in conv_h16w.hip
 // ------------------------------------------------------------------------------------------------------------
-template <int CI, int CO>
-struct S2 {
-    static constexpr int BR = 8, BC = 64;            // positions (Y, Q) per tile
-    static constexpr int XR = 2 * BR + 3;            // x rows of a tile
-    static constexpr int XRS = 72;                   // plane row stride (floats): 68 used
-    static constexpr int XP = XR * XRS + 8;          // plane stride
-    static constexpr int DRS = 72;                   // dy plane row stride
-    static constexpr int DP = BR * DRS + 8;
-    static constexpr int NT = (10 * CI + 1 + 15) / 16;   // M tiles (the ones row included)
-    static constexpr int NV = 25 * CI * CO + CO;
-    static constexpr int XU = 17;                    // x staging units (8 pixels) per row: 136 >= 132 pixels
-};
-
 template <int CI, int CO>
 __global__ __launch_bounds__(256) void wgrad_t32_s2_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                            float* __restrict__ partial, int h, int wd, int oh, int ow,
@@ -194,8 +177,7 @@ __global__ __launch_bounds__(256) void wgrad_t32_s2_kernel(const float* __restri
         }
     }
     __syncthreads();
-    for (int i = tid; i < G::NV; i += 256)
-        partial[(size_t)blockIdx.x * G::NV + i] = red[0][i] + red[1][i] + red[2][i] + red[3][i];
+    write_partials(red, partial);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -301,8 +283,7 @@ __global__ __launch_bounds__(256) void wgrad_t32_e_kernel(const float* __restric
             }
     }
     __syncthreads();
-    for (int i = tid; i < G::NV; i += 256)
-        partial[(size_t)blockIdx.x * G::NV + i] = red[0][i] + red[1][i] + red[2][i] + red[3][i];
+    write_partials(red, partial);
 }
 
 template <int CI, int CO>
@@ -310,8 +291,8 @@ int launch_s2(uocr_ctx* ctx, const void* x, const void* dy, void* dw, void* db, 
               int use_bias, int accumulate) {
     using G = S2<CI, CO>;
     static int cache = 0;
-    const int tiles_x = (d.ow + 2 + G::BC - 1) / G::BC, tiles_y = (d.oh + G::BR - 1) / G::BR;   // Q runs over [-1, ow]
-    const long ntiles = (long)d.n * tiles_y * tiles_x;
+    int tiles_x, tiles_y;
+    const long ntiles = s2_tiles<CI, CO>(d, &tiles_x, &tiles_y);
     int grid = 0;
     int rc = uocr_persistent_grid(ctx, wgrad_t32_s2_kernel<CI, CO>, ntiles, 1, &cache, &grid);
     if (rc != UOCR_OK) return rc;
@@ -349,18 +330,13 @@ int launch_e(uocr_ctx* ctx, const void* x, const void* dy, void* dw, void* db, c
     return UOCR_OK;
 }
 
-inline bool is5x5(const ConvDims& d, int s) {
-    return d.kh == 5 && d.kw == 5 && d.sh == s && d.sw == s && d.ph == 2 && d.pw == 2 &&
-           d.oh == (s == 1 ? d.h : (d.h + 1) / 2) && d.ow == (s == 1 ? d.w : (d.w + 1) / 2);
-}
-
 }  // namespace
 
 // "t32" option bits: 64 = stride-1 weight gradients (4 -> 2, 1 -> 1), 128 = stride-2 (4 -> 4, 1 -> 4, 1 -> 1)
 bool uocr_conv_wgrad_t32_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d) {
     if (dtype != UOCR_F32 || !ctx->opt_fast || (long)d.h * d.w * d.cin >= (1l << 31)) return false;
-    if ((ctx->opt_t32 & 64) && is5x5(d, 1)) return (d.cin == 4 && d.cout == 2) || (d.cin == 1 && d.cout == 1);
-    if ((ctx->opt_t32 & 128) && is5x5(d, 2))
+    if ((ctx->opt_t32 & 64) && conv_is5x5_pad2(d, 1)) return (d.cin == 4 && d.cout == 2) || (d.cin == 1 && d.cout == 1);
+    if ((ctx->opt_t32 & 128) && conv_is5x5_pad2(d, 2))
         return (d.cin == 4 && d.cout == 4) || (d.cin == 1 && (d.cout == 4 || d.cout == 1));
     return false;
 }

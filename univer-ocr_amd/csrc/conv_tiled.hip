@@ -20,15 +20,6 @@ struct TileDims {
     int n, h, w, ph, pw;           // same-size stride-1 conv: output (h, w) == input (h, w)
 };
 
-__device__ __forceinline__ float act_apply(float v, int act, float alpha) {
-    switch (act) {
-        case UOCR_ACT_RELU: return v * (v >= 0.f ? 1.f : 0.f);
-        case UOCR_ACT_LEAKY: return v * ((v >= 0.f ? 1.f : 0.f) + alpha * (v < 0.f ? 1.f : 0.f));
-        case UOCR_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
-        default: return v;
-    }
-}
-
 template <int C, typename TA>
 __device__ __forceinline__ void store_c(TA* p, const float (&v)[C]) {
     if constexpr (C == 4) st4(p, make_float4(v[0], v[1], v[2], v[3]));

@@ -1,7 +1,10 @@
 // Shared between the vertical-Toeplitz convolution kernels (conv_h16.hip: binary16 MFMAs, conv_t32.hip: float32
-// MFMAs): what a result row of the weight operand means in each mode and where its value comes from.
+// MFMAs): what a result row of the weight operand means in each mode and where its value comes from, the part of a
+// kernel's geometry that does not depend on the element type, and the host side of a launch (its arguments, its tile
+// grid).  tap_group also serves conv_up.hip.
 #pragma once
 #include "conv_dims.h"
+#include "mfma.h"
 
 namespace {
 
@@ -16,8 +19,8 @@ enum Mode {
 };
 
 // taps k of one axis of the 5x5 kernel that land on source offset mi - 1 for output parity `phase`: [lo, hi)
-// (upsample2x + conv, see conv_up.hip)
-__device__ __forceinline__ void tap_group(int phase, int mi, int& lo, int& hi) {
+// (upsample2x + conv: conv_up.hip builds its phase weights with it too)
+__host__ __device__ __forceinline__ void tap_group(int phase, int mi, int& lo, int& hi) {
     if (phase == 0) {
         lo = 2 * mi;
         hi = mi == 2 ? 5 : 2 * mi + 2;
@@ -28,6 +31,70 @@ __device__ __forceinline__ void tap_group(int phase, int mi, int& lo, int& hi) {
 }
 
 constexpr int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// What the binary16 and the float32 kernel agree on: an output block of 16 columns x DY position rows per MFMA chain,
+// a block tile of BR position rows (BRT_ = the height aimed at), the staged window.  Each file's Geo derives from this
+// and adds what depends on the element type (chunks per window row, tile width, staging units, LDS row stride).
+template <int C_, int COUT_, int KH_, int KW_, int S_, int MODE_, int BRT_, int DY_>
+struct ToeplitzGeo {
+    static constexpr int C = C_, COUT = COUT_, KH = KH_, KW = KW_, S = S_, MODE = MODE_;
+    static constexpr int U = (MODE == M_UPFWD || MODE == M_S2DGRAD) ? 2 : 1;   // output pixels per position and axis
+    static constexpr int NCO = U * U * COUT;                   // result rows per position: (phase, co)
+    static constexpr int DY = DY_ ? DY_ : 16 / NCO;            // position rows of one MFMA chain (fewer: zero rows)
+    static constexpr int ROWS = (DY - 1) * S + KH;             // window rows of one chain
+    static constexpr int IB = (ROWS + 3) / 4;                  // row quads
+    static constexpr int BRT = BRT_;
+    static constexpr int RPW = BRT / (4 * DY) > 0 ? BRT / (4 * DY) : 1;  // chains (row bands) per wave
+    static constexpr int BR = 4 * RPW * DY;                    // position rows of a block tile
+    static constexpr int IH = (BR - 1) * S + KH;               // staged input rows
+    static constexpr int IHA = (BR - DY) * S + 4 * IB;         // rows a chain may address (the rest stays zero)
+    static constexpr int NW = (MODE == M_UPDGRAD || MODE == M_UPFWD || MODE == M_S2DGRAD ? 25 : KH * KW) * C * COUT;
+    static_assert(RPW >= 1 && 16 % NCO == 0 && DY * NCO <= 16 && (C == 1 || C == 2 || C == 4), "unsupported geometry");
+};
+
+// One launch of a Toeplitz kernel as the entry points describe it; unpacked into the kernel's arguments at the launch.
+//   in  [n][h_in][w_in][C], out [n][h_out][w_out][COUT]; forward: bias / act / alpha, backward-data: mask_y (the
+//   activation OUTPUT of the layer below, same shape as out) / mask_act / mask_alpha
+struct ToeplitzCall {
+    const void *in, *w, *bias;
+    void* out;
+    const void* mask_y;
+    int n, h_in, w_in, h_out, w_out, ph, pw;
+    float pad;
+    int use_bias, act;
+    float alpha;
+    int mask_act;
+    float mask_alpha;
+};
+
+// a forward conv: bias and activation, no mask
+inline ToeplitzCall toeplitz_fwd_call(const void* x, const void* w, const void* b, void* y, int n, int h_in, int w_in,
+                                      int h_out, int w_out, int ph, int pw, double pad, int use_bias, int act,
+                                      double alpha) {
+    return {x, w, b, y, nullptr, n, h_in, w_in, h_out, w_out, ph, pw, (float)pad, use_bias, act, (float)alpha,
+            UOCR_ACT_NONE, 0.f};
+}
+// backward-data: a conv over dy with zero padding, no bias, no activation; dx *= act'(mask_y) where there is a mask
+inline ToeplitzCall toeplitz_dgrad_call(const void* dy, const void* w, void* dx, int n, int h_in, int w_in, int h_out,
+                                        int w_out, int ph, int pw, const void* mask_y, int mask_act, double mask_alpha) {
+    return {dy, w, nullptr, dx, mask_y, n, h_in, w_in, h_out, w_out, ph, pw, 0.f, 0, UOCR_ACT_NONE, 0.f,
+            mask_y ? mask_act : UOCR_ACT_NONE, (float)mask_alpha};
+}
+
+// the tile grid of a call over its position grid (U x U output pixels per position), and the size the kernels' 32-bit
+// offsets inside one input image allow
+struct ToeplitzTiles {
+    int tiles_x, tiles_y;
+    long ntiles;
+};
+template <class G>
+inline int toeplitz_tiles(uocr_ctx* ctx, const ToeplitzCall& c, ToeplitzTiles* t) {
+    const int hp = (c.h_out + G::U - 1) / G::U, wp = (c.w_out + G::U - 1) / G::U;
+    t->tiles_x = (wp + G::BC - 1) / G::BC, t->tiles_y = (hp + G::BR - 1) / G::BR;
+    t->ntiles = (long)c.n * t->tiles_y * t->tiles_x;
+    UOCR_REQUIRE(ctx, (long)c.h_in * c.w_in * G::C < (1l << 31));
+    return UOCR_OK;
+}
 
 // weight of window position (ty, tx), input channel ci, output channel co, from the layer's float32 weights
 // (w = their copy in LDS: every lane builds its NM x 4 operand values from it once per block)

@@ -24,41 +24,15 @@
 // (MFMA accumulators in VGPRs: no v_accvgpr copies between the MFMAs and the VALU code that consumes them)
 #include "up_phase.h"
 #include "finish_group.h"
-#include "conv_dims.h"
+#include "conv_toeplitz.h"
 
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int CH = 4;
 constexpr int RH = 16, RW = 32;                 // low-res positions per tile
 constexpr int XH = RH + 2, XW = RW + 2;         // xl tile: halo 1
 constexpr int XPLANE = 624;                     // >= XH*XW, = 16 mod 32: the 4 channel planes of a half wave on disjoint banks
 constexpr int NWEFF = 9 * CH * 16;
-
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ float act_apply(float v, int act, float alpha) {
-    switch (act) {
-        case UOCR_ACT_RELU: return v * (v >= 0.f ? 1.f : 0.f);
-        case UOCR_ACT_LEAKY: return v * ((v >= 0.f ? 1.f : 0.f) + alpha * (v < 0.f ? 1.f : 0.f));
-        case UOCR_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
-        default: return v;
-    }
-}
-
-// taps k of one axis that land on source offset m (index mi = m + 1) for output parity `phase`: [lo, hi)
-__host__ __device__ __forceinline__ void tap_group(int phase, int mi, int& lo, int& hi) {
-    if (phase == 0) {
-        lo = 2 * mi;
-        hi = mi == 2 ? 5 : 2 * mi + 2;
-    } else {
-        lo = mi == 0 ? 0 : 2 * mi - 1;
-        hi = mi == 0 ? 1 : 2 * mi + 1;
-    }
-}
 
 // weff[(m*4 + c)*16 + phase*4 + o], m = my*3 + mx, phase = py*2 + px
 __global__ __launch_bounds__(256) void upconv_weff_kernel(const float* __restrict__ w, float* __restrict__ weff) {
@@ -164,7 +138,7 @@ __global__ __launch_bounds__(256) void upconv_fwd_kernel(const TA* __restrict__ 
             const float* xr = xs + kq * XPLANE + r * XW + c0 + n;
             f32x4 acc = b4;
 #pragma unroll
-            for (int t = 0; t < 9; ++t) acc = mfma(wa[t], xr[(t / 3) * XW + t % 3], acc);
+            for (int t = 0; t < 9; ++t) acc = mfma4(wa[t], xr[(t / 3) * XW + t % 3], acc);
             // lane: phase = kq, registers = the 4 channels of high-res pixel (2P + phase)
             const int py = ry + r, pxl = rx + c0 + n;
             if (py < row_end && pxl < wl) {
@@ -228,7 +202,7 @@ __global__ __launch_bounds__(256) void upconv_wgrad_kernel(const TA* __restrict_
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
                     const float xv = xr[4 * i + aoff[j]];
-                    acc[j] = mfma(aok[j] ? xv : 0.f, g, acc[j]);
+                    acc[j] = mfma4(aok[j] ? xv : 0.f, g, acc[j]);
                 }
             }
         }

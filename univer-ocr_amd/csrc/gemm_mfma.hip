@@ -95,15 +95,6 @@ struct Epilogue {
     float mask_alpha;
 };
 
-__device__ __forceinline__ float act_apply(float v, int act, float alpha) {
-    switch (act) {
-        case UOCR_ACT_RELU: return v * (v >= 0.f ? 1.f : 0.f);
-        case UOCR_ACT_LEAKY: return v * ((v >= 0.f ? 1.f : 0.f) + alpha * (v < 0.f ? 1.f : 0.f));
-        case UOCR_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
-        default: return v;
-    }
-}
-
 __device__ __forceinline__ void epilogue_store(const Epilogue& e, int i, int j, float v) {
     if (e.bias) v += e.bias[j];
     v = act_apply(v, e.act, e.alpha);

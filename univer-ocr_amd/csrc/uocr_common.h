@@ -345,6 +345,16 @@ static inline bool uocr_aligned_act(const void* p, int dtype) {
 }
 static inline bool uocr_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// act(v) as the float32 epilogues compute it: the products of the reference's masks, 1 / (1 + expf(-v))
+__device__ __forceinline__ float act_apply(float v, int act, float alpha) {
+    switch (act) {
+        case UOCR_ACT_RELU: return v * (v >= 0.f ? 1.f : 0.f);
+        case UOCR_ACT_LEAKY: return v * ((v >= 0.f ? 1.f : 0.f) + alpha * (v < 0.f ? 1.f : 0.f));
+        case UOCR_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
+        default: return v;
+    }
+}
+
 // d act(x) / dx expressed through the activation OUTPUT y (leaky: alpha > 0 so sign(y) == sign(x))
 template <typename T>
 __device__ __forceinline__ T act_grad_from_output(T y, int act, T alpha) {

@@ -7,7 +7,7 @@
 
 constexpr int UP4_NOUT = 404, UP1_NOUT = 26;
 
-// source offset index (0..2) of tap k for output parity p (conv_up.hip: tap_group, in closed form)
+// source offset index (0..2) of tap k for output parity p (conv_toeplitz.h: tap_group, in closed form)
 __device__ __forceinline__ int up_tap_m(int k, int p) { return (k + p) >> 1; }
 
 // value(i): the block's sum of entry i of the 4-channel dWeff row [((my*3 + mx)*4 + c)*16 + phase*4 + o], db at 576 + o

@@ -93,8 +93,15 @@ def train_model(use_gpu=True, show_progress_bar=False, save_train_progress=False
             for name, model in models.items():
                 if name in better:
                     merged.update(model.get_weights())
-            with open(MODEL_WEIGHTS_FILE_PATH, 'w') as f:
-                json.dump(merged, f, separators=(',', ':'))
+            # written beside and renamed: another rank that starts its next stage meanwhile reads a whole file
+            tmp = f'{MODEL_WEIGHTS_FILE_PATH}.{os.getpid()}.tmp'
+            try:
+                with open(tmp, 'w') as f:
+                    json.dump(merged, f, separators=(',', ':'))
+                os.replace(tmp, MODEL_WEIGHTS_FILE_PATH)
+            finally:
+                if os.path.exists(tmp):
+                    os.remove(tmp)
         dp = None
         if world > 1:
             from ..parallel import DataParallel
