@@ -493,6 +493,36 @@ int uocr_rotate_crop(uocr_ctx* ctx, int dtype, int n_entries, const void* const*
  * inputs from it */
 int uocr_ctx_last_rotate(uocr_ctx* ctx, int* rows_per_band, int* pixels_per_block, int* entries_per_launch, int* launches);
 
+/* ---- text of the lines (interpreter/interpreter.py:574-614 PredToText._func1: the PredToText stage) ----------------
+ * The character ids of ALL lines of a page in one call (the reference hands every line to a worker pool after a
+ * device-to-host copy, my_model/model.py:647-656).  Line i is pred[i]: (w[i], n_chars) in `dtype`, the Char net's raw
+ * output, one row per column window.  Per row the maximum (:597); a row whose maximum == 0.0 -- -0.0 included --
+ * contributes nothing (:598), a row that holds a NaN neither (its maximum is NaN and nothing equals NaN); a negative
+ * maximum is a maximum like any other.  Every column that EQUALS its row's maximum is a candidate (:600-601): an exact tie
+ * gives several; candidates are ordered by row and inside a row by column (:602).  The walk (:603-613) starts with
+ * prev = none: id 0 (the tab) resets prev and emits nothing; an id similar to prev is skipped and leaves prev alone; every
+ * other id is emitted and becomes prev.  similar(a, b) is "a lies in the pair of b" (primitives/__init__.py:16-54):
+ * cls[id] is the index of the id's pair, -1 for an id without one -- the library knows no alphabet.  A repeated paired
+ * id collapses, a repeated unpaired one does not.  Since prev always lies in the pair class of the last id that was not
+ * the tab, candidate s[k] is emitted iff s[k] != 0 and not (cls[s[k]] >= 0 and k > 0 and s[k-1] != 0 and cls[s[k-1]] ==
+ * cls[s[k]]), s[k-1] the previous CANDIDATE (rows without candidates are passed over and reset nothing): that is what the
+ * kernels evaluate.
+ * count[i]: int32, the number of emitted ids, always the full number; ids[i]: uint8 of capacity cap[i], the first
+ * min(count, cap) emitted ids in order -- nothing past cap[i] and nothing past count[i] is written (ids[i] may be NULL
+ * where cap[i] = 0).  pred, w, ids, cap, count and cls (n_chars entries) are HOST arrays; pred[i], ids[i], count[i] are
+ * device pointers.
+ * Limits: 1 <= n_chars <= 256, w[i] >= 1, cap[i] >= 0, -1 <= cls[k] < n_chars (UOCR_ERR_ARG otherwise, as for null
+ * pointers, pred[i] / count[i] off their element's alignment and n_lines < 0); UOCR_ERR_DTYPE for an unknown dtype;
+ * UOCR_ERR_UNSUPPORTED for more rows than one grid takes.  Nothing is written on any error; n_lines = 0 is UOCR_OK and
+ * launches nothing (the other arguments are not looked at).  Two launches per 64 lines; 32 bytes of the ctx workspace per
+ * row plus 16 per 64 rows of a line (UOCR_ERR_WORKSPACE).  Comparisons only, no floating-point arithmetic: results equal
+ * the reference's in every dtype.  No atomics: results are bit-identical run to run.  Asynchronous and capturable. */
+int uocr_pred_to_text(uocr_ctx* ctx, int dtype, int n_lines, const void* const* pred, const int* w, int n_chars,
+                      const int* cls, unsigned char* const* ids, const int* cap, int* const* count);
+/* sizes the last uocr_pred_to_text call on this ctx used: rows of a line per block, lines per launch, launches issued
+ * (all 0 before the first call) -- tests size their inputs from it */
+int uocr_ctx_last_pred_to_text(uocr_ctx* ctx, int* rows_per_block, int* lines_per_launch, int* launches);
+
 /* ---- data parallel over the GPUs of one node: RCCL over xGMI ------------------------------------
  * The reference has no multi-GPU path; BASELINE.json adds one to the step loop my_model/trainer.py:213-233
  * -> nn/model_system.py:104-118 -> nn/models.py:250-254: between compute_loss_and_gradients and update_grads

@@ -136,6 +136,9 @@ _PROTOS = {
     'uocr_rotate_crop': [_ctx, _i, _i, C.POINTER(_vp), C.POINTER(_vp)] + [C.POINTER(_i)] * 4 + [C.POINTER(_d)] * 2 +
                         [C.POINTER(_i)] * 2 + [C.POINTER(_vp), C.POINTER(_i)],
     'uocr_ctx_last_rotate': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
+    'uocr_pred_to_text': [_ctx, _i, _i, C.POINTER(_vp), C.POINTER(_i), _i, C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i),
+                          C.POINTER(_vp)],
+    'uocr_ctx_last_pred_to_text': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     'uocr_dp_init': [_ctx, _i, _i, _vp],
     'uocr_dp_info': [_ctx, C.POINTER(_i), C.POINTER(_i)],
     'uocr_dp_allreduce_sum': [_ctx, _vp, _sz, _i],

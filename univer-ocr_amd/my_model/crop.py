@@ -36,7 +36,21 @@ centres of mass: which bottom belongs to which top, which way the text runs, the
 union of its two components' boxes (:494-502); every companion array is cut to it unmasked, turned by a multiple of 90
 degrees so that the text reads left to right, zoomed to 32 rows at order 0 and zero-padded to 8 columns (:504-523).  All
 lines of all paragraphs and all arrays of a page are ONE kernel call (nn/ops.py: line_crop); there is no worker pool.
+
+PredToText is the reference's PredToText (interpreter/interpreter.py:574-614): the Char net's raw output of every line,
+(W, N_CHARS) with one row per column window, becomes the line's text.  Per row the columns that EQUAL the row's maximum
+are candidates (several on an exact tie; none where the maximum is 0 or the row holds a NaN); the candidates of a line
+are walked in order with the last emitted character at hand: the tab (id 0) resets it and emits nothing, a character
+"similar" to it -- the other half of one of 18 Cyrillic / Latin look-alike pairs, or the character itself if it HAS a
+pair -- is dropped, everything else is emitted.  So "aa" reads "a" and "bb" stays "bb": the reference's behaviour, kept
+as it is.  `pred_to_text_rules` restates that walk in NumPy.  The device decides every emission from two adjacent
+candidates (the remembered character always lies in the pair class of the last candidate that was not the tab), for all
+lines of all paragraphs of a page in ONE kernel call (nn/ops.py: pred_to_text), a second one only for lines with tied
+rows; the host reads back the ids and nothing else.  The reference copies every prediction to the host and hands it to
+a worker pool.
 """
+import string
+
 import numpy as np
 
 from ..nn import ops
@@ -252,3 +266,73 @@ class LabelChars:
         flat = [ops.as_device(line) for paragraph in arrays for line in paragraph]
         labels = iter(ops.char_label(flat, self.bits, self.n_chars))
         return [[next(labels) for _ in paragraph] for paragraph in arrays]
+
+
+def _alphabet(first, yo):
+    """the 33 letters from code point `first` on with `yo` in its place after the sixth (Unicode keeps it apart)"""
+    letters = [chr(first + i) for i in range(32)]
+    return ''.join(letters[:6] + [yo] + letters[6:])
+
+
+# the reference's character table (primitives/__init__.py:6-13), restated: tab, space, the Cyrillic lower and upper case
+# alphabets, the digits, the Latin ones, ASCII punctuation.  The position of a character is its class in the Char net.
+CYRILLIC_LOWER, CYRILLIC_UPPER = _alphabet(0x430, '\u0451'), _alphabet(0x410, '\u0401')
+CHARS = '\t ' + CYRILLIC_LOWER + CYRILLIC_UPPER + string.digits + string.ascii_lowercase + string.ascii_uppercase + string.punctuation
+# the look-alike pairs (primitives/__init__.py:16-37) as positions in CHARS: (Cyrillic, Latin)
+SIMILAR_PAIRS = (
+    (2, 78), (7, 82), (17, 92), (19, 93), (20, 80), (22, 102), (24, 101),                      # a e o p c y x
+    (35, 104), (37, 105), (40, 108), (46, 114), (48, 116), (50, 118), (49, 111), (52, 119),    # A B E K M O H P
+    (53, 106), (54, 123), (57, 127))                                                           # C T X
+
+
+def pair_classes(pairs=SIMILAR_PAIRS, n_chars=len(CHARS)):
+    """cls[id] = the index of the pair that id belongs to, -1 for an id without a pair"""
+    cls = np.full(n_chars, -1, np.int32)
+    for index, pair in enumerate(pairs):
+        for char_id in pair:
+            assert cls[char_id] == -1, 'a character lies in one pair at most'
+            cls[char_id] = index
+    return cls
+
+
+def pred_to_text_rules(prediction, cls=None):
+    """PredToText._func1 (interpreter.py:596-614) restated: the ids emitted for one prediction (W, n_chars), as a list.
+    1. the maximum of every row; a row whose maximum == 0 (-0.0 too) contributes nothing
+    2. every column that equals its row's maximum is a candidate -- none in a row with a NaN --, by row, then by column
+    3. the walk: id 0 forgets the remembered id; an id whose pair holds the remembered id is skipped; every other id is
+       emitted and remembered
+    cls: the pair index of every id (default: the 18 pairs of CHARS)."""
+    prediction = np.asarray(prediction)
+    cls = pair_classes() if cls is None else np.asarray(cls)
+    with np.errstate(invalid='ignore'):
+        maxima = np.max(prediction, axis=1)
+        candidates = (prediction == maxima[:, None]) & (maxima != 0.0)[:, None]
+    emitted, remembered = [], None
+    for _, char_id in np.argwhere(candidates).tolist():
+        if char_id == 0:
+            remembered = None
+        elif remembered is None or cls[char_id] < 0 or cls[remembered] != cls[char_id]:
+            emitted.append(char_id)
+            remembered = char_id
+    return emitted
+
+
+def adjacent_rule(candidates, cls):
+    """what the device evaluates instead of the walk: candidate i is emitted iff it is not the tab and not (paired, with
+    a candidate before it that is not the tab and lies in the same pair)"""
+    s = list(candidates)
+    return [cur for i, cur in enumerate(s)
+            if cur != 0 and not (cls[cur] >= 0 and i > 0 and s[i - 1] != 0 and cls[s[i - 1]] == cls[cur])]
+
+
+class PredToText:
+    def __init__(self, chars=CHARS, pairs=SIMILAR_PAIRS):
+        self.chars, self.cls = chars, pair_classes(pairs, len(chars))
+
+    def __call__(self, predictions):
+        """predictions[paragraph][line]: (W, n_chars) DeviceArrays, the Char net's raw output.  Returns the text of every
+        line as a str in the same nesting (a paragraph without lines stays [], a page without paragraphs []); one kernel
+        call for the page, two when a row holds a tie."""
+        flat = [ops.as_device(line) for paragraph in predictions for line in paragraph]
+        texts = iter(''.join(self.chars[i] for i in ids) for ids in ops.pred_to_text(flat, self.cls))
+        return [[next(texts) for _ in paragraph] for paragraph in predictions]

@@ -9,12 +9,13 @@ channel counts, kernel sizes and losses, so `model_weights.json` files are inter
               dense 512->1024->128->162, softmax cross-entropy                     (:250-304)
 
 Every conv carries L2(0.01) (model.py:36-39).  Of the stages that sit between the nets in the
-reference's model system (host code, interpreter/), ParagraphCrop, LineCrop and CharLabel run on the device
+reference's model system (host code, interpreter/), ParagraphCrop, LineCrop, CharLabel and PredToText run on the device
 (my_model/crop.py): TRAIN_LINE is `make_model_system(mode=Modes.TRAIN_LINE)`, and `make_train_char_system` assembles
 [ParagraphCrop, LineCrop, CharLabel, Char], the reference's TRAIN_CHAR system.  Both take `find_rotation=True` for the
 reference's default ParagraphCrop, the one with the rotation search (CropAndRotateParagraphs); their own default stays
-the upright crop.  PredToText has no device form yet, and `make_model_system` says so for the mode that needs it; the
-TRAIN_CHAR and TRAIN_ALL members of `Modes` are not routed to the new system yet and say where it is.
+the upright crop.  `make_predict_system` chains the four nets through the device stages -- a page goes in, text comes
+out (my_model/predict.py) -- with the rotation search on, as the reference has it in that mode.  The PREDICT,
+TRAIN_CHAR and TRAIN_ALL members of `Modes` are not routed through `make_model_system` and say where their systems are.
 """
 from enum import Enum
 
@@ -216,6 +217,26 @@ def make_char_label_component(progress_tracker=None, source='cropped_2_char', ta
     return RawFunctionComponent(char_label)
 
 
+def make_pred_to_text_component(progress_tracker=None, source='char_pred', target='text', lines=None):
+    """model.py:647-656 (make_pred_to_text_component) without its move component: the nested list
+    context[source][paragraph][line] of the Char net's raw outputs becomes context[target][paragraph][line], the text of
+    every line as a str, in one kernel call for the page (my_model/crop.py: PredToText); only the ids visit the host.
+    A page without a line never reaches the Char net, so context[source] is missing there: the text is [].  lines: the
+    label of the nested list of line crops the predictions were made from -- the text then has one entry per paragraph
+    of context[lines], [] for the paragraphs without lines at the end of the page, which a CharSelector never files."""
+    from .crop import PredToText
+    pred_to_text = PredToText()
+
+    @track_function('PredToText', 'forward', progress_tracker)
+    def to_text(context):
+        predictions = list(context.get(source, []))
+        if lines is not None:
+            predictions += [[] for _ in range(len(context[lines]) - len(predictions))]
+        context[target] = pred_to_text(predictions)
+
+    return RawFunctionComponent(to_text)
+
+
 def make_paragraph_crop_component(find_rotation=False, progress_tracker=None, sources=('monochrome_pred', 'line'),
                                   targets=('cropped_monochrome', 'cropped_line')):
     """model.py:552-576 (make_paragraph_crop_component) as a device component: the stage labels context['paragraph_pred']
@@ -235,12 +256,13 @@ def make_paragraph_crop_component(find_rotation=False, progress_tracker=None, so
 
 
 def make_line_crop_component(progress_tracker=None, mask='cropped_line', sources=('cropped_monochrome', 'cropped_char'),
-                             targets=('cropped_2_monochrome', 'cropped_2_char')):
+                             targets=('cropped_2_monochrome', 'cropped_2_char'), empty_page_ok=False):
     """model.py:595-612 (make_line_crop_component) as a device component: context[mask][paragraph] is the paragraph's
     (1, H, W, 2) line mask (the reference reads it as `line_pred_cpu`, in TRAIN_CHAR the renamed `cropped_line_cpu`,
     :635-637), context[source][paragraph] a companion array; context[target][paragraph][line] becomes the line cut out
     of it, turned upright, zoomed to CHAR_INPUT_HEIGHT rows and padded to CHAR_FIXED_WIDTH columns
-    (my_model/crop.py: CropLines).  One kernel call for the page; the host reads the component tables only."""
+    (my_model/crop.py: CropLines).  One kernel call for the page; the host reads the component tables only.
+    empty_page_ok: a missing context[mask] is a page without paragraphs (a LineSelector that met none files nothing)."""
     from .crop import CropLines
     crop_lines = CropLines(CHAR_INPUT_HEIGHT, CHAR_FIXED_WIDTH)
     if len(sources) != len(targets):
@@ -248,7 +270,8 @@ def make_line_crop_component(progress_tracker=None, mask='cropped_line', sources
 
     @track_function('LineCrop', 'forward', progress_tracker)
     def line_crop(context):
-        context.update(zip(targets, crop_lines(context[mask], [context[source] for source in sources])))
+        masks = context.get(mask, []) if empty_page_ok else context[mask]
+        context.update(zip(targets, crop_lines(masks, [context[source] for source in sources])))
 
     return RawFunctionComponent(line_crop)
 
@@ -324,7 +347,7 @@ _MISSING_STAGE = {
                   'make_train_char_context_maker',
     'TRAIN_ALL': 'the nets have not been chained through the device ParagraphCrop / LineCrop / CharLabel stages yet '
                  '(TRAIN_CHAR alone is make_train_char_system)',
-    'PREDICT': 'PredToText (the rotation search of ParagraphCrop is my_model/crop.py: CropAndRotateParagraphs)',
+    'PREDICT': 'the system that ends in PredToText is built by make_predict_system (my_model/predict.py runs it)',
 }
 
 
@@ -438,3 +461,39 @@ def make_train_char_system(input_shape, optimizer=None, progress_tracker=None, w
     components = [paragraph_crop, make_line_crop_component(progress_tracker),
                   make_char_label_component(progress_tracker), char]
     return ModelSystem(components), {'Char': model}, ['ParagraphCrop', 'LineCrop', 'CharLabel', 'Char']
+
+
+def make_predict_system(input_shape, progress_tracker=None, weights=None, find_rotation=True):
+    """model.py:688-717: the reference's PREDICT system without its rename and move components -- a page goes in as
+    context['monochrome_X'] (1, H, W, 1), H and W multiples of 16 (make_divisible_by), and context['text'][p][l] comes
+    out.  No array visits the host between the stages: only the component tables, the probe extents of the rotation
+    search and the final ids are read back.  Returns (model_system, models, names), names = ['Monochrome', 'Paragraph',
+    'ParagraphCrop', 'Line', 'LineCrop', 'Char', 'PredToText'].
+      Monochrome     monochrome_X -> monochrome_pred
+      Paragraph      reads monochrome_pred (the reference renames it to paragraph_X) -> paragraph_pred
+      ParagraphCrop  labels paragraph_pred, cuts monochrome_pred to every paragraph, turned by the angle of its rotation
+                     search (find_rotation=True, the reference's default in this mode), in make_divisible_by's frame:
+                     cropped_monochrome[p]
+      Line           one pass per paragraph through a LineSelector -> line_pred[p]
+      LineCrop       finds the lines of every paragraph in line_pred and cuts them out of cropped_monochrome:
+                     cropped_2_monochrome[p][l]
+      Char           one pass per line through a CharSelector -> char_pred[p][l]
+      PredToText     text[p][l] from char_pred
+    The nets are built for input_shape and take every size they meet afterwards (crops are multiples of 16, lines 32
+    rows high and at least 8 columns wide)."""
+    models = {name: _make_net(name, shape, None, progress_tracker, weights)
+              for name, shape in (('Monochrome', input_shape), ('Paragraph', input_shape), ('Line', input_shape),
+                                  ('Char', (input_shape[0], CHAR_INPUT_HEIGHT, 64, 1)))}
+    selectors = {'Monochrome': StringSelector('monochrome_X', None, 'monochrome_pred'),
+                 'Paragraph': StringSelector('monochrome_pred', None, 'paragraph_pred'),
+                 'Line': LineSelector('cropped_monochrome', None, 'line_pred'),
+                 'Char': CharSelector('cropped_2_monochrome', None, 'char_pred')}
+    net = {name: ModelComponent(name, models[name], selectors[name], delist_result=True) for name in models}
+    components = [net['Monochrome'], net['Paragraph'],
+                  make_paragraph_crop_component(find_rotation, progress_tracker, ('monochrome_pred',), ('cropped_monochrome',)),
+                  net['Line'],
+                  make_line_crop_component(progress_tracker, 'line_pred', ('cropped_monochrome',), ('cropped_2_monochrome',),
+                                           empty_page_ok=True),
+                  net['Char'], make_pred_to_text_component(progress_tracker, lines='cropped_2_monochrome')]
+    return (ModelSystem(components), models,
+            ['Monochrome', 'Paragraph', 'ParagraphCrop', 'Line', 'LineCrop', 'Char', 'PredToText'])

@@ -721,6 +721,49 @@ def char_label(lines, bits, n_chars, want_ids=False):
     return (labels, ids) if want_ids else labels
 
 
+# ---- text of the lines (interpreter/interpreter.py:574-614: PredToText) ------------------------------------------------
+def _pred_to_text_call(lines, cls, caps):
+    """ONE uocr_pred_to_text call and ONE device-to-host copy: the counts sit at the head of the buffer the ids follow
+    in.  Returns (counts, [the first min(count, cap) ids of every line])."""
+    n = len(lines)
+    starts = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64) + 4 * n
+    out = CP.empty((int(starts[-1]),), np.uint8)
+    address = lambda offsets: (C.c_void_p * n)(*[out.ptr + int(o) for o in offsets])
+    _rt().call('uocr_pred_to_text', _shared_code(lines, 'pred_to_text', 'a dtype'), n, _pointers(lines),
+               _ints([a.shape[0] for a in lines]), int(lines[0].shape[1]), _ints(cls), address(starts[:-1]), _ints(caps),
+               address(4 * np.arange(n)))
+    host = out.numpy()
+    counts = host[:4 * n].view(np.int32)
+    return counts, [host[s:s + min(int(c), cap)] for s, c, cap in zip(starts, counts, caps)]
+
+
+def pred_to_text(lines, cls):
+    """PredToText._func1 (interpreter.py:596-614) up to the character table: the ids the reference's walk emits for every
+    line of `lines`, a flat list of (W, n_chars) DeviceArrays (the Char net's raw output), as one list of ints per line.
+    cls[id] is the index of the id's pair of similar characters, -1 for an id without one.  ONE uocr_pred_to_text call
+    for all lines with room for one id per row -- exact whenever no row holds a tie -- and ONE device-to-host copy; the
+    lines that emitted more (rows with ties) are repeated in ONE second call with the room their counts ask for.  No
+    call for an empty list."""
+    lines = list(lines)
+    for a in lines:
+        if not isinstance(a, DeviceArray) or a.ndim != 2 or a.shape[0] < 1:
+            raise ValueError(f'pred_to_text: expected (W, n_chars) device arrays, got {getattr(a, "shape", type(a))}')
+    if not lines:
+        return []
+    cls = [int(v) for v in cls]
+    if any(a.shape[1] != len(cls) for a in lines):
+        raise ValueError(f'pred_to_text: {len(cls)} classes, but the lines are ' + ', '.join(str(a.shape) for a in lines))
+    caps = [a.shape[0] for a in lines]
+    counts, ids = _pred_to_text_call(lines, cls, caps)
+    longer = [i for i, (count, cap) in enumerate(zip(counts, caps)) if count > cap]
+    if longer:
+        again, full = _pred_to_text_call([lines[i] for i in longer], cls, [int(counts[i]) for i in longer])
+        assert all(again[k] == counts[i] for k, i in enumerate(longer))
+        for k, i in enumerate(longer):
+            ids[i] = full[k]
+    return [v.tolist() for v in ids]
+
+
 # ---- line crops (interpreter/interpreter.py:504-523: the gather half of LineCrop) -------------------------------------
 def line_crop_shape(box_h, box_w, quarter_turns, zoomed_height=32, minimal_width=8):
     """(zoom_h, zoom_w, out_w) of a box_h x box_w box after `quarter_turns` turns of 90 degrees, ndimage.zoom by
