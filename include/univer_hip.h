@@ -492,6 +492,35 @@ int uocr_rotate_crop(uocr_ctx* ctx, int dtype, int n_entries, const void* const*
  * block of an entry, probes / entries per launch, kernels launched (all 0 before the first call) -- tests size their
  * inputs from it */
 int uocr_ctx_last_rotate(uocr_ctx* ctx, int* rows_per_band, int* pixels_per_block, int* entries_per_launch, int* launches);
+/* The whole angle search of CropAndRotateSingleParagraph._func (:321-336) for ALL paragraphs of a page in one call,
+ * without a host step between its rounds.  The search tree does not depend on the data: node 0 is (low, high) = (0, 180),
+ * a node probes a = low + (high - low) / 3 and b = high - (high - low) / 3, child 2j + 1 is the branch height_a < height_b
+ * (high = b), child 2j + 2 the other (low = a).  table: DEVICE float64 (2^rounds - 1, 4), per node cos a, sin a, cos b,
+ * sin b in heap order (nn/ops.py: search_table); the device never evaluates a cosine.  Per round and paragraph the two
+ * probes are evaluated as uocr_rotated_extent evaluates them, except that the DEVICE computes the rotated plane and the
+ * offset from the box and (c, s) -- in float64, every product and sum rounded on its own:
+ *   row0 = {0, s*cw, c*ch, c*ch + s*cw}, row1 = {0, c*cw, (-s)*ch, (-s)*ch + c*cw},
+ *   out_h = int((max row0 - min row0) + 0.5), out_w likewise from row1, hy = (out_h - 1) / 2, hx = (out_w - 1) / 2,
+ *   offset = {(ch - 1) / 2 - (c*hy + s*hx), (cw - 1) / 2 - ((-s)*hy + c*hx)}, M = {c, s, -s, c}
+ * (nn/ops.py: search_geometry; scipy's own matrix products may fuse a multiply-add and differ from it by some 1e-13 in
+ * the offset).  The height of a probe is y1 - y0 of its extent, 0 when no pixel is set (then low = a).
+ * labels, n, h, w, image_index as above; label_id (n_paragraphs) and box (4 ints per paragraph: y0, x0, ch, cw) are HOST
+ * arrays.  result: DEVICE int32 (n_paragraphs, 1 + 2 * rounds): the LEAF the paragraph ends on -- the heap index
+ * below node 0 after `rounds` decisions, 2^rounds - 1 <= leaf <= 2^(rounds + 1) - 2; the host replays the decisions for the
+ * angle -- then height_a, height_b of every round.  workspace: DEVICE, uocr_rotation_search_workspace bytes, the call
+ * zeroes it.  UOCR_ERR_ARG for null pointers, pointers off their element's alignment, n, h, w < 1, image_index outside
+ * [0, n), rounds outside 1..16, label_id < 1, a box that is empty or not inside the image and n_paragraphs < 0;
+ * UOCR_ERR_UNSUPPORTED for more blocks than one grid takes; nothing is written on any error; n_paragraphs = 0 is UOCR_OK
+ * and launches nothing.  One zero fill, then two kernels per round and 14 paragraphs, all enqueued by this call in
+ * stream order: no host synchronisation, no spinning, no cooperative launch.  Vector integer atomics only:
+ * bit-identical run to run.  Asynchronous and capturable. */
+int uocr_rotation_search(uocr_ctx* ctx, const int* labels, int n, int h, int w, int image_index, int n_paragraphs,
+                         const int* label_id, const int* box, int rounds, const double* table, int* result, int* workspace);
+/* bytes of the workspace of a uocr_rotation_search call on n_paragraphs paragraphs */
+int uocr_rotation_search_workspace(int n_paragraphs, size_t* bytes);
+/* what the last uocr_rotation_search call on this ctx used: rounds, paragraphs per launch, kernels launched (all 0 before
+ * the first call) -- tests size their inputs from it */
+int uocr_ctx_last_rotation_search(uocr_ctx* ctx, int* rounds, int* paragraphs_per_launch, int* launches);
 
 /* ---- text of the lines (interpreter/interpreter.py:574-614 PredToText._func1: the PredToText stage) ----------------
  * The character ids of ALL lines of a page in one call (the reference hands every line to a worker pool after a

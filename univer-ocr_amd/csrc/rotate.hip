@@ -21,6 +21,15 @@
 //                  a region of the rotated plane and centred in make_divisible_by's zero frame, one thread per output
 //                  pixel looping over the channels (NHWC stores of neighbouring threads are contiguous).  Coordinates,
 //                  weights and the sum are float64 for every dtype; the result is rounded once.
+// rotation_search   the whole ternary search of interpreter.py:321-336 without the host: the tree of (low, high)
+//                  intervals does not depend on the data, so the host tabulates cos a, sin a, cos b, sin b of every node
+//                  once (nn/ops.py: search_table) and the device walks the tree.  A round is two launches: search_probe
+//                  is rotated_extent for the two probes of every paragraph, with the paragraph's current NODE read from
+//                  the workspace, the geometry of the rotated plane evaluated by every block for itself (rs_geometry:
+//                  nn/ops.py: search_geometry bit for bit, identical in all blocks of a probe) and only the row range
+//                  kept; search_decide turns the ranges into the round's two heights, moves every paragraph to a child
+//                  node and clears the ranges.  The host cannot know a probe's rows and sizes the grid by their bound;
+//                  blocks past the plane return.  All rounds are enqueued back to back: plain stream order, nothing spins.
 // All probes / entries of a call travel together, RT_ENTRIES per launch, in a by-value kernel argument (no device
 // allocation, no host synchronisation: asynchronous and capturable).  Integer atomics only: bit-identical run to run.
 // hipcc-flags: -ffp-contract=off
@@ -58,7 +67,25 @@ struct RCBatch {
     int block_first[RT_ENTRIES + 1];
     int n;
 };
-static_assert(sizeof(RTBatch) <= 4096 && sizeof(RCBatch) <= 4096, "the descriptor travels as a kernel argument");
+constexpr int RS_PARAGRAPHS = RT_ENTRIES / 2;   // rotation_search: paragraphs per launch, two probes each
+constexpr int RS_MAX_ROUNDS = 16;
+constexpr int RS_STATE = 5;                     // workspace ints per paragraph: node, then (top - first row, last row + 1) of a and b
+constexpr int RS_TOP = 1 << 30;                 // lower ends are stored as RS_TOP - index: zero = nothing set
+struct RSParagraph {
+    const int* lab;                 // label of the box's first pixel
+    int id, ch, cw;
+};
+struct RSBatch {
+    RSParagraph par[RS_PARAGRAPHS];
+    int block_first[2 * RS_PARAGRAPHS + 1];   // first block of probe i = 2 * paragraph + (0: a, 1: b)
+    int n;                          // paragraphs of this launch
+    int pitch, round, stride;       // row pitch of the labels; the round; ints per paragraph in the result
+    const double* table;            // four doubles per node: cos a, sin a, cos b, sin b
+    int* state;                     // RS_STATE ints per paragraph of this launch
+    int* result;                    // per paragraph of this launch: leaf, then height_a, height_b of every round
+};
+static_assert(sizeof(RTBatch) <= 4096 && sizeof(RCBatch) <= 4096 && sizeof(RSBatch) <= 4096,
+              "the descriptor travels as a kernel argument");
 
 // (offset + oy * m0) + ox * m1, each operation rounded on its own
 __device__ __forceinline__ double rt_coord(double off, double m0, double m1, int oy, int ox) {
@@ -108,6 +135,68 @@ __global__ void rotated_extent_finish(const RTBatch b) {
     if (i >= b.n) return;
     int* e = b.extent + 4 * i;
     if (e[1] > 0) e[0] = b.probe[i].out_h - e[0], e[2] = b.probe[i].out_w - e[2];    // (else all four are 0 already)
+}
+
+// nn/ops.py: search_geometry, operation by operation: the shape of the rotated plane of an ih x iw box and the offset
+struct RSGeometry { double off[2]; int out_h, out_w; };
+__device__ __forceinline__ double rs_ptp(double p1, double p2) {       // max - min over (0, p1, p2, p2 + p1)
+    const double p3 = __dadd_rn(p2, p1);
+    return __dadd_rn(fmax(fmax(0.0, p1), fmax(p2, p3)), -fmin(fmin(0.0, p1), fmin(p2, p3)));
+}
+__device__ __forceinline__ RSGeometry rs_geometry(int ch, int cw, double c, double s) {
+    const double ih = (double)ch, iw = (double)cw, ns = -s;
+    RSGeometry g;
+    g.out_h = (int)__dadd_rn(rs_ptp(__dmul_rn(s, iw), __dmul_rn(c, ih)), 0.5);
+    g.out_w = (int)__dadd_rn(rs_ptp(__dmul_rn(c, iw), __dmul_rn(ns, ih)), 0.5);
+    const double hy = (double)(g.out_h - 1) / 2.0, hx = (double)(g.out_w - 1) / 2.0;
+    g.off[0] = __dadd_rn((double)(ch - 1) / 2.0, -__dadd_rn(__dmul_rn(c, hy), __dmul_rn(s, hx)));
+    g.off[1] = __dadd_rn((double)(cw - 1) / 2.0, -__dadd_rn(__dmul_rn(ns, hy), __dmul_rn(c, hx)));
+    return g;
+}
+
+__global__ __launch_bounds__(RT_NT) void search_probe(const RSBatch b) {
+    const int i = eb_entry_of(b.block_first, 2 * b.n, blockIdx.x);
+    const RSParagraph& p = b.par[i >> 1];
+    int* state = b.state + RS_STATE * (i >> 1);
+    const double* t = b.table + 4 * (size_t)state[0] + 2 * (i & 1);   // (the node: below 2^round - 1 rows of the table)
+    const double c = t[0], s = t[1];
+    const RSGeometry g = rs_geometry(p.ch, p.cw, c, s);
+    const int row0 = (blockIdx.x - b.block_first[i]) * RT_BAND;
+    if (row0 >= g.out_h) return;                                       // (the grid holds the bound of out_h)
+    const int rows = g.out_h - row0 < RT_BAND ? g.out_h - row0 : RT_BAND;
+    const int segs = (g.out_w + 63) / 64;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int y_lo = INT32_MAX, y_hi = -1;                                   // (wave-uniform)
+    for (int item = wave; item < rows * segs; item += RT_NT / 64) {
+        const int oy = row0 + item / segs, ox = (item % segs) * 64 + lane;
+        bool set = false;                                              // (the pixel test of rotated_extent, which stays as it is)
+        if (ox < g.out_w) {
+            const double cy = rt_coord(g.off[0], c, s, oy, ox), cx = rt_coord(g.off[1], -s, c, oy, ox);
+            if (rt_inside(cy, p.ch) && rt_inside(cx, p.cw)) {
+                int sy = (int)__dadd_rn(cy, 0.5), sx = (int)__dadd_rn(cx, 0.5);   // (>= 0: the conversion is the floor)
+                sy = sy < p.ch ? sy : p.ch - 1, sx = sx < p.cw ? sx : p.cw - 1;   // (never taken: n - 1 + 0.5 floors to n - 1)
+                set = p.lab[(size_t)sy * b.pitch + sx] == p.id;
+            }
+        }
+        if (__ballot(set)) y_lo = oy < y_lo ? oy : y_lo, y_hi = oy > y_hi ? oy : y_hi;
+    }
+    if (lane == 0 && y_hi >= 0) {
+        int* e = state + 1 + 2 * (i & 1);
+        atomicMax(e + 0, RS_TOP - y_lo);
+        atomicMax(e + 1, y_hi + 1);
+    }
+}
+
+__global__ void search_decide(const RSBatch b) {
+    const int i = threadIdx.x;
+    if (i >= b.n) return;
+    int* state = b.state + RS_STATE * i;
+    int* result = b.result + (size_t)b.stride * i;
+    const int height_a = state[2] > 0 ? state[2] - (RS_TOP - state[1]) : 0;
+    const int height_b = state[4] > 0 ? state[4] - (RS_TOP - state[3]) : 0;
+    result[1 + 2 * b.round] = height_a, result[2 + 2 * b.round] = height_b;
+    state[0] = result[0] = 2 * state[0] + (height_a < height_b ? 1 : 2);   // (after the last round: the leaf)
+    state[1] = state[2] = state[3] = state[4] = 0;
 }
 
 template <typename T>
@@ -281,6 +370,76 @@ int uocr_rotate_crop(uocr_ctx* ctx, int dtype, int n_entries, const void* const*
         launches += 1;
     }
     ctx->rt_band = RT_BAND, ctx->rt_block = RT_NT, ctx->rt_entries = RT_ENTRIES, ctx->rt_launches = launches;
+    return UOCR_OK;
+}
+
+int uocr_rotation_search_workspace(int n_paragraphs, size_t* bytes) {
+    if (n_paragraphs < 0 || !bytes) return UOCR_ERR_ARG;
+    *bytes = (size_t)n_paragraphs * RS_STATE * sizeof(int);
+    return UOCR_OK;
+}
+
+int uocr_rotation_search(uocr_ctx* ctx, const int* labels, int n, int h, int w, int image_index, int n_paragraphs,
+                         const int* label_id, const int* box, int rounds, const double* table, int* result, int* workspace) {
+    UOCR_CHECK_CTX(ctx);
+    UOCR_REQUIRE(ctx, n_paragraphs >= 0);
+    if (n_paragraphs == 0) return UOCR_OK;                         // nothing to do, whatever else was passed
+    UOCR_REQUIRE(ctx, labels && label_id && box && table && result && workspace);
+    UOCR_REQUIRE(ctx, n >= 1 && h >= 1 && w >= 1 && image_index >= 0 && image_index < n);
+    UOCR_REQUIRE(ctx, rounds >= 1 && rounds <= RS_MAX_ROUNDS);
+    UOCR_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(result) | reinterpret_cast<uintptr_t>(workspace)) % sizeof(int) == 0);
+    UOCR_REQUIRE(ctx, reinterpret_cast<uintptr_t>(table) % sizeof(double) == 0);
+    if ((long long)h * w > INT32_MAX) UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "image of %d x %d pixels: linear indices must fit int32", h, w);
+    // everything is checked before the first launch: an error leaves the result as it was.  A probe's rows are known to
+    // the device alone; out_h = int(ptp + 0.5) with ptp <= |c| h + |s| w <= hypot(h, w) is at most int(hypot) + 1
+    const auto blocks = [&](int i) {
+        const int* bx = box + 4 * (i >> 1);
+        return ((int)hypot((double)bx[2], (double)bx[3]) + 2 + RT_BAND - 1) / RT_BAND;
+    };
+    for (int first = 0; first < n_paragraphs; first += RS_PARAGRAPHS) {
+        const int count = eb_group_size(n_paragraphs, first, RS_PARAGRAPHS);
+        for (int i = first; i < first + count; ++i) {
+            UOCR_REQUIRE(ctx, label_id[i] >= 1);
+            UOCR_REQUIRE(ctx, rt_box_inside(box + 4 * i, h, w));
+        }
+        if (eb_group_blocks(2 * first, 2 * count, blocks) < 0)
+            UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "paragraphs %d..: too many blocks for one grid", first);
+    }
+    UOCR_HIP(ctx, hipMemsetAsync(workspace, 0, (size_t)n_paragraphs * RS_STATE * sizeof(int), ctx->stream));   // node 0, nothing set
+    const int* lab = labels + (size_t)image_index * h * w;
+    int launches = 0;
+    for (int first = 0; first < n_paragraphs; first += RS_PARAGRAPHS) {
+        RSBatch b;
+        memset(&b, 0, sizeof(b));
+        b.n = eb_group_size(n_paragraphs, first, RS_PARAGRAPHS);
+        eb_block_first(2 * first, 2 * b.n, b.block_first, blocks);
+        b.pitch = w, b.stride = 1 + 2 * rounds, b.table = table;
+        b.state = workspace + (size_t)RS_STATE * first;
+        b.result = result + (size_t)b.stride * first;
+        for (int i = 0; i < b.n; ++i) {
+            const int s = first + i;
+            RSParagraph& p = b.par[i];
+            p.lab = lab + (size_t)box[4 * s] * w + box[4 * s + 1];
+            p.id = label_id[s], p.ch = box[4 * s + 2], p.cw = box[4 * s + 3];
+        }
+        for (b.round = 0; b.round < rounds; ++b.round) {
+            hipLaunchKernelGGL(search_probe, dim3((unsigned)b.block_first[2 * b.n]), dim3(RT_NT), 0, ctx->stream, b);
+            UOCR_LAUNCH_CHECK(ctx);
+            hipLaunchKernelGGL(search_decide, dim3(1), dim3(64), 0, ctx->stream, b);
+            UOCR_LAUNCH_CHECK(ctx);
+            launches += 2;
+        }
+    }
+    ctx->rs_rounds = rounds, ctx->rs_paragraphs = RS_PARAGRAPHS, ctx->rs_launches = launches;
+    return UOCR_OK;
+}
+
+int uocr_ctx_last_rotation_search(uocr_ctx* ctx, int* rounds, int* paragraphs_per_launch, int* launches) {
+    UOCR_CHECK_CTX(ctx);
+    UOCR_REQUIRE(ctx, rounds && paragraphs_per_launch && launches);
+    *rounds = ctx->rs_rounds;
+    *paragraphs_per_launch = ctx->rs_paragraphs;
+    *launches = ctx->rs_launches;
     return UOCR_OK;
 }
 

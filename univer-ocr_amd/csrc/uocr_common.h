@@ -52,6 +52,7 @@ struct uocr_ctx {
     int cl_cols, cl_chunk, cl_lines, cl_launches; // uocr_ctx_last_char_label: sizes and launch count of the last char-label call
     int lc_chunk, lc_vec_bytes, lc_entries, lc_launches;   // uocr_ctx_last_line_crop: sizes and launch count of the last line-crop call
     int rt_band, rt_block, rt_entries, rt_launches;        // uocr_ctx_last_rotate: sizes and launch count of the last rotation call
+    int rs_rounds, rs_paragraphs, rs_launches;             // uocr_ctx_last_rotation_search: rounds, paragraphs per launch and launch count of the last search
     int pt_rows, pt_lines, pt_launches;                    // uocr_ctx_last_pred_to_text: sizes and launch count of the last pred-to-text call
     char err[512];
 };

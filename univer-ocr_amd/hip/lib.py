@@ -136,6 +136,9 @@ _PROTOS = {
     'uocr_rotate_crop': [_ctx, _i, _i, C.POINTER(_vp), C.POINTER(_vp)] + [C.POINTER(_i)] * 4 + [C.POINTER(_d)] * 2 +
                         [C.POINTER(_i)] * 2 + [C.POINTER(_vp), C.POINTER(_i)],
     'uocr_ctx_last_rotate': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
+    'uocr_rotation_search': [_ctx, _vp, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _i, _vp, _vp, _vp],
+    'uocr_rotation_search_workspace': [_i, C.POINTER(_sz)],
+    'uocr_ctx_last_rotation_search': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     'uocr_pred_to_text': [_ctx, _i, _i, C.POINTER(_vp), C.POINTER(_i), _i, C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i),
                           C.POINTER(_vp)],
     'uocr_ctx_last_pred_to_text': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],

@@ -18,7 +18,10 @@ lock step, so a round is ONE call holding both probes of every paragraph, one mo
 angles, and ONE rotate_crop call produces all arrays of all rotated paragraphs, make_divisible_by's frame included: 14
 extent calls and 1 crop call per page, whatever the number of paragraphs, 16 bytes read back per probe.  The geometry
 (matrix, offset, shape of the rotated plane) is computed on the host as scipy computes it (nn/ops.py:
-rotation_geometry).  Unrotated paragraphs go through masked_crop as in CropParagraphs.
+rotation_geometry).  Unrotated paragraphs go through masked_crop as in CropParagraphs.  search='device' hands the 13
+rounds to the device (nn/ops.py: rotation_search): the search tree does not depend on the data, so every angle it can
+visit is tabulated once and the device walks it for all paragraphs, round after round in stream order -- 1 search call
+with 1 readback, 1 extent call and 1 crop call per page.  The default stays the host search.
 
 LabelChars is the reference's LabelChar (interpreter/interpreter.py:524-571): the `char` layer tag of every cropped line
 -- bit layers first, then letter_spacing -- becomes the (W, N_CHARS) one-hot labels the Char net trains on.  Per line:
@@ -163,8 +166,17 @@ def search_angle(height_of, eps=1.0):
 
 
 class CropAndRotateParagraphs:
-    def __init__(self, find_rotation=True, eps=1.0, max_components=4096):
-        self.find_rotation, self.eps, self.max_components = find_rotation, eps, max_components
+    def __init__(self, find_rotation=True, eps=1.0, max_components=4096, search='host'):
+        """search: 'host' walks the rounds on the host (find_angles), 'device' leaves them to ONE rotation_search call;
+        an eps whose tree the device cannot walk (nn/ops.py: search_table) keeps to the host search."""
+        if search not in ('host', 'device'):
+            raise ValueError(f"CropAndRotateParagraphs: search must be 'host' or 'device', got {search!r}")
+        self.find_rotation, self.eps, self.max_components, self.search = find_rotation, eps, max_components, search
+        if search == 'device' and find_rotation:
+            try:
+                ops.search_table(eps)
+            except ValueError:
+                self.search = 'host'
 
     def find_angles(self, components, paragraphs):
         """the reference's angle (degrees, or None) of paragraphs 1..`paragraphs` of image 0: all searches in lock step,
@@ -190,7 +202,12 @@ class CropAndRotateParagraphs:
         afterwards: degrees, or None for a paragraph cut upright).  A paragraph whose rotated mask has no set pixel --
         the reference raises there -- is cut upright too."""
         arrays, components, paragraphs = label_page('CropAndRotateParagraphs', mask, arrays, self.max_components)
-        angles = self.find_angles(components, paragraphs) if self.find_rotation else [None] * paragraphs
+        if not self.find_rotation or not paragraphs:
+            angles = [None] * paragraphs
+        elif self.search == 'device':
+            angles = list(ops.rotation_search(components, 0, range(1, paragraphs + 1), self.eps)[0])
+        else:
+            angles = self.find_angles(components, paragraphs)
         rotated = [p for p in range(paragraphs) if angles[p] is not None]
         regions = {}
         if rotated:

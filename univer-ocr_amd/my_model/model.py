@@ -13,8 +13,9 @@ reference's model system (host code, interpreter/), ParagraphCrop, LineCrop, Cha
 (my_model/crop.py): TRAIN_LINE is `make_model_system(mode=Modes.TRAIN_LINE)`, and `make_train_char_system` assembles
 [ParagraphCrop, LineCrop, CharLabel, Char], the reference's TRAIN_CHAR system.  Both take `find_rotation=True` for the
 reference's default ParagraphCrop, the one with the rotation search (CropAndRotateParagraphs); their own default stays
-the upright crop.  `make_predict_system` chains the four nets through the device stages -- a page goes in, text comes
-out (my_model/predict.py) -- with the rotation search on, as the reference has it in that mode.  The PREDICT,
+the upright crop; `rotation_search='device'` lets the device walk that search, one call per page.
+`make_predict_system` chains the four nets through the device stages -- a page goes in, text comes out
+(my_model/predict.py) -- with the rotation search on, as the reference has it in that mode.  The PREDICT,
 TRAIN_CHAR and TRAIN_ALL members of `Modes` are not routed through `make_model_system` and say where their systems are.
 """
 from enum import Enum
@@ -238,12 +239,14 @@ def make_pred_to_text_component(progress_tracker=None, source='char_pred', targe
 
 
 def make_paragraph_crop_component(find_rotation=False, progress_tracker=None, sources=('monochrome_pred', 'line'),
-                                  targets=('cropped_monochrome', 'cropped_line')):
+                                  targets=('cropped_monochrome', 'cropped_line'), rotation_search='host'):
     """model.py:552-576 (make_paragraph_crop_component) as a device component: the stage labels context['paragraph_pred']
     and cuts every context[source] to every paragraph, padded to multiples of 16: context[target][paragraph]
-    (my_model/crop.py: CropParagraphs; with find_rotation=True CropAndRotateParagraphs, the reference's default)."""
+    (my_model/crop.py: CropParagraphs; with find_rotation=True CropAndRotateParagraphs, the reference's default, whose
+    angle search walks its rounds on the host, or with rotation_search='device' in one call on the device)."""
     from .crop import CropAndRotateParagraphs, CropParagraphs
-    crop_paragraphs = CropAndRotateParagraphs(find_rotation=True) if find_rotation else CropParagraphs(find_rotation=False)
+    crop_paragraphs = (CropAndRotateParagraphs(find_rotation=True, search=rotation_search) if find_rotation
+                       else CropParagraphs(find_rotation=False))
     if len(sources) != len(targets):
         raise ValueError(f'make_paragraph_crop_component: {len(sources)} sources for {len(targets)} targets')
 
@@ -390,7 +393,7 @@ def make_context_maker(mode=Modes.PREDICT):
 
 
 def make_model_system(input_shape, optimizer=None, progress_tracker=None, weights=None, mode=Modes.PREDICT,
-                      char_input_shape=None, find_rotation=False):
+                      char_input_shape=None, find_rotation=False, rotation_search='host'):
     """model.py:486-717 for the device-resident modes.  Returns (model_system, models, names).
 
     TRAIN_LINE is the system [ParagraphCrop, Line] (names ['ParagraphCrop', 'Line']): the crop stage labels
@@ -400,9 +403,9 @@ def make_model_system(input_shape, optimizer=None, progress_tracker=None, weight
     TRAIN_LINE system (model.py:585-593) built with find_rotation=False, minus its move_to_gpu component: no array
     visits the host between the stages (the crop stage reads back the component table only).  find_rotation=True (TRAIN_LINE
     only) puts CropAndRotateParagraphs in the ParagraphCrop slot: the reference's default, every paragraph turned by the
-    angle of its rotation search."""
+    angle of its rotation search; rotation_search='device' lets the device walk that search (one call per page)."""
     if mode is Modes.TRAIN_LINE:
-        return _make_train_line_system(input_shape, optimizer, progress_tracker, weights, find_rotation)
+        return _make_train_line_system(input_shape, optimizer, progress_tracker, weights, find_rotation, rotation_search)
     if find_rotation:
         raise ValueError(f'find_rotation=True: {mode.name} has no ParagraphCrop stage')
     plan = {
@@ -427,11 +430,12 @@ def make_model_system(input_shape, optimizer=None, progress_tracker=None, weight
     return ModelSystem(components), models, list(plan[mode])
 
 
-def _make_train_line_system(input_shape, optimizer, progress_tracker, weights, find_rotation=False):
+def _make_train_line_system(input_shape, optimizer, progress_tracker, weights, find_rotation=False, rotation_search='host'):
     model = _make_net('Line', input_shape, optimizer, progress_tracker, weights)
     line = ModelComponent('Line', model, LineSelector('cropped_monochrome', 'cropped_line', 'line_pred'),
                           delist_result=True)
-    return (ModelSystem([make_paragraph_crop_component(find_rotation, progress_tracker), line]), {'Line': model},
+    paragraph_crop = make_paragraph_crop_component(find_rotation, progress_tracker, rotation_search=rotation_search)
+    return (ModelSystem([paragraph_crop, line]), {'Line': model},
             ['ParagraphCrop', 'Line'])
 
 
@@ -441,9 +445,11 @@ def make_train_char_context_maker():
     return _context_maker({'monochrome_pred': 'monochrome', 'paragraph_pred': 'paragraph', 'line': 'line', 'char': 'char'})
 
 
-def make_train_char_system(input_shape, optimizer=None, progress_tracker=None, weights=None, find_rotation=False):
+def make_train_char_system(input_shape, optimizer=None, progress_tracker=None, weights=None, find_rotation=False,
+                           rotation_search='host'):
     """model.py:632-645: the reference's TRAIN_CHAR system built with find_rotation=False (or, with find_rotation=True,
-    as the reference builds it: CropAndRotateParagraphs in the ParagraphCrop slot), minus its rename and move
+    as the reference builds it: CropAndRotateParagraphs in the ParagraphCrop slot, its angle search on the host or, with
+    rotation_search='device', on the device), minus its rename and move
     components -- no array visits the host between the stages.  Returns (model_system, {'Char': model},
     ['ParagraphCrop', 'LineCrop', 'CharLabel', 'Char']).
       ParagraphCrop  labels context['paragraph_pred'], cuts context['monochrome_pred'], ['line'] and ['char'] to every
@@ -454,7 +460,7 @@ def make_train_char_system(input_shape, optimizer=None, progress_tracker=None, w
       Char           one step per line through a CharSelector; predictions at context['char_pred'][p][l]
     input_shape is the Char net's, (batch, *, width, channels): its height is CHAR_INPUT_HEIGHT."""
     paragraph_crop = make_paragraph_crop_component(find_rotation, progress_tracker, ('monochrome_pred', 'line', 'char'),
-                                                   ('cropped_monochrome', 'cropped_line', 'cropped_char'))
+                                                   ('cropped_monochrome', 'cropped_line', 'cropped_char'), rotation_search)
     model = _make_net('Char', input_shape, optimizer, progress_tracker, weights)
     char = ModelComponent('Char', model, CharSelector('cropped_2_monochrome', 'char_labels', 'char_pred'),
                           delist_result=True)
@@ -463,7 +469,7 @@ def make_train_char_system(input_shape, optimizer=None, progress_tracker=None, w
     return ModelSystem(components), {'Char': model}, ['ParagraphCrop', 'LineCrop', 'CharLabel', 'Char']
 
 
-def make_predict_system(input_shape, progress_tracker=None, weights=None, find_rotation=True):
+def make_predict_system(input_shape, progress_tracker=None, weights=None, find_rotation=True, rotation_search='host'):
     """model.py:688-717: the reference's PREDICT system without its rename and move components -- a page goes in as
     context['monochrome_X'] (1, H, W, 1), H and W multiples of 16 (make_divisible_by), and context['text'][p][l] comes
     out.  No array visits the host between the stages: only the component tables, the probe extents of the rotation
@@ -480,7 +486,8 @@ def make_predict_system(input_shape, progress_tracker=None, weights=None, find_r
       Char           one pass per line through a CharSelector -> char_pred[p][l]
       PredToText     text[p][l] from char_pred
     The nets are built for input_shape and take every size they meet afterwards (crops are multiples of 16, lines 32
-    rows high and at least 8 columns wide)."""
+    rows high and at least 8 columns wide).  rotation_search: 'host' walks the 13 rounds of the angle search on the
+    host, a readback per round; 'device' makes it one call and one readback per page (my_model/crop.py)."""
     models = {name: _make_net(name, shape, None, progress_tracker, weights)
               for name, shape in (('Monochrome', input_shape), ('Paragraph', input_shape), ('Line', input_shape),
                                   ('Char', (input_shape[0], CHAR_INPUT_HEIGHT, 64, 1)))}
@@ -490,7 +497,8 @@ def make_predict_system(input_shape, progress_tracker=None, weights=None, find_r
                  'Char': CharSelector('cropped_2_monochrome', None, 'char_pred')}
     net = {name: ModelComponent(name, models[name], selectors[name], delist_result=True) for name in models}
     components = [net['Monochrome'], net['Paragraph'],
-                  make_paragraph_crop_component(find_rotation, progress_tracker, ('monochrome_pred',), ('cropped_monochrome',)),
+                  make_paragraph_crop_component(find_rotation, progress_tracker, ('monochrome_pred',), ('cropped_monochrome',),
+                                                rotation_search),
                   net['Line'],
                   make_line_crop_component(progress_tracker, 'line_pred', ('cropped_monochrome',), ('cropped_2_monochrome',),
                                            empty_page_ok=True),

@@ -204,6 +204,14 @@ class Runtime:
         self.call('uocr_ctx_last_rotate', *[C.byref(x) for x in v])
         return tuple(x.value for x in v)
 
+    def last_rotation_search(self):
+        """(rounds, paragraphs per launch, kernel launches) of the most recent uocr_rotation_search call on the current
+        lane (uocr_ctx_last_rotation_search); all 0 before the first."""
+        import ctypes as C
+        v = [C.c_int() for _ in range(3)]
+        self.call('uocr_ctx_last_rotation_search', *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
     def last_pred_to_text(self):
         """(rows of a line per block, lines per launch, kernel launches) of the most recent uocr_pred_to_text call on the
         current lane (uocr_ctx_last_pred_to_text); all 0 before the first."""

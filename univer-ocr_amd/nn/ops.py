@@ -696,6 +696,119 @@ def rotate_crop(entries, divisible_by=None):
     return outs
 
 
+# ---- the rotation search on the device (interpreter.py:321-336 walked by uocr_rotation_search) -------------------------
+SEARCH_MAX_ROUNDS = 16
+_search_tables = {}                  # eps -> (rounds, host table); (eps, device) -> the table on that device
+
+
+def search_table(eps=1.0):
+    """The tree of the ternary search of my_model/crop.py: search_steps, which does not depend on the data, in heap
+    order: node 0 is (low, high) = (0, 180), child 2j + 1 the branch height_a < height_b (high = b), child 2j + 2 the
+    other (low = a), a and b by search_steps' own expressions.  Returns (rounds, table): table float64 (2^rounds - 1, 4),
+    per node cos a, sin a, cos b, sin b -- each a scalar call of the expression rotation_geometry uses, so that a row
+    equals what rotation_geometry computes for the node's angles to the bit.  Built once per eps.  ValueError where the
+    device cannot walk the tree: root-to-leaf paths of different lengths, none, or more than SEARCH_MAX_ROUNDS rounds."""
+    eps = float(eps)
+    if eps not in _search_tables:
+        levels, level = [], [(0.0, 180.0)]
+        while True:
+            running = [high - low > eps for low, high in level]
+            if not any(running):
+                break
+            if not all(running):
+                raise ValueError(f'search_table: at eps = {eps} some searches end after {len(levels)} rounds and others go on')
+            if len(levels) == SEARCH_MAX_ROUNDS:
+                raise ValueError(f'search_table: the search at eps = {eps} takes more than {SEARCH_MAX_ROUNDS} rounds')
+            levels.append([(low + (high - low) / 3, high - (high - low) / 3) for low, high in level])
+            level = [child for (low, high), (a, b) in zip(level, levels[-1]) for child in ((low, b), (a, high))]
+        if not levels:
+            raise ValueError(f'search_table: the search at eps = {eps} makes no round')
+        table = np.array([[np.cos(np.deg2rad(a)), np.sin(np.deg2rad(a)), np.cos(np.deg2rad(b)), np.sin(np.deg2rad(b))]
+                          for probes in levels for a, b in probes], np.float64)
+        table.setflags(write=False)
+        _search_tables[eps] = len(levels), table
+    return _search_tables[eps]
+
+
+def search_path(leaf, eps=1.0):
+    """search_steps replayed with the decisions in a leaf's heap index (from the top: a 0 bit of leaf + 1 after the
+    leading one is height_a < height_b): the probes [(a, b)] of every round and the angle, None outside
+    [eps, 180 - eps]"""
+    low, high, probes = 0.0, 180.0, []
+    for decision in bin(int(leaf) + 1)[3:]:
+        if not high - low > eps:
+            raise ValueError(f'search_path: {leaf} lies below a leaf of the tree at eps = {eps}')
+        a = low + (high - low) / 3
+        b = high - (high - low) / 3
+        probes.append((a, b))
+        if decision == '0':
+            high = b
+        else:
+            low = a
+    if int(leaf) < 0 or high - low > eps:
+        raise ValueError(f'search_path: {leaf} is no leaf of the tree at eps = {eps}')
+    angle = (high + low) / 2
+    return probes, (angle if eps <= angle <= 180.0 - eps else None)
+
+
+def angle_of_leaf(leaf, eps=1.0):
+    """the angle search_steps returns after the decisions in the leaf's heap index: degrees, or None"""
+    return search_path(leaf, eps)[1]
+
+
+def search_geometry(ih, iw, c, s):
+    """rotation_geometry as the DEVICE evaluates it during the search, from the cosine and sine of the table: plain
+    Python floats, every product and sum rounded on its own, in this order -- the definition csrc/rotate.hip:
+    rs_geometry matches bit for bit.  Returns (M, offset, out_shape) as flat tuples: M = (c, s, -s, c).
+    rotation_geometry's `M @ ..` goes through NumPy's matrix product, which may fuse a multiply-add: the shapes agree, the
+    offsets to some 1e-13 (tests/test_rotation_search_host.py)."""
+    ih, iw, c, s = int(ih), int(iw), float(c), float(s)
+    row0 = (0, s * iw, c * ih, c * ih + s * iw)
+    row1 = (0, c * iw, (-s) * ih, (-s) * ih + c * iw)
+    out_h = int((max(row0) - min(row0)) + 0.5)
+    out_w = int((max(row1) - min(row1)) + 0.5)
+    hy, hx = (out_h - 1) / 2, (out_w - 1) / 2
+    off0 = (ih - 1) / 2 - (c * hy + s * hx)
+    off1 = (iw - 1) / 2 - ((-s) * hy + c * hx)
+    return (c, s, -s, c), (off0, off1), (out_h, out_w)
+
+
+def _search_table_device(eps):
+    rounds, table = search_table(eps)
+    key = (float(eps), str(CP.storage_device()))
+    if key not in _search_tables:
+        _search_tables[key] = CP.copy(table.copy(), np.float64)
+    return rounds, _search_tables[key]
+
+
+def rotation_search(components, image_index, ks, eps=1.0):
+    """The angle search of interpreter.py:321-336 for the components `ks` (1-based) of image `image_index`, walked by the
+    device: returns (angles, traces) -- angles[i] in degrees or None, as search_steps returns it, computed on the host
+    from the leaf the device ended on; traces[i] float64 (rounds, 4) = a, b, height_a, height_b per round.  ONE
+    uocr_rotation_search call and ONE readback of (1 + 2 * rounds) ints per component (none for an empty list).
+    ValueError from search_table where the device cannot walk the tree at this eps."""
+    ks = [int(k) for k in ks]
+    search_table(eps)
+    if not ks:
+        return [], []
+    rounds, table = _search_table_device(eps)
+    n, h, w = components.labels.shape
+    boxes = [_box_of(components, image_index, k, 'rotation_search') for k in ks]
+    size = C.c_size_t()
+    if hiplib.get_lib().uocr_rotation_search_workspace(len(ks), C.byref(size)) != 0:
+        raise HipError(f'uocr_rotation_search_workspace failed for {len(ks)} paragraphs')
+    result = CP.empty((len(ks), 1 + 2 * rounds), np.int32)
+    workspace = CP.empty((size.value // 4,), np.int32)
+    _rt().call('uocr_rotation_search', components.labels.ptr, n, h, w, int(image_index), len(ks), _ints(ks),
+               _flat(boxes, C.c_int), rounds, table.ptr, result.ptr, workspace.ptr)
+    angles, traces = [], []
+    for row in result.numpy():
+        probes, angle = search_path(row[0], eps)
+        angles.append(angle)
+        traces.append(np.column_stack([np.array(probes, np.float64), row[1:].reshape(rounds, 2).astype(np.float64)]))
+    return angles, traces
+
+
 # ---- char labels (interpreter/interpreter.py:547-571: CharLabel) -----------------------------------------------------
 def char_label(lines, bits, n_chars, want_ids=False):
     """The (W, n_chars) one-hot labels of every line of `lines`, a flat list of (1, H, W, C) DeviceArrays whose first
