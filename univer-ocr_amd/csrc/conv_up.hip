@@ -34,103 +34,107 @@ constexpr int XH = RH + 2, XW = RW + 2;         // xl tile: halo 1
 constexpr int XPLANE = 624;                     // >= XH*XW, = 16 mod 32: the 4 channel planes of a half wave on disjoint banks
 constexpr int NWEFF = 9 * CH * 16;
 
-// weff[(m*4 + c)*16 + phase*4 + o], m = my*3 + mx, phase = py*2 + px
+// weff[(m*4 + c)*16 + phase*4 + o], m = my*3 + mx, phase = py*2 + px: entry i, the sum of the taps of its group.  A group has
+// at most 2 x 2 taps; all four are read from clamped indices and one outside the group adds +0.f (a sum that starts from
+// +0.f is never -0.f, so that changes no bit of it).  Loops over the group's own bounds, which depend on the lane, compile
+// to one waited load per trip: 36 round trips in a row for the nine entries of a forward lane when w is in global memory.
+// (hipcc still moves some of the four reads behind a branch on their validity: the forward kernel reads w from LDS.)
+__device__ __forceinline__ float weff_entry(const float* __restrict__ w, int i) {
+    const int o = i & 3, phase = (i >> 2) & 3, c = (i >> 4) & 3, m = i >> 6;
+    int ylo, yhi, xlo, xhi;
+    tap_group(phase >> 1, m / 3, ylo, yhi);
+    tap_group(phase & 1, m % 3, xlo, xhi);
+    float v[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) v[a][b] = w[((min(ylo + a, 4) * 5 + min(xlo + b, 4)) * CH + c) * CH + o];
+    float s = 0.f;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)                         // ky ascending, then kx
+#pragma unroll
+        for (int b = 0; b < 2; ++b) s += (ylo + a < yhi && xlo + b < xhi) ? v[a][b] : 0.f;
+    return s;
+}
+constexpr int NW = 25 * CH * CH;
+
 __global__ __launch_bounds__(256) void upconv_weff_kernel(const float* __restrict__ w, float* __restrict__ weff) {
-    for (int i = threadIdx.x; i < NWEFF; i += blockDim.x) {
-        const int o = i & 3, phase = (i >> 2) & 3, c = (i >> 4) & 3, m = i >> 6;
-        int ylo, yhi, xlo, xhi;
-        tap_group(phase >> 1, m / 3, ylo, yhi);
-        tap_group(phase & 1, m % 3, xlo, xhi);
-        float s = 0.f;
-        for (int ky = ylo; ky < yhi; ++ky)
-            for (int kx = xlo; kx < xhi; ++kx) s += w[((ky * 5 + kx) * CH + c) * CH + o];
-        weff[i] = s;
-    }
+    for (int i = threadIdx.x; i < NWEFF; i += blockDim.x) weff[i] = weff_entry(w, i);
 }
 
-// xl tile (halo 1) of the region at low-res origin (ry, rx), channel-planar in LDS; zero outside the image
+// xl tile (halo 1) of the region at low-res origin (ry, rx): a thread's three pixels, loaded from clamped addresses (no
+// branch, so the loads go out together and can be left in flight over other work) ...
 template <typename TA>
-__device__ __forceinline__ void stage_planar(float* __restrict__ xs, const TA* __restrict__ xb, int ry, int rx,
+__device__ __forceinline__ void xl_tile_load(float4 (&v)[3], bool (&in)[3], const TA* __restrict__ xb, int ry, int rx,
                                              int hl, int wl, int tid) {
-    if constexpr (sizeof(TA) == 4) {
-        stage_batched<XH * XW, 256, 3, float4>(
-            tid,
-            [&](int i, bool& inside) {
-                const int r = i / XW, c = i - r * XW;
-                const int gy = ry - 1 + r, gx = rx - 1 + c;
-                inside = gy >= 0 && gy < hl && gx >= 0 && gx < wl;
-                return reinterpret_cast<const float4*>(xb + ((size_t)min(max(gy, 0), hl - 1) * wl + min(max(gx, 0), wl - 1)) * CH);
-            },
-            [&](int i, float4 v, bool inside) {
-                if (!inside) v = make_float4(0.f, 0.f, 0.f, 0.f);
-                xs[i] = v.x;
-                xs[XPLANE + i] = v.y;
-                xs[2 * XPLANE + i] = v.z;
-                xs[3 * XPLANE + i] = v.w;
-            });
-        return;
-    }
-    for (int i = tid; i < XH * XW; i += 256) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int i = min(tid + 256 * k, XH * XW - 1);
         const int r = i / XW, c = i - r * XW;
         const int gy = ry - 1 + r, gx = rx - 1 + c;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (gy >= 0 && gy < hl && gx >= 0 && gx < wl) v = ld4(xb + ((size_t)gy * wl + gx) * CH);
-        xs[i] = v.x;
-        xs[XPLANE + i] = v.y;
-        xs[2 * XPLANE + i] = v.z;
-        xs[3 * XPLANE + i] = v.w;
+        in[k] = gy >= 0 && gy < hl && gx >= 0 && gx < wl;
+        v[k] = ld4(xb + ((size_t)min(max(gy, 0), hl - 1) * wl + min(max(gx, 0), wl - 1)) * CH);
+    }
+}
+// ... and written channel-planar to LDS, zero outside the image
+__device__ __forceinline__ void xl_tile_put(float* __restrict__ xs, const float4 (&v)[3], const bool (&in)[3], int tid) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int i = tid + 256 * k;
+        if (i >= XH * XW) continue;
+        const float4 u = in[k] ? v[k] : make_float4(0.f, 0.f, 0.f, 0.f);
+        xs[i] = u.x;
+        xs[XPLANE + i] = u.y;
+        xs[2 * XPLANE + i] = u.z;
+        xs[3 * XPLANE + i] = u.w;
     }
 }
 
 // forward.  Block = 16 x 32 low-res positions per tile iteration over a band of rows; wave w owns rows
 // 4w..4w+3 (8 groups of 16 consecutive positions).
+// (8 waves per SIMD, 64 registers: the 2048 blocks of the budget are then resident together on 256 CUs)
 template <typename TA, class K>
-__global__ __launch_bounds__(256) void upconv_fwd_kernel(const TA* __restrict__ xl, const float* __restrict__ w,
+__global__ __launch_bounds__(256, 8) void upconv_fwd_kernel(const TA* __restrict__ xl, const float* __restrict__ w,
                                                          const float* __restrict__ bias, TA* __restrict__ y,
                                                          int hl, int wl, int rows_per_block, int use_bias, int act,
                                                          float alpha, float* __restrict__ weff_out) {
     act = act_kind<K::act>(act);                 // (a constant unless the tag is dynamic: uocr_common.h)
     __shared__ float xs[CH * XPLANE];
+    __shared__ float ws[512];                    // w, and copies of its last entry up to two per thread
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = lane & 15, kq = lane >> 4;
-    // the per-phase 3 x 3 weights the backward-data kernel of this layer wants (upconv_weff_kernel's table), written by
-    // block 0 while it is here anyway: the caller hands the buffer back to uocr_upconv2x_bwd_data, which then needs no
-    // launch of its own for them (a launch costs the lane 8-10 us inside the page step)
-    if (weff_out && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
-        for (int i = tid; i < NWEFF; i += 256) {
-            const int o = i & 3, phase = (i >> 2) & 3, c = (i >> 4) & 3, m = i >> 6;
-            int ylo, yhi, xlo, xhi;
-            tap_group(phase >> 1, m / 3, ylo, yhi);
-            tap_group(phase & 1, m % 3, xlo, xhi);
-            float s = 0.f;
-            for (int ky = ylo; ky < yhi; ++ky)
-                for (int kx = xlo; kx < xhi; ++kx) s += w[((ky * 5 + kx) * CH + c) * CH + o];
-            weff_out[i] = s;
-        }
-    }
     const int rx = blockIdx.x * RW;
     const int row_begin = blockIdx.y * rows_per_block, row_end = min(hl, row_begin + rows_per_block);
     const TA* xb = xl + (size_t)blockIdx.z * hl * wl * CH;
     const int W = 2 * wl;
     TA* yb = y + (size_t)blockIdx.z * (2 * hl) * W * CH;
-    // A = Weff^T: lane (m = (phase,o) = n, k = channel kq), one register per tap, summed here from the 25
-    // taps of w (each belongs to exactly one source offset for this lane's phase)
-    float wa[9];
+    // One batch of loads in front of the block: the 400 weights (to LDS) and the first tile.
+    float wr[2];
 #pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        int ylo, yhi, xlo, xhi;
-        tap_group(n >> 3, t / 3, ylo, yhi);
-        tap_group((n >> 2) & 1, t % 3, xlo, xhi);
-        float s = 0.f;
-        for (int ky = ylo; ky < yhi; ++ky)
-            for (int kx = xlo; kx < xhi; ++kx) s += w[((ky * 5 + kx) * CH + kq) * CH + (n & 3)];
-        wa[t] = s;
-    }
+    for (int k = 0; k < 2; ++k) wr[k] = w[min(tid + 256 * k, NW - 1)];
+    float4 xv[3];
+    bool xin[3];
+    xl_tile_load(xv, xin, xb, row_begin, rx, hl, wl, tid);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) ws[tid + 256 * k] = wr[k];      // (no condition: hipcc would move the load behind it)
+    xl_tile_put(xs, xv, xin, tid);
+    __syncthreads();
+    // the per-phase 3 x 3 weights the backward-data kernel of this layer wants (upconv_weff_kernel's table), written by
+    // block 0 while it is here anyway: the caller hands the buffer back to uocr_upconv2x_bwd_data, which then needs no
+    // launch of its own for them (a launch costs the lane 8-10 us inside the page step)
+    if (weff_out && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)
+        for (int i = tid; i < NWEFF; i += 256) weff_out[i] = weff_entry(ws, i);
     f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
     if (use_bias) b4 = f32x4{bias[0], bias[1], bias[2], bias[3]};
+    // A = Weff^T: lane (m = (phase,o) = n, k = channel kq), one register per tap, summed here from the 25 taps of w (each
+    // belongs to exactly one source offset for this lane's phase).  Directly in front of the tile loop: with a branch in
+    // between, hipcc reads the 36 values here and adds them behind the branch (83 registers, or spills at 64).
+    float wa[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) wa[t] = weff_entry(ws, (t * CH + kq) * 16 + n);
     for (int ry = row_begin; ry < row_end; ry += RH) {
-        __syncthreads();
-        stage_planar(xs, xb, ry, rx, hl, wl, tid);
-        __syncthreads();
+        // the next tile of the band is requested before this tile's MFMAs and lands in LDS after them
+        const bool more = ry + RH < row_end;
+        if (more) xl_tile_load(xv, xin, xb, ry + RH, rx, hl, wl, tid);
 #pragma unroll 2
         for (int k = 0; k < 8; ++k) {
             const int gi = wv * 8 + k, r = gi >> 1, c0 = (gi & 1) * 16;
@@ -150,6 +154,11 @@ __global__ __launch_bounds__(256) void upconv_fwd_kernel(const TA* __restrict__ 
                 st4(yb + ((size_t)(2 * py + (kq >> 1)) * W + 2 * pxl + (kq & 1)) * CH, out);
             }
         }
+        if (more) {
+            __syncthreads();
+            xl_tile_put(xs, xv, xin, tid);
+            __syncthreads();
+        }
     }
 }
 
@@ -161,50 +170,82 @@ __global__ __launch_bounds__(256) void upconv_wgrad_kernel(const TA* __restrict_
     __shared__ float xs[CH * XPLANE];
     __shared__ float red[4][48][16];
     __shared__ float reddb[4][64];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = lane & 15, kq = lane >> 4;
+    const int tid = threadIdx.x, lane = tid & 63, n = lane & 15, kq = lane >> 4;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rx = blockIdx.x * RW;
     const int row_begin = blockIdx.y * rows_per_block, row_end = min(hl, row_begin + rows_per_block);
     const TA* xb = xl + (size_t)blockIdx.z * hl * wl * CH;
     const int W = 2 * wl;
     const TA* gb = dy + (size_t)blockIdx.z * (2 * hl) * W * CH;
-    // A = Xcol^T: lane (m = K index 16j + n -> tap K/4, channel K%4; k = position 4i + kq)
+    // A = Xcol^T: lane (m = K index 16j + n -> tap K/4, channel K%4; k = position 4i + kq).  K = 36..47 read the in-range
+    // offset of K = 35: those accumulator rows hold sums that no partial row reads (up4_write_row stops at K = 35).
     int aoff[3];
-    bool aok[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        const int K = 16 * j + n;
-        aok[j] = K < 36;
-        const int Kc = aok[j] ? K : 35, t = Kc >> 2;
+        const int Kc = min(16 * j + n, 35), t = Kc >> 2;
         aoff[j] = (Kc & 3) * XPLANE + (t / 3) * XW + t % 3 + kq;
     }
-    // B = dY: lane (k = position 4i + kq, n = (phase, o))
+    // B = dY: lane (k = position 4i + kq, n = (phase, o)).  A trip of the depth loop is one low-res row of the tile (two
+    // groups of 16 positions, wave w owns rows 4w..4w+3): eight loads at a wave-uniform row base plus these lane offsets,
+    // clamped into the image, with the column's validity beside them.
     const int boff = ((n >> 3) * W + ((n >> 2) & 1)) * CH + (n & 3);
+    int goff[2][4];
+    bool gok[2][4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int pl = 16 * h + 4 * i + kq;          // position of this lane's K slot
+            gok[h][i] = rx + pl < wl;
+            goff[h][i] = boff + 2 * min(pl, wl - 1 - rx) * CH;
+        }
+    // the dy values of the NEXT trip (across the tile boundary: of the next tile's first trip) are requested before the
+    // MFMAs of the current one and wait in registers; a row past the band is clamped into the image and counts as zero
+    // (two register sets in turn: with one set and a copy, hipcc moves the loads behind the last use of the copy)
+    float ga[2][4], gz[2][4];
+    auto load_row = [&](float (&g)[2][4], int py) {
+        const TA* gr = gb + ((size_t)(2 * min(py, hl - 1)) * W + 2 * rx) * CH;
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) g[h][i] = ld1(gr + goff[h][i]);
+    };
     f32x4 acc[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     float dbacc = 0.f;
-    for (int ry = row_begin; ry < row_end; ry += RH) {
-        __syncthreads();
-        stage_planar(xs, xb, ry, rx, hl, wl, tid);
-        __syncthreads();
-#pragma unroll 2
-        for (int k = 0; k < 8; ++k) {
-            const int gi = wv * 8 + k, r = gi >> 1, c0 = (gi & 1) * 16;
-            const int py = ry + r;
-            const bool row_ok = py < row_end;
-            const float* xr = xs + r * XW + c0;
-            const TA* gr = gb + ((size_t)(2 * min(py, hl - 1)) * W + 2 * rx) * CH + boff;
+    auto trip = [&](const float (&g)[2][4], int r, bool row_ok) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float* xr = xs + r * XW + 16 * h;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int pl = c0 + 4 * i + kq;          // position of this lane's K slot
-                const bool ok = row_ok && rx + pl < wl;
-                float g = ld1(gr + (size_t)2 * min(pl, wl - 1 - rx) * CH);
-                g = ok ? g : 0.f;
-                dbacc += g;
+                const float gv = row_ok && gok[h][i] ? g[h][i] : 0.f;
+                dbacc += gv;
 #pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    const float xv = xr[4 * i + aoff[j]];
-                    acc[j] = mfma4(aok[j] ? xv : 0.f, g, acc[j]);
-                }
+                for (int j = 0; j < 3; ++j) acc[j] = mfma4(xr[4 * i + aoff[j]], gv, acc[j]);
             }
+        }
+    };
+    float4 xv[3];
+    bool xin[3];
+    xl_tile_load(xv, xin, xb, row_begin, rx, hl, wl, tid);
+    // (the tile's loads first, as in the loop: loads complete in order, and where the two paths into the loop disagree
+    // about which are the oldest, the wait in front of xl_tile_put becomes a wait for everything, the dy row included)
+    __builtin_amdgcn_sched_barrier(0);
+    load_row(ga, row_begin + wv * 4);
+    for (int ry = row_begin; ry < row_end; ry += RH) {
+        __syncthreads();
+        xl_tile_put(xs, xv, xin, tid);
+        __syncthreads();
+        if (ry + RH < row_end) xl_tile_load(xv, xin, xb, ry + RH, rx, hl, wl, tid);
+#pragma unroll 1
+        for (int kp = 0; kp < 4; kp += 2) {
+            const int r = wv * 4 + kp, py = ry + r;
+            load_row(gz, py + 1);
+            __builtin_amdgcn_sched_barrier(0);               // (the loads stay in front of the trip's MFMAs)
+            trip(ga, r, py < row_end);
+            load_row(ga, kp == 0 ? py + 2 : py + RH - 2);    // (kp == 2: the wave's first row of the next tile)
+            __builtin_amdgcn_sched_barrier(0);
+            trip(gz, r + 1, py + 1 < row_end);
         }
     }
 #pragma unroll
@@ -218,8 +259,13 @@ __global__ __launch_bounds__(256) void upconv_wgrad_kernel(const TA* __restrict_
     // 580-column row per output and block: 10-13 us inside the step)
     if (tid < 4) {                                       // db[o]: lanes with (n & 3) == o
         float s = 0.f;
-        for (int w = 0; w < 4; ++w)
-            for (int l = tid; l < 64; l += 4) s += reddb[w][l];
+        for (int w = 0; w < 4; ++w) {                    // (a wave's 16 values read together, then added in lane order)
+            float v[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) v[k] = reddb[w][tid + 4 * k];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) s += v[k];
+        }
         reddb[0][tid] = s;                               // (read back below as entry 576 + o)
     }
     __syncthreads();
@@ -279,15 +325,23 @@ __global__ __launch_bounds__(256) void upconv_dgrad_kernel(const TA* __restrict_
     const int H = 2 * hl, W = 2 * wl;
     const TA* gb = dy + (size_t)blockIdx.z * H * W * CH;
     if constexpr (sizeof(TA) == 4) {
-        stage_batched<GH * GW, 256, 5, float4>(
-            tid,
-            [&](int i, bool& inside) {
-                const int r = i / GW, c = i - r * GW;
-                const int gy = 2 * (ry - 1) + r, gx = 2 * (rx - 1) + c;
-                inside = gy >= 0 && gy < H && gx >= 0 && gx < W;
-                return reinterpret_cast<const float4*>(gb + ((size_t)min(max(gy, 0), H - 1) * W + min(max(gx, 0), W - 1)) * CH);
-            },
-            [&](int i, float4 v, bool inside) { gs[i] = inside ? v : make_float4(0.f, 0.f, 0.f, 0.f); });
+        // A thread's ten pixels of the tile in ONE batch of loads from clamped addresses.  A thread past the end of the tile
+        // loads and stores the last pixel again: with a condition around the store, hipcc moves that load behind the
+        // condition and waits for it there, a round trip of its own after the others.
+        constexpr int NK = (GH * GW + 255) / 256;
+        float4 v[NK];
+        bool in[NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int i = min(tid + 256 * k, GH * GW - 1);
+            const int r = i / GW, c = i - r * GW;
+            const int gy = 2 * (ry - 1) + r, gx = 2 * (rx - 1) + c;
+            in[k] = gy >= 0 && gy < H && gx >= 0 && gx < W;
+            v[k] = ld4(gb + ((size_t)min(max(gy, 0), H - 1) * W + min(max(gx, 0), W - 1)) * CH);
+        }
+#pragma unroll
+        for (int k = 0; k < NK; ++k)
+            gs[min(tid + 256 * k, GH * GW - 1)] = in[k] ? v[k] : make_float4(0.f, 0.f, 0.f, 0.f);
     } else {
         for (int i = tid; i < GH * GW; i += 256) {
             const int r = i / GW, c = i - r * GW;
@@ -297,8 +351,16 @@ __global__ __launch_bounds__(256) void upconv_dgrad_kernel(const TA* __restrict_
             gs[i] = v;
         }
     }
-    __syncthreads();
     const int c = tid & 31, r0 = tid >> 5;               // positions (r0, c) and (r0 + 8, c)
+    // the activation outputs the epilogue masks with: requested here, behind the tile's loads, so that they arrive during
+    // the tap loop (position clamped into the image: a thread outside it stores nothing)
+    float4 yv[2];
+    if (mask_act != UOCR_ACT_NONE) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+            yv[p] = ld4(mask_y + (((size_t)blockIdx.z * hl + min(ry + r0 + 8 * p, hl - 1)) * wl + min(rx + c, wl - 1)) * CH);
+    }
+    __syncthreads();
     float acc[2][4];
 #pragma unroll
     for (int p = 0; p < 2; ++p)
@@ -330,11 +392,10 @@ __global__ __launch_bounds__(256) void upconv_dgrad_kernel(const TA* __restrict_
         const size_t off = (((size_t)blockIdx.z * hl + qy) * wl + qx) * CH;
         float4 out = make_float4(acc[p][0], acc[p][1], acc[p][2], acc[p][3]);
         if (mask_act != UOCR_ACT_NONE) {
-            const float4 yv = ld4(mask_y + off);
-            out.x *= act_grad_from_output<float>(yv.x, mask_act, mask_alpha);
-            out.y *= act_grad_from_output<float>(yv.y, mask_act, mask_alpha);
-            out.z *= act_grad_from_output<float>(yv.z, mask_act, mask_alpha);
-            out.w *= act_grad_from_output<float>(yv.w, mask_act, mask_alpha);
+            out.x *= act_grad_from_output<float>(yv[p].x, mask_act, mask_alpha);
+            out.y *= act_grad_from_output<float>(yv[p].y, mask_act, mask_alpha);
+            out.z *= act_grad_from_output<float>(yv[p].z, mask_act, mask_alpha);
+            out.w *= act_grad_from_output<float>(yv[p].w, mask_act, mask_alpha);
         }
         st4(dxl + off, out);
     }
