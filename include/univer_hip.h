@@ -179,7 +179,12 @@ int uocr_graph_destroy(void* graph_exec);
  * overwrites.  With a snapshot configured, the fused optimizer entry points (uocr_momentum_step_fused /
  * uocr_adam_step_fused: the last kernel of a train step) end by copying slots[0..count) into row (n % ring_len) of
  * ring[ring_len][count], n = the number of such calls since `counter` (one device word, zeroed by the caller) was set
- * up -- a device-side count, so a replayed HIP graph advances it by itself.  slots == NULL switches it off. */
+ * up -- a device-side count, so a replayed HIP graph advances it by itself.  Every such call with count > 0 parameters
+ * writes exactly one row (a call with no parameters launches nothing and writes none); reg_loss_out may be one of the
+ * slots, the row then holds the value that call stored.  A row keeps its step's values until ring_len further calls have
+ * been made, then it is overwritten without notice: the caller counts its calls and must not read a row that late.
+ * slots == NULL switches it off (the counter keeps its value: configured again, the numbering goes on from there);
+ * otherwise count > 0, ring != NULL, ring_len > 0 and counter != NULL, or UOCR_ERR_ARG.  Host bookkeeping only. */
 int uocr_ctx_set_loss_snapshot(uocr_ctx* ctx, const double* slots, int count, double* ring, int ring_len,
                                unsigned* counter);
 /* Deferred weight gradients.  The reference computes dW of a layer right where it computes dX (convolutional.py:101-145,

@@ -354,7 +354,8 @@ __device__ __forceinline__ void opt_fused_one(T& wi, T& gi, T& vi, T& ai, long l
 // uocr_ctx_set_loss_snapshot: the thread that ends the step's last kernel (the one that stores the regularisation loss)
 // copies the net's loss slots into the next row of a ring -- the per-step snapshot of the losses without a copy launch
 // of its own (a launch costs its lane 8-10 us inside the page step).  The row index is a device counter: a replayed
-// HIP graph advances it by itself.
+// HIP graph advances it by itself.  Every launch with a snapshot configured writes exactly one row, from one of three
+// places: no ranges (block 0), ranges in one block, ranges in several blocks (the last block to arrive).
 struct LossSnapshot {
     const double* src;       // null: off
     int count;
@@ -378,8 +379,10 @@ template <typename T, int OPT, int VEC>
 __global__ __launch_bounds__(256) void opt_fused_kernel(T* __restrict__ w, T* __restrict__ g, T* __restrict__ s1,
                                                         T* __restrict__ s2, size_t n, T p0, T p1, T p2, T p3,
                                                         RegRanges rr, double* partial /* [grid][4] */,
-                                                        double* __restrict__ loss_out, unsigned* counter,
-                                                        int zero_grad, const double* __restrict__ hyper, LossSnapshot snap) {
+                                                        double* loss_out, unsigned* counter, int zero_grad,
+                                                        const double* __restrict__ hyper, LossSnapshot snap) {
+    // (loss_out is NOT __restrict__: the trainer's regularisation slot is one of snap.src's slots, and loss_snapshot must read
+    // the value stored just before it, not the previous step's)
     if (hyper) {      // hyper-parameters from device memory: a captured HIP graph follows lr / beta changes
         p0 = (T)hyper[0];
         p1 = (T)hyper[1];

@@ -42,7 +42,7 @@ class PageTrainer:
                  nets=('Monochrome', 'Paragraph', 'Line', 'Char'), data_parallel=None, overlap=True,
                  dp_coalesce=False, dp_backend=None,
                  init='kaiming_normal', fuse=True, lanes=True, input_grads=True, graphs=False, eager_nets=(), pipelined=False,
-                 snapshot_losses=True,
+                 snapshot_losses=True, snapshot_ring_len=64,
                  lane_groups=(('Monochrome', 'Paragraph'), ('Line',), ('Char',)), lane_xcds=None, side_wgrad=None,
                  group_wgrad=None):
         np.random.seed(seed)                        # kaiming_uniform draws from the NumPy global RNG
@@ -108,9 +108,14 @@ class PageTrainer:
         # first GPU call (bench.py sets it; ROCm's default 4 makes two nets share a queue)
         self.pipelined = bool(pipelined) and self.lanes is not None
         # graphs: the captured step writes its losses into static slots that the NEXT replay overwrites; with
-        # snapshot_losses the step's last kernel copies them into the next row of a ring of 64 (LossArena) so that the
-        # scalars it returns keep the value of THEIR step however late they are read
+        # snapshot_losses the step's last kernel copies them into the next row of a ring of snapshot_ring_len rows
+        # (LossArena), so that the scalars it returns keep the value of THEIR step for snapshot_ring_len - 1 further steps of
+        # their net.  After that the row belongs to a later step: a first read that late raises HipError (DeviceScalar),
+        # it never returns the other step's value -- read an epoch's losses at least that often, or ask for a longer ring
         self.snapshot_losses = bool(snapshot_losses)
+        self.snapshot_ring_len = int(snapshot_ring_len)
+        if self.snapshot_ring_len < 1:
+            raise ValueError(f'snapshot_ring_len {snapshot_ring_len} < 1')
         self._lane_done = {}
         self._event_rings = {}
         self.eager_nets = tuple(eager_nets)          # nets kept out of the graphs (e.g. to time one kernel)
@@ -295,7 +300,7 @@ class PageTrainer:
                     # (what is allocated in the pool between or during captures may be handed out again to a later capture)
                     ring = self.snapshot_losses and model.has_fused_tail()
                     with torch.cuda.use_mem_pool(pool):
-                        arena = CP.loss_arena = LossArena(16)
+                        arena = CP.loss_arena = LossArena(16, ring_len=self.snapshot_ring_len)
                         if ring:
                             arena.arm()
                     cap = [rt.capture(pool)]
@@ -426,7 +431,8 @@ class PageTrainer:
             if entry['prediction'] is not None:
                 context[comp.selector.pred_label] = entry['prediction']
             if snap is not None:
-                values = [DeviceScalar(snap.t[i]) for i in entry['slot_index']]
+                ringed = entry['arena'] if entry['arena'].ring is not None else None     # (a ring row is recycled: stamped)
+                values = [DeviceScalar(snap.t[i], arena=ringed) for i in entry['slot_index']]
             else:                                             # aliases of the static slots: read before the next step()
                 values = [DeviceScalar(t) for t in entry['output_losses']] + [DeviceScalar(entry['regularization_loss'])]
             context['losses'][comp.name] = {'output_losses': values[:-1], 'regularization_loss': values[-1]}

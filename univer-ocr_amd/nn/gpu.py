@@ -376,12 +376,17 @@ class LossArena:
     Per-step snapshots: `arm()` gives the arena a ring of `ring_len` rows; with Runtime.set_loss_snapshot(arena) in force
     the step's last kernel (the fused optimizer tail) copies the slots into the next row by itself
     (uocr_ctx_set_loss_snapshot), and `next_row()` names that row on the host -- no copy launch.  A row is overwritten
-    `ring_len` steps later."""
+    `ring_len` steps later: a DeviceScalar made from a row with `arena=` remembers `rows` and refuses to be read for the
+    first time once `ring_len` further tails have been launched (a HipError, never another step's number).  The host's
+    `rows` and the device counter agree as long as every tail launched with this arena's snapshot in force is followed by
+    one `next_row()`; tails launched with the snapshot off (eager steps of a captured net) advance neither."""
 
     def __init__(self, capacity=16, ring_len=64):
+        if int(ring_len) < 1:
+            raise HipError(f'LossArena: ring_len {ring_len} < 1')
         self.array = CP.empty((capacity,), np.float64)
         self.used = 0
-        self.ring_len = ring_len
+        self.ring_len = int(ring_len)
         self.ring = self.counter = None
         self.rows = 0                                # optimizer tails launched since arm() (the device counts the same)
 
@@ -410,7 +415,8 @@ class LossArena:
         return self
 
     def next_row(self):
-        """the ring row the optimizer tail that was just launched writes: a view, valid for ring_len further steps"""
+        """the ring row the optimizer tail that was just launched writes: a view, valid until ring_len further tails have
+        been launched (DeviceScalar(row.t[i], arena=self), made before the next call, enforces that)"""
         capacity = self.array.shape[0]
         k = self.rows % self.ring_len
         self.rows += 1
@@ -753,17 +759,25 @@ class CP:
 class DeviceScalar:
     """A float64 loss value that lives in a device slot until somebody needs the number.  The
     reference converts every loss with float() right away (losses.py:25,42,57,73 -- one host sync
-    each); with CP.lazy_losses the sync happens once, when the caller formats / adds the value."""
+    each); with CP.lazy_losses the sync happens once, when the caller formats / adds the value.
+    `arena`: the slot is in the row LossArena.next_row() has just named; the first read fails once the ring has come
+    round to that row again (a host-side comparison of two counts: no device work)."""
 
-    __slots__ = ('t', '_value', 'ready')
+    __slots__ = ('t', '_value', 'ready', 'arena', 'stamp')
 
-    def __init__(self, tensor, ready=None):
+    def __init__(self, tensor, ready=None, arena=None):
         self.t = tensor          # 0-d or 1-element float64 tensor
         self._value = None
         self.ready = ready       # event of the stream that writes the slot, when that is not the reader's stream
+        self.arena = arena       # the LossArena whose ring row holds the slot, or None
+        self.stamp = arena.rows if arena is not None else 0      # tails launched up to and including this value's own
 
     def __float__(self):
         if self._value is None:
+            if self.arena is not None and self.arena.rows - self.stamp >= self.arena.ring_len:
+                raise HipError(f'loss read {self.arena.rows - self.stamp} steps after its own: its row of the snapshot ring '
+                               f'has been overwritten (snapshot_ring_len = {self.arena.ring_len}); read losses within '
+                               f'snapshot_ring_len steps or raise PageTrainer(snapshot_ring_len=...)')
             if self.ready is not None:
                 self.ready.synchronize()
             self._value = float(self.t.item())
