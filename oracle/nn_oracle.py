@@ -28,6 +28,11 @@ def _pair(v):
     return (v, v) if isinstance(v, (int, np.integer)) else tuple(int(t) for t in v)
 
 
+def round16(a):
+    """float64 -> nearest binary16 -> float64: what one store of the float16 mode keeps (Net.stored16)."""
+    return np.asarray(a, dtype=np.float64).astype(np.float16).astype(np.float64)
+
+
 # ----------------------------------------------------------------------------
 # Convolutional2D  (layers/convolutional.py)
 # ----------------------------------------------------------------------------
@@ -432,7 +437,8 @@ class Net:
     def param_names(self):
         return sorted(self.params.keys())
 
-    def forward(self, X, keep=False):
+    def forward(self, X, keep=False, store=None):
+        """store: applied to every layer's output as it is written (stored16); None = kept as computed."""
         stash = []
         for name, kind, cfg in self.spec:
             inp = X
@@ -463,11 +469,14 @@ class Net:
                 pass
             else:
                 raise ValueError(kind)
+            if store is not None:
+                X = store(X)
             if keep:
                 stash.append(inp)
         return (X, stash) if keep else X
 
-    def backward(self, g, stash):
+    def backward(self, g, stash, store=None):
+        """store: applied to every layer's input gradient as it is written (stored16); dw / db are left as summed."""
         grads = {}
         for (name, kind, cfg), inp in zip(reversed(self.spec), reversed(stash)):
             if kind == 'conv':
@@ -491,23 +500,53 @@ class Net:
                 g = fixed_width_bwd(g, inp, cfg['width'])
             elif kind == 'flatten':
                 g = g.reshape(inp)
+            if store is not None:
+                g = store(g)
         return g, grads
 
-    def loss_and_grads(self, X, y):
-        """compute_loss_and_gradients (models.py:232-248)."""
-        pred, stash = self.forward(X, keep=True)
-        loss, g = LOSSES[self.loss](pred, y)
-        dx, grads = self.backward(g, stash)
-        reg = 0.0
+    def regularised(self):
+        """[(parameter, L2 strength)] of every regularised parameter, in spec order."""
+        out = []
         for name, kind, cfg in self.spec:
             lam = cfg.get('l2') if kind in ('conv', 'dense') else None
             if lam:
-                for pn in ([f'{name}/w', f'{name}/b'] if kind == 'conv' else [f'{name}/w']):
-                    rl, rg = l2_reg(self.params[pn], lam)
-                    grads[pn] = grads[pn] + rg
-                    reg += rl
+                out += [(pn, lam) for pn in ([f'{name}/w', f'{name}/b'] if kind == 'conv' else [f'{name}/w'])]
+        return out
+
+    def data_grads(self, X, y):
+        """(prediction, loss, {param: gradient of the loss alone}): forward, loss, backward, no regulariser.  The
+        gradient w.r.t. X is left in `input_grad`."""
+        pred, stash = self.forward(X, keep=True)
+        loss, g = LOSSES[self.loss](pred, y)
+        self.input_grad, grads = self.backward(g, stash)
+        return pred, loss, grads
+
+    def stored16(self, X, y, grad_scale_log2, rnd=None):
+        """data_grads with every activation and every activation gradient stored once in binary16: each layer's output is
+        rounded on the way forward, the loss gradient and each layer's input gradient as rnd(g * 2^k) / 2^k on the way
+        back (k = grad_scale_log2, the power of two a float16 run gives its gradients); parameters, dw / db and every
+        sum stay float64.  No kernel's rounding points are copied: this only measures how far honest binary16 storage
+        moves a data gradient.  rnd: the rounding, binary16 by default (the identity gives data_grads back)."""
+        rnd = round16 if rnd is None else rnd
+        factor = 2.0 ** grad_scale_log2
+
+        def rnd_grad(g):
+            return rnd(g * factor) / factor
+        pred, stash = self.forward(X, keep=True, store=rnd)
+        loss, g = LOSSES[self.loss](pred, y)
+        _, grads = self.backward(rnd_grad(g), stash, store=rnd_grad)
+        return pred, loss, grads
+
+    def loss_and_grads(self, X, y):
+        """compute_loss_and_gradients (models.py:232-248)."""
+        pred, loss, grads = self.data_grads(X, y)
+        reg = 0.0
+        for pn, lam in self.regularised():
+            rl, rg = l2_reg(self.params[pn], lam)
+            grads[pn] = grads[pn] + rg
+            reg += rl
         self.grads = grads
-        return {'output_losses': [loss], 'regularization_loss': reg}, pred, dx
+        return {'output_losses': [loss], 'regularization_loss': reg}, pred, self.input_grad
 
     def train_step(self, X, y, optimizer):
         losses, pred, _ = self.loss_and_grads(X, y)

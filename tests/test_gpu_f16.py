@@ -318,7 +318,9 @@ def nest(flat):
 
 def f16_net_step(CP, name, shape, X, y, fuse=True):
     """One compute_loss_and_gradients of net `name` in float16 mode and the oracle's on the binary16-rounded
-    page with float32-rounded weights.  Returns the error triple (prediction, loss, worst parameter gradient)."""
+    page with float32-rounded weights.  Returns the error triple (prediction, loss, worst parameter gradient).
+    The gradients compared include the L2 term, which dominates most of them, so the callers' 1e-2 says little about the
+    data gradients: those are judged on their own in tests/test_gpu_f16_training.py."""
     from univer_ocr_amd.my_model.model import NET_MAKERS
     from univer_ocr_amd.nn.optimizers import Momentum
     net = O.make_net(name)
