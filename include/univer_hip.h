@@ -405,6 +405,34 @@ int uocr_masked_crop(uocr_ctx* ctx, int dtype, const void* image, const int* lab
 /* the tile (rows, columns) of the last uocr_label_components call on this ctx and the kernels it launched (all 0 before the
  * first): tests size their images from it so that components cross tile borders */
 int uocr_ctx_last_label(uocr_ctx* ctx, int* tile_h, int* tile_w, int* launches);
+/* Connected components of a LIST of images of different sizes, every image one channel of an interleaved tensor, in one
+ * call (interpreter.py:437-438, :16-21, :36-39, :494-502 for every paragraph of a page at once).  Entry i is channel
+ * channel[i] of x[i]: (1, h[i], w[i], c[i]) in `dtype`, read in place -- pixel (y, x) is the element at
+ * (y * w + x) * c + channel; no split copy is made.  Foreground is value > t, t chosen PER ENTRY by thresh_mode as in
+ * uocr_label_components: mean and max are float64 reductions over the h * w elements of that entry's channel only, not
+ * over its other channels and not over the call.  The summation order is fixed (per 4096 pixels of the entry, then over
+ * those partials), so results are bit-identical run to run; it is NOT the order uocr_label_components uses, so a value
+ * within rounding of its threshold may fall on the other side there.
+ * table: int64 [n_entries][max_components][8] and count: int32 [n_entries], both on the device, with exactly the
+ * semantics of uocr_label_components: scipy's numbering (order of the first pixel, row-major), 4-connectivity, half-open
+ * boxes; rows past count[i] are zero; count[i] is the true count even above max_components (the table then holds the
+ * first max_components rows, the labels stay complete).  labels may be NULL and so may any labels[i]; a given labels[i]
+ * is int32 (h[i], w[i]) and every element is written, otherwise the entry's plane lives in the ctx workspace (line
+ * finding needs no labels).  x, h, w, c, channel, labels are HOST arrays of n_entries entries (device pointers / sizes).
+ * The entries travel as kernel arguments, 32 per group: no descriptor copy, no allocation.  Per group one chain of 6-7
+ * kernels (5 without statistics and tile borders) whatever the number of entries, per call one memset of the table.
+ * UOCR_ERR_ARG for a null x, table or count, a null x[i], pointers off their element's alignment, h[i], w[i] or c[i] < 1,
+ * channel[i] outside [0, c[i]), a bad thresh_mode, max_components < 0 and n_entries < 0; UOCR_ERR_UNSUPPORTED for h * w
+ * beyond int32 linear indices or a group with too many blocks for one grid; scratch (two int32 per pixel of a group at
+ * most, and a little more) comes from the ctx workspace (UOCR_ERR_WORKSPACE).  Nothing is written on any error;
+ * n_entries = 0 is UOCR_OK and launches nothing (the other arguments are not looked at).  Integer atomics only between
+ * blocks.  Asynchronous and capturable. */
+int uocr_label_batch(uocr_ctx* ctx, int dtype, int n_entries, const void* const* x, const int* h, const int* w,
+                     const int* c, const int* channel, int thresh_mode, double thresh_value, int* const* labels,
+                     long long* table, int max_components, int* count);
+/* sizes the last uocr_label_batch call on this ctx used: the tile (rows, columns), entries per launch group, kernels
+ * launched (all 0 before the first call) -- tests size their inputs from it */
+int uocr_ctx_last_label_batch(uocr_ctx* ctx, int* tile_h, int* tile_w, int* entries_per_launch, int* launches);
 
 /* ---- char labels (interpreter/interpreter.py:547-571 LabelChar._func1: the CharLabel stage) --------------------
  * The one-hot training labels of the Char net from the bit layers of every cropped line, for ALL lines of a page in one

@@ -126,6 +126,8 @@ _PROTOS = {
     'uocr_label_components': [_ctx, _i, _vp, _i, _i, _i, _i, _d, _vp, _vp, _i, _vp],
     'uocr_masked_crop': [_ctx, _i, _vp, _vp] + [_i] * 10 + [_vp, _i, _i],
     'uocr_ctx_last_label': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
+    'uocr_label_batch': [_ctx, _i, _i, C.POINTER(_vp)] + [C.POINTER(_i)] * 4 + [_i, _d, C.POINTER(_vp), _vp, _i, _vp],
+    'uocr_ctx_last_label_batch': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     'uocr_char_label': [_ctx, _i, _i, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _i, _i, _i, C.POINTER(_vp),
                         C.POINTER(_vp)],
     'uocr_ctx_last_char_label': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],

@@ -39,6 +39,9 @@ centres of mass: which bottom belongs to which top, which way the text runs, the
 union of its two components' boxes (:494-502); every companion array is cut to it unmasked, turned by a multiple of 90
 degrees so that the text reads left to right, zoomed to 32 rows at order 0 and zero-padded to 8 columns (:504-523).  All
 lines of all paragraphs and all arrays of a page are ONE kernel call (nn/ops.py: line_crop); there is no worker pool.
+labelling='page' labels the masks of ALL paragraphs of the page in one call (nn/ops.py: label_batch): both channels of
+every mask are read in place, no split, one launch chain and one readback of a few rows per mask, instead of one split,
+two labelling calls and four readbacks per paragraph.  The default stays 'paragraph'.
 
 PredToText is the reference's PredToText (interpreter/interpreter.py:574-614): the Char net's raw output of every line,
 (W, N_CHARS) with one row per column window, becomes the line's text.  Per row the columns that EQUAL the row's maximum
@@ -224,27 +227,40 @@ class CropAndRotateParagraphs:
 
 
 class CropLines:
-    def __init__(self, zoomed_height=CHAR_INPUT_HEIGHT, minimal_width=CHAR_FIXED_WIDTH, max_components=4096):
+    def __init__(self, zoomed_height=CHAR_INPUT_HEIGHT, minimal_width=CHAR_FIXED_WIDTH, max_components=4096,
+                 labelling='paragraph'):
+        """labelling: 'paragraph' labels the two masks of every paragraph in calls of their own, 'page' the masks of all
+        paragraphs in ONE label_batch call"""
+        if labelling not in ('paragraph', 'page'):
+            raise ValueError(f"CropLines: labelling must be 'paragraph' or 'page', got {labelling!r}")
         self.zoomed_height, self.minimal_width = zoomed_height, minimal_width    # (None: no zoom / no padding, :511, :516)
-        self.max_components = max_components
+        self.max_components, self.labelling = max_components, labelling
 
     def find_lines(self, masks):
         """per paragraph (rotation, [(y0, x0, height, width) per line in reading order]) from masks[p]: (1, H, W, 2);
         (None, []) for a paragraph where the reference would raise"""
-        components = []
-        for mask in masks:
-            _, h, w, _ = mask.shape
-            top, bottom = ops.split(mask, [(1, h, w, 1), (1, h, w, 1)])
-            components.append((ops.label_components(top, 'mean_max', self.max_components),
-                               ops.label_components(bottom, 'mean_max', self.max_components)))
+        if self.labelling == 'page':
+            entries = [(mask, channel) for mask in masks for channel in (0, 1)]
+            both = ops.label_batch(entries, 'mean_max', self.max_components)
+            tables = [(top.center_of_mass, top.boxes, bottom.center_of_mass, bottom.boxes)
+                      for top, bottom in zip(both[0::2], both[1::2])]
+        else:
+            components = []
+            for mask in masks:
+                _, h, w, _ = mask.shape
+                top, bottom = ops.split(mask, [(1, h, w, 1), (1, h, w, 1)])
+                components.append((ops.label_components(top, 'mean_max', self.max_components),
+                                   ops.label_components(bottom, 'mean_max', self.max_components)))
+            tables = [(top.center_of_mass[0], top.boxes[0], bottom.center_of_mass[0], bottom.boxes[0])
+                      for top, bottom in components]                # (the component tables: the only host traffic)
         found = []
-        for top, bottom in components:                              # (the component tables: the only host traffic)
-            arranged = arrange_lines(top.center_of_mass[0], bottom.center_of_mass[0])
+        for top_centers, top_boxes, bottom_centers, bottom_boxes in tables:
+            arranged = arrange_lines(top_centers, bottom_centers)
             if arranged is None:
                 found.append((None, []))
             else:
                 top_ids, bottom_ids, rotation = arranged
-                found.append((rotation, line_boxes(top.boxes[0], bottom.boxes[0], top_ids, bottom_ids)))
+                found.append((rotation, line_boxes(top_boxes, bottom_boxes, top_ids, bottom_ids)))
         return found
 
     def __call__(self, masks, arrays):

@@ -259,15 +259,18 @@ def make_paragraph_crop_component(find_rotation=False, progress_tracker=None, so
 
 
 def make_line_crop_component(progress_tracker=None, mask='cropped_line', sources=('cropped_monochrome', 'cropped_char'),
-                             targets=('cropped_2_monochrome', 'cropped_2_char'), empty_page_ok=False):
+                             targets=('cropped_2_monochrome', 'cropped_2_char'), empty_page_ok=False,
+                             line_labelling='paragraph'):
     """model.py:595-612 (make_line_crop_component) as a device component: context[mask][paragraph] is the paragraph's
     (1, H, W, 2) line mask (the reference reads it as `line_pred_cpu`, in TRAIN_CHAR the renamed `cropped_line_cpu`,
     :635-637), context[source][paragraph] a companion array; context[target][paragraph][line] becomes the line cut out
     of it, turned upright, zoomed to CHAR_INPUT_HEIGHT rows and padded to CHAR_FIXED_WIDTH columns
     (my_model/crop.py: CropLines).  One kernel call for the page; the host reads the component tables only.
-    empty_page_ok: a missing context[mask] is a page without paragraphs (a LineSelector that met none files nothing)."""
+    empty_page_ok: a missing context[mask] is a page without paragraphs (a LineSelector that met none files nothing).
+    line_labelling: 'paragraph' labels the two masks of every paragraph in calls of their own, 'page' all masks of the
+    page in ONE label_batch call with one readback (my_model/crop.py: CropLines)"""
     from .crop import CropLines
-    crop_lines = CropLines(CHAR_INPUT_HEIGHT, CHAR_FIXED_WIDTH)
+    crop_lines = CropLines(CHAR_INPUT_HEIGHT, CHAR_FIXED_WIDTH, labelling=line_labelling)
     if len(sources) != len(targets):
         raise ValueError(f'make_line_crop_component: {len(sources)} sources for {len(targets)} targets')
 
@@ -276,7 +279,7 @@ def make_line_crop_component(progress_tracker=None, mask='cropped_line', sources
         masks = context.get(mask, []) if empty_page_ok else context[mask]
         context.update(zip(targets, crop_lines(masks, [context[source] for source in sources])))
 
-    return RawFunctionComponent(line_crop)
+    return RawFunctionComponent(line_crop, crop_lines)
 
 
 class LineSelector(IterableSelector):
@@ -446,7 +449,7 @@ def make_train_char_context_maker():
 
 
 def make_train_char_system(input_shape, optimizer=None, progress_tracker=None, weights=None, find_rotation=False,
-                           rotation_search='host'):
+                           rotation_search='host', line_labelling='paragraph'):
     """model.py:632-645: the reference's TRAIN_CHAR system built with find_rotation=False (or, with find_rotation=True,
     as the reference builds it: CropAndRotateParagraphs in the ParagraphCrop slot, its angle search on the host or, with
     rotation_search='device', on the device), minus its rename and move
@@ -458,18 +461,20 @@ def make_train_char_system(input_shape, optimizer=None, progress_tracker=None, w
                      cropped_char: context['cropped_2_monochrome'][p][l], ['cropped_2_char'][p][l]
       CharLabel      context['char_labels'][p][l] from cropped_2_char
       Char           one step per line through a CharSelector; predictions at context['char_pred'][p][l]
-    input_shape is the Char net's, (batch, *, width, channels): its height is CHAR_INPUT_HEIGHT."""
+    input_shape is the Char net's, (batch, *, width, channels): its height is CHAR_INPUT_HEIGHT.  line_labelling:
+    'paragraph' or 'page', how LineCrop labels its masks (make_line_crop_component)."""
     paragraph_crop = make_paragraph_crop_component(find_rotation, progress_tracker, ('monochrome_pred', 'line', 'char'),
                                                    ('cropped_monochrome', 'cropped_line', 'cropped_char'), rotation_search)
     model = _make_net('Char', input_shape, optimizer, progress_tracker, weights)
     char = ModelComponent('Char', model, CharSelector('cropped_2_monochrome', 'char_labels', 'char_pred'),
                           delist_result=True)
-    components = [paragraph_crop, make_line_crop_component(progress_tracker),
+    components = [paragraph_crop, make_line_crop_component(progress_tracker, line_labelling=line_labelling),
                   make_char_label_component(progress_tracker), char]
     return ModelSystem(components), {'Char': model}, ['ParagraphCrop', 'LineCrop', 'CharLabel', 'Char']
 
 
-def make_predict_system(input_shape, progress_tracker=None, weights=None, find_rotation=True, rotation_search='host'):
+def make_predict_system(input_shape, progress_tracker=None, weights=None, find_rotation=True, rotation_search='host',
+                        line_labelling='paragraph'):
     """model.py:688-717: the reference's PREDICT system without its rename and move components -- a page goes in as
     context['monochrome_X'] (1, H, W, 1), H and W multiples of 16 (make_divisible_by), and context['text'][p][l] comes
     out.  No array visits the host between the stages: only the component tables, the probe extents of the rotation
@@ -487,7 +492,8 @@ def make_predict_system(input_shape, progress_tracker=None, weights=None, find_r
       PredToText     text[p][l] from char_pred
     The nets are built for input_shape and take every size they meet afterwards (crops are multiples of 16, lines 32
     rows high and at least 8 columns wide).  rotation_search: 'host' walks the 13 rounds of the angle search on the
-    host, a readback per round; 'device' makes it one call and one readback per page (my_model/crop.py)."""
+    host, a readback per round; 'device' makes it one call and one readback per page (my_model/crop.py).
+    line_labelling: 'paragraph' or 'page', how LineCrop labels its masks (make_line_crop_component)."""
     models = {name: _make_net(name, shape, None, progress_tracker, weights)
               for name, shape in (('Monochrome', input_shape), ('Paragraph', input_shape), ('Line', input_shape),
                                   ('Char', (input_shape[0], CHAR_INPUT_HEIGHT, 64, 1)))}
@@ -501,7 +507,7 @@ def make_predict_system(input_shape, progress_tracker=None, weights=None, find_r
                                                 rotation_search),
                   net['Line'],
                   make_line_crop_component(progress_tracker, 'line_pred', ('cropped_monochrome',), ('cropped_2_monochrome',),
-                                           empty_page_ok=True),
+                                           empty_page_ok=True, line_labelling=line_labelling),
                   net['Char'], make_pred_to_text_component(progress_tracker, lines='cropped_2_monochrome')]
     return (ModelSystem(components), models,
             ['Monochrome', 'Paragraph', 'ParagraphCrop', 'Line', 'LineCrop', 'Char', 'PredToText'])

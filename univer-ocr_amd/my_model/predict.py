@@ -2,7 +2,7 @@
 on one page.  Image file input stays with the caller: `predict_text` takes the page as an array,
 `main` an .npy file.
 
-    python -m univer_ocr_amd.my_model.predict page.npy [--weights model_weights.json] [--device-search]
+    python -m univer_ocr_amd.my_model.predict page.npy [--weights model_weights.json] [--device-search] [--page-line-labels]
 """
 import json
 
@@ -12,10 +12,11 @@ from ..nn.gpu import CP
 from .model import make_divisible_by, make_predict_system
 
 
-def load_model_system(input_shape, weights_path=None, find_rotation=True, rotation_search='host'):
+def load_model_system(input_shape, weights_path=None, find_rotation=True, rotation_search='host', line_labelling='paragraph'):
     """predict.py:12-23: the PREDICT system with the weights of `weights_path` (a model_weights.json); a missing file,
     or none, leaves the fresh weights in place.  rotation_search: 'host' or 'device', where the angle search of the
-    paragraphs walks its rounds (make_predict_system)."""
+    paragraphs walks its rounds; line_labelling: 'paragraph' or 'page', whether LineCrop labels the line masks paragraph
+    by paragraph or all in one call (make_predict_system)."""
     weights = {}
     if weights_path is not None:
         try:
@@ -24,11 +25,12 @@ def load_model_system(input_shape, weights_path=None, find_rotation=True, rotati
         except OSError:
             print(f'No {weights_path} file found')
     model_system, _, _ = make_predict_system(input_shape, weights=weights, find_rotation=find_rotation,
-                                             rotation_search=rotation_search)
+                                             rotation_search=rotation_search, line_labelling=line_labelling)
     return model_system
 
 
-def predict_text(image, model_system=None, weights_path=None, find_rotation=True, context=None, rotation_search='host'):
+def predict_text(image, model_system=None, weights_path=None, find_rotation=True, context=None, rotation_search='host',
+                 line_labelling='paragraph'):
     """predict.py:48-59: `image` is one page, (1, H, W, 1) with values in [0, 1] as the reference's encode_X leaves
     them.  It is framed to multiples of 16 (make_divisible_by), moved to the device and run through `model_system`
     (default: load_model_system for the framed shape).  Returns context['text']: text[paragraph][line], a str each.
@@ -38,7 +40,7 @@ def predict_text(image, model_system=None, weights_path=None, find_rotation=True
         raise ValueError(f'predict_text: the page must have shape (1, H, W, 1), got {image.shape}')
     X = make_divisible_by(image, 16, 16)
     if model_system is None:
-        model_system = load_model_system(X.shape, weights_path, find_rotation, rotation_search)
+        model_system = load_model_system(X.shape, weights_path, find_rotation, rotation_search, line_labelling)
     context = {} if context is None else context
     context['monochrome_X'] = CP.copy(X)
     model_system.predict(context)
@@ -53,13 +55,16 @@ def main(argv=None):
     parser.add_argument('--no-rotation', action='store_true', help='cut the paragraphs upright, without the rotation search')
     parser.add_argument('--device-search', action='store_true',
                         help='the angle search of the paragraphs in one call on the device, not round by round on the host')
+    parser.add_argument('--page-line-labels', action='store_true',
+                        help='the line masks of all paragraphs of the page labelled in one call, not paragraph by paragraph')
     args = parser.parse_args(argv)
     page = np.load(args.page, allow_pickle=False)
     if page.ndim == 2:
         page = page[None, :, :, None]
     CP.use_gpu()
     for paragraph in predict_text(page, weights_path=args.weights, find_rotation=not args.no_rotation,
-                                  rotation_search='device' if args.device_search else 'host'):
+                                  rotation_search='device' if args.device_search else 'host',
+                                  line_labelling='page' if args.page_line_labels else 'paragraph'):
         for line in paragraph:
             print(line)
         print()

@@ -179,6 +179,14 @@ class Runtime:
         self.call('uocr_ctx_last_label', *[C.byref(x) for x in v])
         return tuple(x.value for x in v)
 
+    def last_label_batch(self):
+        """(tile rows, tile columns, entries per launch group, kernel launches) of the most recent uocr_label_batch call
+        on the current lane (uocr_ctx_last_label_batch); all 0 before the first."""
+        import ctypes as C
+        v = [C.c_int() for _ in range(4)]
+        self.call('uocr_ctx_last_label_batch', *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
     def last_char_label(self):
         """(columns per vote block, elements per statistics chunk, lines per launch, kernel launches) of the most recent
         uocr_char_label call on the current lane (uocr_ctx_last_char_label); all 0 before the first."""

@@ -596,6 +596,88 @@ def label_components(x, threshold='mean', max_components=4096):
     return Components(labels, table, count, max_components)
 
 
+class EntryComponents:
+    """Result of label_batch for ONE entry, on the host already: `count` (an int), `table` int64 (count, 8) = first
+    pixel, area, y0, y1, x0, x1, sum of y, sum of x, and `boxes` (count, 4), `area` (count,), `center_of_mass`
+    (count, 2) as Components has them per image.  `labels`: the int32 (H, W) DeviceArray, or None where none was asked
+    for."""
+
+    def __init__(self, count, table, labels=None):
+        self.count, self.table, self.labels = int(count), table, labels
+
+    @property
+    def boxes(self):
+        return self.table[:, 2:6]
+
+    @property
+    def area(self):
+        return self.table[:, 1]
+
+    @property
+    def center_of_mass(self):
+        return self.table[:, 6:8] / np.maximum(self.table[:, 1:2], 1)
+
+
+def _label_batch_call(entries, mode, value, cap, planes):
+    """ONE uocr_label_batch call with room for `cap` rows per entry and ONE device-to-host copy: the counts sit at the
+    head of the buffer the tables follow in.  planes: the label planes to write, or None.  Returns (counts, [the first
+    min(count, cap) rows of every entry])."""
+    n = len(entries)
+    arrays = [a for a, _ in entries]
+    head = (4 * n + 7) & ~7                                        # (the tables are int64)
+    out = CP.empty((head + n * cap * 64,), np.uint8)
+    _rt().call('uocr_label_batch', _shared_code(arrays, 'label_batch', 'a dtype'), n, _pointers(arrays),
+               *(_ints([a.shape[d] for a in arrays]) for d in (1, 2, 3)), _ints([ch for _, ch in entries]), mode, value,
+               _pointers(planes) if planes is not None else None, C.c_void_p(out.ptr + head), cap, C.c_void_p(out.ptr))
+    host = out.numpy()
+    counts = host[:4 * n].view(np.int32)
+    tables = host[head:].view(np.int64).reshape(n, cap, 8)
+    return counts, [tables[i, :min(int(count), cap)].copy() for i, count in enumerate(counts)]
+
+
+def label_batch(entries, threshold='mean', max_components=4096, cap=256, labels=False):
+    """Connected components of a flat list of entries (array, channel): channel `channel` of the (1, H, W, C) DeviceArray
+    `array`, read in place, thresholded at its OWN mean ('mean', interpreter.py:16-21), (mean + max) / 2 ('mean_max',
+    :437-438) or at a number, whatever the sizes of the entries.  Returns one EntryComponents per entry.  ONE
+    uocr_label_batch call with room for `cap` components per entry and ONE device-to-host copy of the counts and those
+    rows (64 bytes a row); the entries that hold more, up to max_components, are repeated in ONE second call with the
+    room their counts ask for; an entry with more than max_components raises HipError.  labels=True also writes every
+    entry's int32 (H, W) label plane (EntryComponents.labels).  No call for an empty list."""
+    entries = [(a, int(channel)) for a, channel in entries]
+    for a, channel in entries:
+        if not isinstance(a, DeviceArray) or a.ndim != 4 or a.shape[0] != 1:
+            raise ValueError(f'label_batch: expected (1, H, W, C) device arrays, got {getattr(a, "shape", type(a))}')
+        if not 0 <= channel < a.shape[3]:
+            raise ValueError(f'label_batch: channel {channel} of an array of shape {a.shape}')
+        if a.shape[1] < 1 or a.shape[2] < 1:
+            raise ValueError(f'label_batch: an empty array, {a.shape}')
+    if isinstance(threshold, str):
+        if threshold not in ('mean', 'mean_max'):
+            raise ValueError(f"label_batch: threshold must be 'mean', 'mean_max' or a number, got {threshold!r}")
+        mode, value = (hiplib.THRESH_MEAN if threshold == 'mean' else hiplib.THRESH_MEAN_MAX), 0.0
+    else:
+        mode, value = hiplib.THRESH_VALUE, float(threshold)
+    max_components, cap = int(max_components), int(cap)
+    if max_components < 0 or cap < 0:
+        raise ValueError(f'label_batch: max_components = {max_components}, cap = {cap}')
+    if not entries:
+        return []
+    _shared_code([a for a, _ in entries], 'label_batch', 'a dtype')
+    cap = min(cap, max_components)
+    planes = [CP.empty(a.shape[1:3], np.int32) for a, _ in entries] if labels else None
+    counts, tables = _label_batch_call(entries, mode, value, cap, planes)
+    if int(counts.max()) > max_components:
+        raise HipError(f'label_batch: an entry has {int(counts.max())} components, more than max_components = {max_components}')
+    longer = [i for i, count in enumerate(counts) if count > cap]
+    if longer:
+        again, full = _label_batch_call([entries[i] for i in longer], mode, value, max(int(counts[i]) for i in longer), None)
+        assert all(again[k] == counts[i] for k, i in enumerate(longer))
+        for k, i in enumerate(longer):
+            tables[i] = full[k]
+    return [EntryComponents(count, table, planes[i] if labels else None)
+            for i, (count, table) in enumerate(zip(counts, tables))]
+
+
 def masked_crop(array, components, image_index, k, divisible_by=None):
     """Component k (1-based) of image `image_index`: array * (labels == k) cut to the component's box
     (interpreter.py:304-308), as a new (1, h, w, C) DeviceArray.  divisible_by=(y, x) also adds make_divisible_by's zero
