@@ -64,8 +64,8 @@ def cdiv(a, b):
     return (a + b - 1) // b
 
 
-# ---- the host rules (Python copies of strip_bwd_launch, uocr_pair_strip_fwd_f32, uocr_pair_strip_fwd_f16,
-# wave_bwd_launch, uocr_pair_strip_bwd_f16) ------------------------------------------------------------------------------
+# ---- the host rules (independent Python copies of pair_block_geometry, pair_bands_per_cu, pair_wave_geometry and
+# pair_bands_rounds of conv_pair_strip.h, and of how the five launchers combine them) ------------------------------------
 def block_geometry(w, g=4, max_waves=8):
     """cooperative block: waves, computed columns, column blocks (overlapping by two columns)"""
     cols = 16 * g

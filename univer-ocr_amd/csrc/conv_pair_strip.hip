@@ -22,6 +22,8 @@
 // by one row of d_a1 on each side (recomputed, 10 of 18 MFMAs), column blocks by one column on each side.
 // Per group of 16 positions: 18 MFMAs (Z^T 3, S^T 3, dW1^T 4, dW2^T 4, U^T 4), ~27 vector and ~11 LDS
 // instructions (tile kernels: 58 / 19 + the 9-tap gather).  Deterministic: no atomics, fixed summation order.
+// What these kernels share with the binary16 ones -- LDS layouts, row descriptors, the block reduction of the weight
+// gradients, and the host rules of every launch form (block / strip geometry, bands) -- is in conv_pair_strip.h.
 // hipcc-flags: -mllvm -amdgpu-mfma-vgpr-form=1 -fno-slp-vectorize
 #include <algorithm>
 #include <type_traits>
@@ -119,12 +121,8 @@ __global__ __launch_bounds__(G <= 2 ? 1024 : 512) void pair_strip_bwd_kernel(con
         goff[g] = max(wc0 + 16 * g + n - sh, 0) * 4;
     }
     const float xkeep = wc0 + n + sh >= 0 ? 1.f : 0.f, gkeep = wc0 + n - sh >= 0 ? 1.f : 0.f;
-    const unsigned row_bytes = (unsigned)wd * 4u;
-    auto row_rsrc = [&](const float* base, int row) {
-        const bool in = row >= 0 && row < h;
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base + (size_t)min(max(row, 0), h - 1) * wd), 0,
-                                                 in ? row_bytes : 0u, 0x00020000);
-    };
+    const unsigned row_bytes = (unsigned)wd * (unsigned)sizeof(float);
+    const RowRsrc<float> row_rsrc{h, wd, row_bytes};
 
     // ---- state ------------------------------------------------------------------------------------------------
     float xw[G][3], gw[G][3];                          // rolling row windows, index = ring slot
@@ -333,32 +331,8 @@ __global__ __launch_bounds__(G <= 2 ? 1024 : 512) void pair_strip_bwd_kernel(con
     }
 
     // ---- block reduction of the weight gradients -> partial[block][PAIR_NPART] ----------------------------------
-    __syncthreads();
-    float* red = lds;                                  // [nw][PAIR_NPART]
-    {
-        const f32x4 s1 = acc1[0] + acc1[1], s2 = acc2[0] + acc2[1];
-        float* rw = red + wv * PAIR_NPART;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            rw[(4 * kq + i) * 16 + n] = s1[i];
-            rw[256 + (4 * kq + i) * 16 + n] = s2[i];
-        }
-        float b2 = 0.f;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const int c = wc0 + 16 * g + n;
-            if (kq == 1 && c >= own_lo && c < own_hi) b2 += db2acc[g];
-        }
-        b2 = wave_reduce_sum(b2);
-        if (lane == 0) rw[512] = b2;
-    }
-    __syncthreads();
-    const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    for (int i = tid; i < PAIR_NPART; i += blockDim.x) {
-        float v = 0.f;
-        for (int w = 0; w < nw; ++w) v += red[w * PAIR_NPART + i];
-        partial[blk * PAIR_NPART + i] = v;
-    }
+    PAIR_STRIP_REDUCE_TO_PARTIAL(G, lds, partial, ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, acc1, acc2,
+                                 db2acc, tid, lane, n, kq, wv, nw, wc0, own_lo, own_hi);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -419,11 +393,10 @@ __global__ __launch_bounds__(512) void pair_strip_fwd_kernel(const float* __rest
 #pragma unroll
     for (int g = 0; g < G; ++g) xoff[g] = max(wc0 + 16 * g + n + sh, 0) * 4;
     const float xkeep = wc0 + n + sh >= 0 ? 1.f : 0.f;
-    const unsigned row_bytes = (unsigned)wd * 4u;
+    const unsigned row_bytes = (unsigned)wd * (unsigned)sizeof(float);
+    const RowRsrc<float> row_rsrc{h, wd, row_bytes};
     auto load_row = [&](int row, float (&xn)[G]) {
-        const bool in = row >= 0 && row < h;
-        const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb + (size_t)min(max(row, 0), h - 1) * wd), 0,
-                                                          in ? row_bytes : 0u, 0x00020000);
+        const auto rx = row_rsrc(xb, row);
 #pragma unroll
         for (int g = 0; g < G; ++g)
             xn[g] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, xoff[g], 0, 0));
@@ -622,42 +595,26 @@ int strip_bwd_launch(uocr_ctx* ctx, const float* x, const float* y, const float*
                      const float* b1, const float* w2, float* dw1, float* db1, float* dw2, float* db2,
                      float* dx, int n, int h, int w, float pad1, int use_b1, int use_b2, float alpha,
                      bool sig, int accumulate, float unscale) {
-    const int nw = std::min(MAXW, (w + Strip<G>::COLS - 1) / Strip<G>::COLS);
-    const int bwc = nw * Strip<G>::COLS;
-    const int nbx = w <= bwc ? 1 : 1 + (w - bwc + (bwc - 2) - 1) / (bwc - 2);
-    // bands: about one block per CU (a block of 8 waves holds 126 KB of LDS), rows per band a multiple of 3 + 1
-    // so that the t = r0-1 .. r1 steps fill whole batches of three
-    int bands = std::max(1, (ctx->cu_count + n * nbx - 1) / (n * nbx));
-    if (ctx->opt_pair_band > 0) bands = (h + ctx->opt_pair_band - 1) / ctx->opt_pair_band;
-    int band_h = std::max(4, (h + bands - 1) / bands);
-    band_h = std::min(h, band_h);
-    bands = (h + band_h - 1) / band_h;
+    const auto [nw, bwc, nbx] = pair_block_geometry(w, Strip<G>::COLS, MAXW);
+    // bands: about one block per CU (a block of 8 waves holds 126 KB of LDS)
+    const auto [bands, band_h] = pair_bands_per_cu(h, (ctx->cu_count + n * nbx - 1) / (n * nbx), ctx->opt_pair_band);
     const size_t nblocks = (size_t)nbx * bands * n;
     UOCR_REQUIRE(ctx, bands <= 65535 && n <= 65535);
     int rc = UOCR_OK;
     float* partial = uocr_partial_buffer(ctx, nblocks * PAIR_NPART * sizeof(float), &rc);
     if (rc != UOCR_OK) return rc;
     const size_t lds = strip_lds_bytes<G>(nw, dx != nullptr);
-    auto launch = [&](auto kernel) -> int {
-        static bool attr_set = false;      // (per instantiation) allow more than 64 KB of dynamic LDS
-        if (!attr_set) {
-            UOCR_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(kernel, dim3(nbx, bands, n), dim3(nw * 64), lds, ctx->stream, x, y, dy, w1, b1, w2, partial,
-                           dx, h, w, band_h, pad1, use_b1, alpha);
-        UOCR_LAUNCH_CHECK(ctx);
-        return UOCR_OK;
-    };
+    const dim3 grid(nbx, bands, n), block(nw * 64);
     const bool plain = nbx == 1 && w == bwc && pad1 == 0.f;      // MODE 0: no position is ever masked
     uocr_note_pair(ctx, 2, G, plain ? 0 : 1, 0, nw, nbx, bands, band_h);
-    auto pick = [&](auto dxtag, auto sigtag) -> int {
+    rc = pair_dx_sig(dx != nullptr, sig, [&](auto dxtag, auto sigtag) -> int {
         constexpr bool D = decltype(dxtag)::value, S = decltype(sigtag)::value;
-        return plain ? launch(pair_strip_bwd_kernel<G, D, S, 0>) : launch(pair_strip_bwd_kernel<G, D, S, 1>);
-    };
-    if (dx) rc = sig ? pick(std::true_type{}, std::true_type{}) : pick(std::true_type{}, std::false_type{});
-    else rc = sig ? pick(std::false_type{}, std::true_type{}) : pick(std::false_type{}, std::false_type{});
+        auto launch = [&](auto mode) -> int {
+            return pair_launch_big_lds<pair_strip_bwd_kernel<G, D, S, decltype(mode)::value>>(
+                ctx, grid, block, lds, x, y, dy, w1, b1, w2, partial, dx, h, w, band_h, pad1, use_b1, alpha);
+        };
+        return plain ? launch(phase_t<0>{}) : launch(phase_t<1>{});
+    });
     if (rc != UOCR_OK) return rc;
     return uocr_pair_strip_finish(ctx, partial, dw1, db1, dw2, db2, (int)nblocks, use_b1, use_b2, accumulate, unscale);
 }
@@ -680,14 +637,9 @@ int uocr_pair_strip_fwd_f32(uocr_ctx* ctx, const float* x, const float* w1, cons
                             const float* b2, float* y, int n, int h, int w, float pad1, int use_b1, int use_b2,
                             float alpha, int act2) {
     constexpr int G = 4;
-    const int nw = std::min(8, (w + Strip<G>::COLS - 1) / Strip<G>::COLS);
-    const int bwc = nw * Strip<G>::COLS;
-    const int nbx = w <= bwc ? 1 : 1 + (w - bwc + (bwc - 2) - 1) / (bwc - 2);
+    const auto [nw, bwc, nbx] = pair_block_geometry(w, Strip<G>::COLS, 8);
     // the forward block holds 38 KB of LDS and ~100 registers: two blocks per CU
-    int bands = std::max(1, (2 * ctx->cu_count + n * nbx - 1) / (n * nbx));
-    if (ctx->opt_pair_band > 0) bands = (h + ctx->opt_pair_band - 1) / ctx->opt_pair_band;
-    int band_h = std::min(h, std::max(4, (h + bands - 1) / bands));
-    bands = (h + band_h - 1) / band_h;
+    const auto [bands, band_h] = pair_bands_per_cu(h, (2 * ctx->cu_count + n * nbx - 1) / (n * nbx), ctx->opt_pair_band);
     UOCR_REQUIRE(ctx, bands <= 65535 && n <= 65535);
     const size_t lds = sizeof(float) * NSLOT * NPLANE * (bwc + 16);
     const bool plain = nbx == 1 && w == bwc && pad1 == 0.f;

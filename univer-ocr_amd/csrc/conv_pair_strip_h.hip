@@ -1,5 +1,7 @@
 // The Monochrome block on column strips, binary16 storage (UOCR_F16): see conv_pair_strip.hip for the float32 kernels
 // and the idea (reference: my_model/model.py:108-135, nn/layers/convolutional.py:62-145, nn/layers/layers.py:377-418).
+// The row descriptors, the block reduction of the weight gradients and the host rules of the launch forms (block /
+// strip geometry, bands, tag dispatch, the launch with more than 64 KB of LDS) are shared: conv_pair_strip.h.
 // hipcc-flags: -mllvm -amdgpu-mfma-vgpr-form=1 -fno-slp-vectorize
 #include <algorithm>
 #include <type_traits>
@@ -51,9 +53,10 @@ __device__ __forceinline__ uint32_t half_bits(float v) {
     return (uint32_t)__builtin_bit_cast(unsigned short, (_Float16)v);
 }
 
-// MODE 0: no position is ever masked; MODE 2: a column block between other blocks, all of its computed columns inside
-// the image: only its first and last computed column (owned by the neighbours) are taken out of the weight gradients
-// (two registers per row step); MODE 1: anything else, per-position selects.  bx0: first column block of this launch.
+// One block of cooperating waves that spans the image.  MODE 0: no position is ever masked; MODE 1: anything else
+// (computed columns beyond the image, padding value), per-position selects.  bx0 / nbx_total (first column block of the
+// launch, column blocks in all) are always 0 / 1: they stay because taking them out moved registers and instruction
+// counts of three MODE 1 instantiations (profiles/pair_strip_share.txt).
 template <int G, bool DX, bool SIG, int MODE>
 __global__ __launch_bounds__(512) void pair_strip_bwd_h_kernel(const _Float16* __restrict__ x,
                                                                const _Float16* __restrict__ yout,
@@ -128,15 +131,8 @@ __global__ __launch_bounds__(512) void pair_strip_bwd_h_kernel(const _Float16* _
         goff[g] = max(wc0 + 16 * g + n - sh, 0) * 2;
     }
     const uint32_t xkeep = wc0 + n + sh >= 0 ? 0xFFFFu : 0u, gkeep = wc0 + n - sh >= 0 ? 0xFFFFu : 0u;
-    const unsigned row_bytes = (unsigned)wd * 2u;
-    auto row_rsrc = [&](const _Float16* base, int row) {
-        const bool in = row >= 0 && row < h;
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(base + (size_t)min(max(row, 0), h - 1) * wd), 0,
-                                                 in ? row_bytes : 0u, 0x00020000);
-    };
-    // the two halo positions of MODE 2 (first computed column of the first wave, last of the last wave)
-    const bool halo_l = MODE == 2 && wv == 0 && bx > 0 && kq == 0;
-    const bool halo_r = MODE == 2 && wv == nw - 1 && !last_block && kq == 3;
+    const unsigned row_bytes = (unsigned)wd * (unsigned)sizeof(_Float16);
+    const RowRsrc<_Float16> row_rsrc{h, wd, row_bytes};
 
     // ---- state --------------------------------------------------------------------------------------------
     uint32_t xp0[G], xp1[G], gp0[G], gp1[G];           // windows: (row t-1, row t), (row t+1, 0)
@@ -248,19 +244,9 @@ __global__ __launch_bounds__(512) void pair_strip_bwd_h_kernel(const _Float16* _
                     dn[i] = owned ? d[i] : 0.f;
                 }
             }
-            if constexpr (MODE == 2) {
-                if (g == 0) {
-                    a[0] = halo_l ? 0.f : a[0];
-                    dn[0] = halo_l ? 0.f : dn[0];
-                }
-                if (g == G - 1) {
-                    a[3] = halo_r ? 0.f : a[3];
-                    dn[3] = halo_r ? 0.f : dn[3];
-                }
-            }
             a4[g] = pack4h(a[0], a[1], a[2], a[3]);
             dn4[g] = pack4h(dn[0], dn[1], dn[2], dn[3]);
-            d4[g] = (MODE == 1 || (MODE == 2 && (g == 0 || g == G - 1))) ? pack4h(d[0], d[1], d[2], d[3]) : dn4[g];
+            d4[g] = MODE == 1 ? pack4h(d[0], d[1], d[2], d[3]) : dn4[g];
             if constexpr (DX) {
                 _Float16* tsc = trs + g * TRSZH;
 #pragma unroll
@@ -346,32 +332,8 @@ __global__ __launch_bounds__(512) void pair_strip_bwd_h_kernel(const _Float16* _
         }
     }
 
-    __syncthreads();
-    float* red = lds;
-    {
-        const f32x4 s1 = acc1[0] + acc1[1], s2 = acc2[0] + acc2[1];
-        float* rw = red + wv * PAIR_NPART;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            rw[(4 * kq + i) * 16 + n] = s1[i];
-            rw[256 + (4 * kq + i) * 16 + n] = s2[i];
-        }
-        float b2 = 0.f;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const int c = wc0 + 16 * g + n;
-            if (kq == 1 && c >= own_lo && c < own_hi) b2 += db2acc[g];
-        }
-        b2 = wave_reduce_sum(b2);
-        if (lane == 0) rw[512] = b2;
-    }
-    __syncthreads();
-    const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * nbx_total + bx;
-    for (int i = tid; i < PAIR_NPART; i += blockDim.x) {
-        float v = 0.f;
-        for (int w = 0; w < nw; ++w) v += red[w * PAIR_NPART + i];
-        partial[blk * PAIR_NPART + i] = v;
-    }
+    PAIR_STRIP_REDUCE_TO_PARTIAL(G, lds, partial, ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * nbx_total + bx, acc1, acc2, db2acc,
+                                 tid, lane, n, kq, wv, nw, wc0, own_lo, own_hi);
 }
 
 // Images wider than one block of waves: INDEPENDENT waves.  Every wave is its own work item (strip s of 16*G computed
@@ -487,12 +449,8 @@ __global__ __launch_bounds__(256) void pair_wave_bwd_h_kernel(const _Float16* __
         goff[g] = max(wc0 + 16 * g + n - sh, 0) * 2;
     }
     const uint32_t xkeep = wc0 + n + sh >= 0 ? 0xFFFFu : 0u, gkeep = wc0 + n - sh >= 0 ? 0xFFFFu : 0u;
-    const unsigned row_bytes = (unsigned)wd * 2u;
-    auto row_rsrc = [&](const _Float16* base, int row) {
-        const bool in = row >= 0 && row < h;
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(base + (size_t)min(max(row, 0), h - 1) * wd), 0,
-                                                 in ? row_bytes : 0u, 0x00020000);
-    };
+    const unsigned row_bytes = (unsigned)wd * (unsigned)sizeof(_Float16);
+    const RowRsrc<_Float16> row_rsrc{h, wd, row_bytes};
     // the two halo positions (first / last computed column: owned by the neighbouring strips) as masks on the packed halves
     const uint32_t keep_l = (sidx > 0 && kq == 0) ? 0xFFFF0000u : 0xFFFFFFFFu;
     const uint32_t keep_r = (!last_strip && kq == 3) ? 0x0000FFFFu : 0xFFFFFFFFu;
@@ -717,32 +675,8 @@ __global__ __launch_bounds__(256) void pair_wave_bwd_h_kernel(const _Float16* __
         if constexpr (DX) flush_row(t0 - 3, 1);        // the row the last step (phase 2) wrote into slot (2+2) mod 3
     }
 
-    __syncthreads();
-    float* red = lds;
-    {
-        const f32x4 s1 = acc1[0] + acc1[1], s2 = acc2[0] + acc2[1];
-        float* rw = red + wv * PAIR_NPART;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            rw[(4 * kq + i) * 16 + n] = s1[i];
-            rw[256 + (4 * kq + i) * 16 + n] = s2[i];
-        }
-        float b2 = 0.f;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const int c = wc0 + 16 * g + n;
-            if (kq == 1 && c >= own_lo && c < own_hi) b2 += db2acc[g];
-        }
-        b2 = wave_reduce_sum(b2);
-        if (lane == 0) rw[512] = b2;
-    }
-    __syncthreads();
-    const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    for (int i = tid; i < PAIR_NPART; i += blockDim.x) {
-        float v = 0.f;
-        for (int w = 0; w < nw; ++w) v += red[w * PAIR_NPART + i];
-        partial[blk * PAIR_NPART + i] = v;
-    }
+    PAIR_STRIP_REDUCE_TO_PARTIAL(G, lds, partial, ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, acc1, acc2,
+                                 db2acc, tid, lane, n, kq, wv, nw, wc0, own_lo, own_hi);
 }
 
 }  // namespace
@@ -804,7 +738,8 @@ __global__ __launch_bounds__(256) void pair_wave_fwd_h_kernel(const _Float16* __
         keep_a[g] = wc0 + 16 * g + n < wd ? 0xFFFFFFFFu : 0u;
     }
     const uint32_t xkeep = wc0 + n + sh >= 0 ? 0xFFFFu : 0u;
-    const unsigned row_bytes = (unsigned)wd * 2u;
+    const unsigned row_bytes = (unsigned)wd * (unsigned)sizeof(_Float16);
+    const RowRsrc<_Float16> row_rsrc{h, wd, row_bytes};
     const unsigned y_off = (lane < COLS && wc0 + lane >= own_lo && wc0 + lane < own_hi) ? (unsigned)(wc0 + lane) * 2u : 0x7FFFFFFFu;
 
     u32x2 xp[G];
@@ -816,9 +751,7 @@ __global__ __launch_bounds__(256) void pair_wave_fwd_h_kernel(const _Float16* __
         for (int j = 0; j < 3; ++j) rr[g][j] = 0.f;
     }
     auto load_row = [&](int row, uint32_t (&xn)[G]) {
-        const bool in = row >= 0 && row < h;
-        const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(xb + (size_t)min(max(row, 0), h - 1) * wd), 0,
-                                                          in ? row_bytes : 0u, 0x00020000);
+        const auto rx = row_rsrc(xb, row);
 #pragma unroll
         for (int g = 0; g < G; ++g) xn[g] = __builtin_amdgcn_raw_buffer_load_b16(rx, xoff[g], 0, 0);
     };
@@ -927,23 +860,8 @@ int uocr_pair_strip_fwd_f16(uocr_ctx* ctx, const void* x, const float* w1, const
                             const float* b2, void* y, int n, int h, int w, float pad1, int use_b1, int use_b2,
                             float alpha, int act2) {
     constexpr int G = 4, COLS = 16 * G;
-    const int nstrips = w <= COLS ? 1 : 1 + (w - COLS + (COLS - 2) - 1) / (COLS - 2);
-    const int nw = std::min(4, nstrips);
-    const int blocks_x = (nstrips + nw - 1) / nw;
-    int bands = 1;
-    {
-        const long resident = 4L * ctx->cu_count;
-        double best = 1e30;
-        for (int b = 1; b <= std::max(1, h / 8); ++b) {
-            const int bh = (h + b - 1) / b;
-            const long blocks = (long)blocks_x * ((h + bh - 1) / bh) * n;
-            const double cost = (double)((blocks + resident - 1) / resident) * (bh + 2);
-            if (cost < best * 0.999) { best = cost; bands = (h + bh - 1) / bh; }
-        }
-        if (ctx->opt_pair_band > 0) bands = (h + ctx->opt_pair_band - 1) / ctx->opt_pair_band;
-    }
-    const int band_h = (h + bands - 1) / bands;
-    bands = (h + band_h - 1) / band_h;
+    const auto [nstrips, nw, blocks_x] = pair_wave_geometry(w, COLS);
+    const auto [bands, band_h] = pair_bands_rounds(n, h, blocks_x, 4L * ctx->cu_count, ctx->opt_pair_band);
     UOCR_REQUIRE(ctx, bands <= 65535 && n <= 65535);
     const size_t lds = sizeof(float) * nw * 3 * NPLANE * (COLS + 2);
     uocr_note_pair(ctx, 3, G, 0, ctx->opt_pair_pf == 0 ? 0 : ctx->opt_pair_pf == 1 ? 1 : 2, nw, blocks_x, bands, band_h);
@@ -962,30 +880,14 @@ int uocr_pair_strip_fwd_f16(uocr_ctx* ctx, const void* x, const float* w1, const
 namespace {
 
 // independent-wave launch (images wider than one cooperative block): strips of COLS computed columns every COLS - 2,
-// 4 strips per block, bands so that the blocks make whole rounds of what is resident at once -- a last round that is a
-// tenth full costs a full one.  G = 4: 187 registers, two blocks per CU; G = 2: four.
+// 4 strips per block, bands in whole rounds of what is resident.  G = 4: 187 registers, two blocks per CU; G = 2: four.
 template <int G>
 int wave_bwd_launch(uocr_ctx* ctx, const void* x, const void* y, const void* dy, const float* w1, const float* b1,
                     const float* w2, float* dw1, float* db1, float* dw2, float* db2, void* dx, int n, int h, int w,
                     float pad1, int use_b1, int use_b2, float alpha, bool sig, int accumulate, float unscale) {
     using L = StripH<G>;
-    const int nstrips = w <= L::COLS ? 1 : 1 + (w - L::COLS + (L::COLS - 2) - 1) / (L::COLS - 2);
-    const int nw = std::min(4, nstrips);
-    const int blocks_x = (nstrips + nw - 1) / nw;
-    int bands = 1;
-    {
-        const long resident = (G == 4 ? 2L : 4L) * ctx->cu_count;
-        double best = 1e30;
-        for (int b = 1; b <= std::max(1, h / 8); ++b) {
-            const int bh = (h + b - 1) / b;
-            const long blocks = (long)blocks_x * ((h + bh - 1) / bh) * n;
-            const double cost = (double)((blocks + resident - 1) / resident) * (bh + 2);
-            if (cost < best * 0.999) { best = cost; bands = (h + bh - 1) / bh; }
-        }
-        if (ctx->opt_pair_band > 0) bands = (h + ctx->opt_pair_band - 1) / ctx->opt_pair_band;
-    }
-    const int band_h = (h + bands - 1) / bands;
-    bands = (h + band_h - 1) / band_h;
+    const auto [nstrips, nw, blocks_x] = pair_wave_geometry(w, L::COLS);
+    const auto [bands, band_h] = pair_bands_rounds(n, h, blocks_x, (G == 4 ? 2L : 4L) * ctx->cu_count, ctx->opt_pair_band);
     const size_t lds = std::max(sizeof(float) * (nw * ((L::XS + L::GS + 3 * G * TWSZ + 3) / 4 * 2 + 3 * NPLANE * (L::COLS + 2)) + G * XROWH / 2),
                                 sizeof(float) * nw * PAIR_NPART);
     const size_t nblocks = (size_t)blocks_x * bands * n;
@@ -994,22 +896,11 @@ int wave_bwd_launch(uocr_ctx* ctx, const void* x, const void* y, const void* dy,
     float* partial = uocr_partial_buffer(ctx, nblocks * PAIR_NPART * sizeof(float), &rc);
     if (rc != UOCR_OK) return rc;
     uocr_note_pair(ctx, 5, G, 0, 0, nw, blocks_x, bands, band_h);
-    auto run = [&](auto dxtag, auto sigtag) -> int {
-        constexpr bool D = decltype(dxtag)::value, S = decltype(sigtag)::value;
-        static bool attr_set = false;
-        if (!attr_set) {
-            UOCR_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(pair_wave_bwd_h_kernel<G, D, S>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((pair_wave_bwd_h_kernel<G, D, S>), dim3(blocks_x, bands, n), dim3(nw * 64), lds, ctx->stream,
-                           (const _Float16*)x, (const _Float16*)y, (const _Float16*)dy, w1, b1, w2, partial, (_Float16*)dx,
-                           h, w, band_h, pad1, use_b1, alpha, nstrips);
-        UOCR_LAUNCH_CHECK(ctx);
-        return UOCR_OK;
-    };
-    if (dx) rc = sig ? run(std::true_type{}, std::true_type{}) : run(std::true_type{}, std::false_type{});
-    else rc = sig ? run(std::false_type{}, std::true_type{}) : run(std::false_type{}, std::false_type{});
+    rc = pair_dx_sig(dx != nullptr, sig, [&](auto dxtag, auto sigtag) -> int {
+        return pair_launch_big_lds<pair_wave_bwd_h_kernel<G, decltype(dxtag)::value, decltype(sigtag)::value>>(
+            ctx, dim3(blocks_x, bands, n), dim3(nw * 64), lds, (const _Float16*)x, (const _Float16*)y, (const _Float16*)dy,
+            w1, b1, w2, partial, (_Float16*)dx, h, w, band_h, pad1, use_b1, alpha, nstrips);
+    });
     if (rc != UOCR_OK) return rc;
     return uocr_pair_strip_finish(ctx, partial, dw1, db1, dw2, db2, (int)nblocks, use_b1, use_b2, accumulate, unscale);
 }
@@ -1025,19 +916,15 @@ int uocr_pair_strip_bwd_f16(uocr_ctx* ctx, const void* x, const void* y, const v
                             bool sig, int accumulate, float unscale) {
     constexpr int G = 4;
     using L = StripH<G>;
-    const int nw = std::min(8, (w + L::COLS - 1) / L::COLS);
-    const int bwc = nw * L::COLS;
-    if (w > bwc) {
+    const auto [nw, bwc, nbx] = pair_block_geometry(w, L::COLS, 8);
+    if (w > bwc) {                                     // (nbx > 1)
         if (ctx->opt_pair_g == 2)
             return wave_bwd_launch<2>(ctx, x, y, dy, w1, b1, w2, dw1, db1, dw2, db2, dx, n, h, w, pad1, use_b1, use_b2, alpha,
                                       sig, accumulate, unscale);
         return wave_bwd_launch<4>(ctx, x, y, dy, w1, b1, w2, dw1, db1, dw2, db2, dx, n, h, w, pad1, use_b1, use_b2, alpha, sig,
                                   accumulate, unscale);
     }
-    int bands = std::max(1, (ctx->cu_count + n - 1) / n);
-    if (ctx->opt_pair_band > 0) bands = (h + ctx->opt_pair_band - 1) / ctx->opt_pair_band;
-    int band_h = std::min(h, std::max(4, (h + bands - 1) / bands));
-    bands = (h + band_h - 1) / band_h;
+    const auto [bands, band_h] = pair_bands_per_cu(h, (ctx->cu_count + n - 1) / n, ctx->opt_pair_band);
     const size_t nblocks = (size_t)bands * n;
     UOCR_REQUIRE(ctx, bands <= 65535 && n <= 65535);
     int rc = UOCR_OK;
@@ -1045,27 +932,18 @@ int uocr_pair_strip_bwd_f16(uocr_ctx* ctx, const void* x, const void* y, const v
     if (rc != UOCR_OK) return rc;
     const size_t ring = dx ? sizeof(float) * NSLOT * NPLANE * (bwc + 16) : 0;
     const size_t lds = std::max(sizeof(float) * ((nw * L::WAVE + 1) / 2) + ring, sizeof(float) * nw * PAIR_NPART);
-    auto launch = [&](auto kernel) -> int {
-        static bool attr_set = false;
-        if (!attr_set) {
-            UOCR_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(kernel, dim3(1, bands, n), dim3(nw * 64), lds, ctx->stream, (const _Float16*)x,
-                           (const _Float16*)y, (const _Float16*)dy, w1, b1, w2, partial, (_Float16*)dx, h, w, band_h, pad1,
-                           use_b1, alpha, 0, 1);
-        UOCR_LAUNCH_CHECK(ctx);
-        return UOCR_OK;
-    };
+    const dim3 grid(1, bands, n), block(nw * 64);
     const bool plain = w == bwc && pad1 == 0.f;
     uocr_note_pair(ctx, 4, G, plain ? 0 : 1, 0, nw, 1, bands, band_h);
-    auto run = [&](auto dxtag, auto sigtag) -> int {
+    rc = pair_dx_sig(dx != nullptr, sig, [&](auto dxtag, auto sigtag) -> int {
         constexpr bool D = decltype(dxtag)::value, S = decltype(sigtag)::value;
-        return plain ? launch(pair_strip_bwd_h_kernel<G, D, S, 0>) : launch(pair_strip_bwd_h_kernel<G, D, S, 1>);
-    };
-    if (dx) rc = sig ? run(std::true_type{}, std::true_type{}) : run(std::true_type{}, std::false_type{});
-    else rc = sig ? run(std::false_type{}, std::true_type{}) : run(std::false_type{}, std::false_type{});
+        auto launch = [&](auto mode) -> int {
+            return pair_launch_big_lds<pair_strip_bwd_h_kernel<G, D, S, decltype(mode)::value>>(
+                ctx, grid, block, lds, (const _Float16*)x, (const _Float16*)y, (const _Float16*)dy, w1, b1, w2, partial,
+                (_Float16*)dx, h, w, band_h, pad1, use_b1, alpha, 0, 1);
+        };
+        return plain ? launch(phase_t<0>{}) : launch(phase_t<1>{});
+    });
     if (rc != UOCR_OK) return rc;
     return uocr_pair_strip_finish(ctx, partial, dw1, db1, dw2, db2, (int)nblocks, use_b1, use_b2, accumulate, unscale);
 }
