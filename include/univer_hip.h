@@ -585,6 +585,34 @@ int uocr_pred_to_text(uocr_ctx* ctx, int dtype, int n_lines, const void* const* 
  * (all 0 before the first call) -- tests size their inputs from it */
 int uocr_ctx_last_pred_to_text(uocr_ctx* ctx, int* rows_per_block, int* lines_per_launch, int* launches);
 
+/* ---- the lines of a page in one strip (the Char net over all lines in one pass; the reference runs a pass per line,
+ * nn/model_system.py:150-154) ----
+ * A strip is (1, h, strip_w, c) in `dtype`; its columns are cut into SEGMENTS [x0[i], x0[i] + w[i]), i < n_lines, with GAPS
+ * in front of, between and behind them (a gap may have no column).  With 4 zero columns between neighbouring lines and the
+ * gaps set back to zero after every conv + LeakyReLU, the Char net (three convs of 3 columns with padding 1, then windows
+ * of 8 columns padded by 4 zero columns on the left and 3 on the right) gives every column of a line exactly what it gives
+ * it when the line is passed alone; the outer ends of the strip need no gap.
+ * Pack: segment i of the strip = src[i]: (1, h, w[i], c) in `dtype`, every gap = +0.0; EVERY element of the strip is
+ * written, the sources are only read.  src, w and x0 are HOST arrays of n_lines entries; src[i] and strip are device
+ * pointers.  A copy, no arithmetic: every element keeps its bits.
+ * UOCR_ERR_ARG for null pointers, pointers off their element's alignment, w[i] < 1, h, c or strip_w < 1, n_lines < 0 and
+ * segments that are not ascending, that overlap or that reach outside [0, strip_w); UOCR_ERR_DTYPE for an unknown dtype;
+ * UOCR_ERR_UNSUPPORTED for a strip row of more than 2^31 - 1 elements and for more blocks than one grid takes.  Nothing
+ * is written on any error; n_lines = 0 is UOCR_OK and launches nothing (the other arguments are not looked at).  One launch
+ * per 128 lines; no workspace, no atomics.  Asynchronous and capturable. */
+int uocr_pack_lines(uocr_ctx* ctx, int dtype, int n_lines, const void* const* src, const int* w, int h, int c,
+                    const int* x0, void* strip, int strip_w);
+/* Zero gaps, in place on x: (1, h, strip_w, c) in `dtype`: every element of every gap becomes +0.0 -- written, not
+ * multiplied: a NaN or an infinity there becomes 0 -- and no element of a segment is touched.  The work is proportional
+ * to the gaps, not to the tensor: only the columns of the gaps are visited.  x0 and w are HOST arrays of n_lines entries.
+ * Errors and n_lines = 0 as for uocr_pack_lines.  One launch per 128 gaps, none when no gap has a column; no workspace,
+ * no atomics.  Asynchronous and capturable. */
+int uocr_zero_gaps(uocr_ctx* ctx, int dtype, void* x, int h, int strip_w, int c, int n_lines, const int* x0, const int* w);
+/* sizes the last uocr_pack_lines or uocr_zero_gaps call on this ctx used: elements of an entry -- a line with the gap
+ * behind it, or a gap -- per block at most (whole rows of the entry, or one piece of a row that is longer), entries per
+ * launch, launches issued (all 0 before the first call) -- tests size their inputs from it */
+int uocr_ctx_last_pack_lines(uocr_ctx* ctx, int* elements_per_block, int* entries_per_launch, int* launches);
+
 /* ---- data parallel over the GPUs of one node: RCCL over xGMI ------------------------------------
  * The reference has no multi-GPU path; BASELINE.json adds one to the step loop my_model/trainer.py:213-233
  * -> nn/model_system.py:104-118 -> nn/models.py:250-254: between compute_loss_and_gradients and update_grads

@@ -1,4 +1,4 @@
-// What the batched page stages (line_crop.hip, char_label.hip, rotate.hip, pred_to_text.hip) share.  The entries of a call travel in by-value
+// What the batched page stages (line_crop.hip, char_label.hip, rotate.hip, pred_to_text.hip, pack_lines.hip) share.  The entries of a call travel in by-value
 // kernel arguments, a GROUP of at most `entries` per launch, next to the prefix sum of their block counts; a block finds
 // its entry by a binary search in it; contiguous ranges move as 16-byte accesses between a scalar head and tail.  The
 // descriptor structs stay with their kernels.  A launcher writes the block count of an entry ONCE, as a function `blocks`

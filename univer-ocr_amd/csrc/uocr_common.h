@@ -55,6 +55,7 @@ struct uocr_ctx {
     int rs_rounds, rs_paragraphs, rs_launches;             // uocr_ctx_last_rotation_search: rounds, paragraphs per launch and launch count of the last search
     int pt_rows, pt_lines, pt_launches;                    // uocr_ctx_last_pred_to_text: sizes and launch count of the last pred-to-text call
     int lb_th, lb_tw, lb_entries, lb_launches;             // uocr_ctx_last_label_batch: tile, entries per launch and launch count of the last batched labelling call
+    int pl_chunk, pl_entries, pl_launches;                 // uocr_ctx_last_pack_lines: sizes and launch count of the last pack-lines or zero-gaps call
     char err[512];
 };
 

@@ -346,6 +346,44 @@ class CharSelector(LineSelector):
         self._grown(per_line, self.line_id)[self.line_id] = pred
 
 
+class PackedLinesComponent(ModelComponent):
+    """The Char net over ALL lines of a page in one pass per strip (predict only; train and test stay one optimizer step
+    per line, the reference's semantics).  The lines the selector yields -- (1, CHAR_INPUT_HEIGHT, W, 1), W >=
+    CHAR_FIXED_WIDTH -- are laid side by side with `gap` zero columns between neighbours (ops.pack_layout, ops.pack_lines),
+    the model runs once on the strip with the gaps set back to zero after every conv + LeakyReLU
+    (Model.forward(keep_columns=...)), and the prediction of a line is the row range [x0, x0 + w) of the strip's (strip_w,
+    N_CHARS) output: a view that keeps the strip's output alive, filed where CharSelector.put files the per-line pass's.
+    Exact, not approximate: every column of a line sees what its own padding shows it alone.
+    max_columns: the widest strip; a page with more columns takes several passes."""
+
+    def __init__(self, name, model, selector, delist_result=False, gap=4, max_columns=32768):
+        ModelComponent.__init__(self, name, model, selector, delist_result)
+        self.gap, self.max_columns = gap, max_columns
+
+    def predict(self, context):
+        from ..nn import ops
+        from ..nn.gpu import DeviceArray
+        selector = self.selector
+        selector(context)
+        lines, places = [], []
+        for X in selector.get_X():
+            lines.append(X)
+            places.append((selector.paragraph_id, selector.line_id))
+        for a in lines:
+            if not isinstance(a, DeviceArray) or a.ndim != 4 or (a.shape[0], a.shape[1], a.shape[3]) != (1, CHAR_INPUT_HEIGHT, 1) \
+                    or a.shape[2] < CHAR_FIXED_WIDTH or a.dtype != lines[0].dtype:
+                raise ValueError(f'{self.name}: the lines of a page are (1, {CHAR_INPUT_HEIGHT}, W, 1) device arrays of one '
+                                 f'dtype, W >= {CHAR_FIXED_WIDTH}, got {getattr(a, "shape", type(a))} {getattr(a, "dtype", "")}')
+        for segments, strip_w in ops.pack_layout([a.shape[2] for a in lines], self.gap, self.max_columns):
+            strip = ops.pack_lines(lines, (segments, strip_w))
+            outputs = self.model.forward(strip, keep_columns=[(x0, w) for _, x0, w in segments])
+            for index, x0, w in segments:
+                views = [DeviceArray(out.t[x0:x0 + w]) for out in outputs]
+                context['prediction'][self.name] = views
+                selector.paragraph_id, selector.line_id = places[index]
+                selector.put(views[0] if self.delist_result else views)
+
+
 # what the modes that still raise are waiting for (the reference's component order, model.py:489-500)
 _MISSING_STAGE = {
     'TRAIN_CHAR': 'this mode is not routed through the device LineCrop stage yet: build the system [ParagraphCrop, '
@@ -474,7 +512,7 @@ def make_train_char_system(input_shape, optimizer=None, progress_tracker=None, w
 
 
 def make_predict_system(input_shape, progress_tracker=None, weights=None, find_rotation=True, rotation_search='host',
-                        line_labelling='paragraph'):
+                        line_labelling='paragraph', char_batching='line'):
     """model.py:688-717: the reference's PREDICT system without its rename and move components -- a page goes in as
     context['monochrome_X'] (1, H, W, 1), H and W multiples of 16 (make_divisible_by), and context['text'][p][l] comes
     out.  No array visits the host between the stages: only the component tables, the probe extents of the rotation
@@ -488,12 +526,16 @@ def make_predict_system(input_shape, progress_tracker=None, weights=None, find_r
       Line           one pass per paragraph through a LineSelector -> line_pred[p]
       LineCrop       finds the lines of every paragraph in line_pred and cuts them out of cropped_monochrome:
                      cropped_2_monochrome[p][l]
-      Char           one pass per line through a CharSelector -> char_pred[p][l]
+      Char           one pass per line through a CharSelector (char_batching='page': one per page) -> char_pred[p][l]
       PredToText     text[p][l] from char_pred
     The nets are built for input_shape and take every size they meet afterwards (crops are multiples of 16, lines 32
     rows high and at least 8 columns wide).  rotation_search: 'host' walks the 13 rounds of the angle search on the
     host, a readback per round; 'device' makes it one call and one readback per page (my_model/crop.py).
-    line_labelling: 'paragraph' or 'page', how LineCrop labels its masks (make_line_crop_component)."""
+    line_labelling: 'paragraph' or 'page', how LineCrop labels its masks (make_line_crop_component).
+    char_batching: 'line' runs the Char net once per line, 'page' once per page on all lines laid side by side
+    (PackedLinesComponent): the same predictions from one pass."""
+    if char_batching not in ('line', 'page'):
+        raise ValueError(f"make_predict_system: char_batching must be 'line' or 'page', got {char_batching!r}")
     models = {name: _make_net(name, shape, None, progress_tracker, weights)
               for name, shape in (('Monochrome', input_shape), ('Paragraph', input_shape), ('Line', input_shape),
                                   ('Char', (input_shape[0], CHAR_INPUT_HEIGHT, 64, 1)))}
@@ -502,6 +544,8 @@ def make_predict_system(input_shape, progress_tracker=None, weights=None, find_r
                  'Line': LineSelector('cropped_monochrome', None, 'line_pred'),
                  'Char': CharSelector('cropped_2_monochrome', None, 'char_pred')}
     net = {name: ModelComponent(name, models[name], selectors[name], delist_result=True) for name in models}
+    if char_batching == 'page':
+        net['Char'] = PackedLinesComponent('Char', models['Char'], selectors['Char'], delist_result=True)
     components = [net['Monochrome'], net['Paragraph'],
                   make_paragraph_crop_component(find_rotation, progress_tracker, ('monochrome_pred',), ('cropped_monochrome',),
                                                 rotation_search),

@@ -3,6 +3,7 @@ on one page.  Image file input stays with the caller: `pre
 `main` an .npy file.
 
     python -m univer_ocr_amd.my_model.predict page.npy [--weights model_weights.json] [--device-search] [--page-line-labels]
+        [--page-char-pass]
 """
 import json
 
@@ -12,11 +13,13 @@ from ..nn.gpu import CP
 from .model import make_divisible_by, make_predict_system
 
 
-def load_model_system(input_shape, weights_path=None, find_rotation=True, rotation_search='host', line_labelling='paragraph'):
+def load_model_system(input_shape, weights_path=None, find_rotation=True, rotation_search='host', line_labelling='paragraph',
+                      char_batching='line'):
     """predict.py:12-23: the PREDICT system with the weights of `weights_path` (a model_weights.json); a missing file,
     or none, leaves the fresh weights in place.  rotation_search: 'host' or 'device', where the angle search of the
     paragraphs walks its rounds; line_labelling: 'paragraph' or 'page', whether LineCrop labels the line masks paragraph
-    by paragraph or all in one call (make_predict_system)."""
+    by paragraph or all in one call; char_batching: 'line' or 'page', whether the Char net runs once per line or once
+    per page on all lines side by side (make_predict_system)."""
     weights = {}
     if weights_path is not None:
         try:
@@ -25,12 +28,13 @@ def load_model_system(input_shape, weights_path=None, find_rotation=True, rotati
         except OSError:
             print(f'No {weights_path} file found')
     model_system, _, _ = make_predict_system(input_shape, weights=weights, find_rotation=find_rotation,
-                                             rotation_search=rotation_search, line_labelling=line_labelling)
+                                             rotation_search=rotation_search, line_labelling=line_labelling,
+                                             char_batching=char_batching)
     return model_system
 
 
 def predict_text(image, model_system=None, weights_path=None, find_rotation=True, context=None, rotation_search='host',
-                 line_labelling='paragraph'):
+                 line_labelling='paragraph', char_batching='line'):
     """predict.py:48-59: `image` is one page, (1, H, W, 1) with values in [0, 1] as the reference's encode_X leaves
     them.  It is framed to multiples of 16 (make_divisible_by), moved to the device and run through `model_system`
     (default: load_model_system for the framed shape).  Returns context['text']: text[paragraph][line], a str each.
@@ -40,7 +44,9 @@ def predict_text(image, model_system=None, weights_path=None, find_rotation=True
         raise ValueError(f'predict_text: the page must have shape (1, H, W, 1), got {image.shape}')
     X = make_divisible_by(image, 16, 16)
     if model_system is None:
-        model_system = load_model_system(X.shape, weights_path, find_rotation, rotation_search, line_labelling)
+        # (the option travels only when it is set: whoever stands in for load_model_system keeps the arguments it knows)
+        packed = {} if char_batching == 'line' else {'char_batching': char_batching}
+        model_system = load_model_system(X.shape, weights_path, find_rotation, rotation_search, line_labelling, **packed)
     context = {} if context is None else context
     context['monochrome_X'] = CP.copy(X)
     model_system.predict(context)
@@ -57,6 +63,8 @@ def main(argv=None):
                         help='the angle search of the paragraphs in one call on the device, not round by round on the host')
     parser.add_argument('--page-line-labels', action='store_true',
                         help='the line masks of all paragraphs of the page labelled in one call, not paragraph by paragraph')
+    parser.add_argument('--page-char-pass', action='store_true',
+                        help='the Char net once per page on all lines laid side by side, not once per line')
     args = parser.parse_args(argv)
     page = np.load(args.page, allow_pickle=False)
     if page.ndim == 2:
@@ -64,7 +72,8 @@ def main(argv=None):
     CP.use_gpu()
     for paragraph in predict_text(page, weights_path=args.weights, find_rotation=not args.no_rotation,
                                   rotation_search='device' if args.device_search else 'host',
-                                  line_labelling='page' if args.page_line_labels else 'paragraph'):
+                                  line_labelling='page' if args.page_line_labels else 'paragraph',
+                                  char_batching='page' if args.page_char_pass else 'line'):
         for line in paragraph:
             print(line)
         print()

@@ -228,6 +228,14 @@ class Runtime:
         self.call('uocr_ctx_last_pred_to_text', *[C.byref(x) for x in v])
         return tuple(x.value for x in v)
 
+    def last_pack_lines(self):
+        """(elements of an entry per block at most, entries per launch, kernel launches) of the most recent uocr_pack_lines
+        or uocr_zero_gaps call on the current lane (uocr_ctx_last_pack_lines); all 0 before the first."""
+        import ctypes as C
+        v = [C.c_int() for _ in range(3)]
+        self.call('uocr_ctx_last_pack_lines', *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
     def set_loss_snapshot(self, arena):
         """From now on the fused optimizer tails launched on the CURRENT lane end by copying `arena`'s slots into the next
         row of its ring (LossArena.arm); None switches it off."""

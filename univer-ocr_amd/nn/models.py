@@ -22,7 +22,7 @@ import numpy as np
 from . import ops, plan
 from .gpu import CP, DeviceScalar
 from .help_func import make_list_if_not
-from .layers import BaseLayer, ParamPack
+from .layers import BaseLayer, LeakyRelu, ParamPack
 from .losses import SoftmaxCrossEntropy
 from .progress_tracker import track_method
 
@@ -207,12 +207,29 @@ class Model(BaseModel):
         return self._steps
 
     @track_method('forward')
-    def forward(self, inputs):
+    def forward(self, inputs, keep_columns=None):
+        """keep_columns: None, or the segments [(x0, w), ...] of a strip of lines laid side by side (ops.pack_lines), the
+        model's only input: the columns outside them are set back to zero (ops.zero_gaps) in every 4-D output that is as
+        wide as the input, so that a layer that looks sideways sees zeros there, as its own padding shows them to a line
+        passed alone.  The rows of a 2-D output that belong to those columns are unspecified."""
         inputs = [ops.as_device(x) for x in make_list_if_not(inputs)]
         if not self.is_initialized:
             self.initialize_from_X(inputs)
+        if keep_columns is not None:
+            keep_columns = [(int(x0), int(w)) for x0, w in keep_columns]
+            if len(inputs) != 1 or self.inputs_count != 1:
+                raise ValueError(f'forward: keep_columns is for a model with one input, this one has {self.inputs_count}')
+            if inputs[0].ndim != 4:
+                raise ValueError(f'forward: keep_columns is for a (B, H, W, C) input, got {inputs[0].shape}')
+            end = 0
+            for x0, w in keep_columns:
+                if w < 1 or x0 < end or x0 + w > inputs[0].shape[2]:
+                    raise ValueError(f'forward: the segments {keep_columns} are not ascending, disjoint and inside the '
+                                     f'{inputs[0].shape[2]} columns of the input')
+                end = x0 + w
         self.clear_param_grads()                      # models.py:188 (per layer there, once here)
         outputs = {}
+        zeroed = set()                                # keep_columns: the nodes whose gap columns hold zeros
         for step in self._compiled().steps:
             kind, layer = step.kind, step.layer
             args = [inputs[s] if isinstance(s, int) else outputs[s] for s in step.sources]
@@ -230,7 +247,15 @@ class Model(BaseModel):
                 out = layer.forward_windows(args[0], step.width, step.act)
             else:                                     # ABSORBED: computed inside the kernel of its consumer
                 out = None
-            outputs[step.node] = out[0] if isinstance(out, list) else out
+            outputs[step.node] = out = out[0] if isinstance(out, list) else out
+            if keep_columns is not None and out is not None and out.ndim == 4 and out.shape[0] == inputs[0].shape[0] \
+                    and out.shape[2] == inputs[0].shape[2]:   # (the windows of a strip of 8 columns are 8 wide too, but B * 8 of them)
+                # an ALIAS shares its producer's array; LeakyReLU(+0.0) = +0.0 leaves zeroed gaps as they are
+                fresh = kind != plan.ALIAS and not (kind == plan.PLAIN and isinstance(layer, LeakyRelu)
+                                                    and step.sources[0] in zeroed)
+                if fresh:
+                    ops.zero_gaps(out, keep_columns)
+                zeroed.add(step.node)
         for k in range(self.outputs_count):
             src = self.relations[k][0]
             outputs[k] = inputs[src] if isinstance(src, int) else outputs[src]

@@ -998,6 +998,77 @@ def line_crop(entries, zoomed_height=32, minimal_width=8):
     return outs
 
 
+# ---- the lines of a page in one strip (the Char net over all lines of a page in one pass) -------------------------------
+PACK_GAP = 4             # columns between neighbouring lines: the left padding of the Char net's windows of 8 columns
+
+
+def pack_layout(widths, gap=PACK_GAP, max_columns=32768):
+    """Where the lines of a page, `widths` columns wide, go when they are laid side by side: a list of strips, each
+    (segments, strip_w) with segments = [(line index, x0, w), ...], line `index` at columns [x0, x0 + w) of a strip of
+    strip_w columns, `gap` columns between neighbours and none at the outer ends.  Host only.  Lines keep their order and
+    are never split; a strip takes lines while it stays within max_columns, a line wider than that gets a strip of its
+    own.  gap >= 4: the windows of the Char net (Conv2DToBatchedFixedWidthed(8)) pad 4 zero columns on their left, so a
+    narrower gap lets a line's first windows see its neighbour -- the convs in front, 3 columns wide with padding 1, need
+    1 each."""
+    gap, max_columns = int(gap), int(max_columns)
+    if gap < PACK_GAP:
+        raise ValueError(f'pack_layout: gap {gap} is narrower than the left padding of the windows of 8 columns, {PACK_GAP}: '
+                         f'a line would see its neighbour')
+    strips = []
+    for index, w in enumerate(int(w) for w in widths):
+        if w < 1:
+            raise ValueError(f'pack_layout: line {index} has width {w}')
+        if strips and strips[-1][1] + gap + w <= max_columns:
+            segments, strip_w = strips[-1]
+            segments.append((index, strip_w + gap, w))
+            strips[-1] = (segments, strip_w + gap + w)
+        else:
+            strips.append(([(index, 0, w)], w))
+    return strips
+
+
+def _segment_arrays(segments, strip_w, who):
+    """(x0, w) of a call as C arrays, after the checks the library makes too (ascending, disjoint, inside the strip)"""
+    segments = [(int(x0), int(w)) for x0, w in segments]
+    end = 0
+    for x0, w in segments:
+        if w < 1 or x0 < end or x0 + w > strip_w:
+            raise ValueError(f'{who}: the segments {segments} are not ascending, disjoint and inside [0, {strip_w})')
+        end = x0 + w
+    return _ints([x0 for x0, _ in segments]), _ints([w for _, w in segments])
+
+
+def pack_lines(lines, strip):
+    """One strip of pack_layout -- strip = (segments, strip_w), segments = [(line index, x0, w), ...] -- filled from the
+    flat list `lines` of (1, H, W, C) DeviceArrays of one height, channel count and dtype: a new (1, H, strip_w, C)
+    DeviceArray, lines[index] at columns [x0, x0 + w), zero everywhere else.  ONE uocr_pack_lines call."""
+    segments, strip_w = strip
+    chosen = [lines[index] for index, _, _ in segments]
+    if not chosen:
+        raise ValueError('pack_lines: a strip without lines')
+    for a in chosen:
+        if not isinstance(a, DeviceArray) or a.ndim != 4 or a.shape[0] != 1:
+            raise ValueError(f'pack_lines: expected (1, H, W, C) device arrays, got {getattr(a, "shape", type(a))}')
+    code, (_, h, _, c) = _shared_code(chosen, 'pack_lines', 'a dtype'), chosen[0].shape
+    if any((a.shape[1], a.shape[3]) != (h, c) for a in chosen) or any(a.shape[2] != w for a, (_, _, w) in zip(chosen, segments)):
+        raise ValueError(f'pack_lines: the lines {[a.shape for a in chosen]} do not fit the segments {segments} of one strip')
+    x0, w = _segment_arrays([s[1:] for s in segments], int(strip_w), 'pack_lines')
+    out = CP.empty((1, h, int(strip_w), c), chosen[0].dtype)
+    _rt().call('uocr_pack_lines', code, len(chosen), _pointers(chosen), w, h, c, x0, out.ptr, int(strip_w))
+    return out
+
+
+def zero_gaps(x, segments):
+    """In place on x: (1, H, W, C): every column outside the segments [(x0, w), ...] becomes +0.0, whatever it held; the
+    segments are not touched.  ONE uocr_zero_gaps call that visits the gaps only (none for an empty list).  Returns x."""
+    if not isinstance(x, DeviceArray) or x.ndim != 4 or x.shape[0] != 1:
+        raise ValueError(f'zero_gaps: expected a (1, H, W, C) device array, got {getattr(x, "shape", type(x))}')
+    x0, w = _segment_arrays(segments, x.shape[2], 'zero_gaps')
+    if len(x0):
+        _rt().call('uocr_zero_gaps', x.code & 0xff, x.ptr, x.shape[1], x.shape[2], x.shape[3], len(x0), x0, w)
+    return x
+
+
 class _Ops:
     add = staticmethod(add)
 
