@@ -118,6 +118,16 @@ int fin_flush(uocr_ctx* ctx) {
     return UOCR_OK;
 }
 
+// true: a and b write one of their outputs (dw, db, dw2, db2) to the same place
+bool same_target(const FinishDesc& a, const FinishDesc& b) {
+    const float* pa[4] = {a.dw, a.db, a.dw2, a.db2};
+    const float* pb[4] = {b.dw, b.db, b.dw2, b.db2};
+    for (const float* x : pa)
+        for (const float* y : pb)
+            if (x && x == y) return true;
+    return false;
+}
+
 }  // namespace
 
 float* uocr_partial_buffer(uocr_ctx* ctx, size_t bytes, int* rc) {
@@ -135,7 +145,18 @@ float* uocr_partial_buffer(uocr_ctx* ctx, size_t bytes, int* rc) {
 
 bool uocr_finish_defer(uocr_ctx* ctx, const FinishDesc& d) {
     FinishDefer* f = fin_of(ctx);
-    if (!f || !f->on || !f->region || f->count >= FIN_MAX) return false;
+    if (!f || !f->on || !f->region) return false;
+    // the finishes of a group run at the same time, and fin_out's `*dst = *dst + s` is no atomic: a finish that writes
+    // where a recorded one writes (two calls accumulating into one dw) waits for those to be launched, as a GEMM of the
+    // group does (defer_record).  Its own partial is already written: the region keeps its fill
+    for (int q = 0; q < f->count; ++q)
+        if (same_target(f->args.d[q], d)) {
+            const size_t used = f->used;
+            if (fin_flush(ctx) != UOCR_OK) return false;
+            f->used = used;
+            break;
+        }
+    if (f->count >= FIN_MAX) return false;
     // only partials that live in the deferred region survive until the flush
     const char* p = (const char*)d.partial;
     if (p < (const char*)f->region || p >= (const char*)f->region + FIN_REGION_BYTES) return false;
