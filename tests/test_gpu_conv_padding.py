@@ -62,8 +62,8 @@ KID = {name: i for i, name in enumerate(KERNELS)}
 FWD, DGRAD, WGRAD = 0, 1, 2
 
 Dims = namedtuple('Dims', 'n h w cin cout kh kw sh sw ph pw oh ow')
-# UOCR_FAST_CONVS (conv_fast.hip): kernel, channels, stride | pixels per thread of conv_fwd_px, conv_dgrad_px (0 = the
-# *_fast kernel) and conv_wgrad_fast | the net's padding
+# FAST_CONVS (conv_fast.hip): kernel, channels, stride | fwd.px, dx.px, the pixels per thread of conv_fwd_px and
+# conv_dgrad_px (0 = the row names the *_fast kernel instead), and dw.px of conv_wgrad_fast | the net's padding
 Cfg = namedtuple('Cfg', 'kh kw cin cout sh sw fpx dpx wpx net_pad')
 TABLE = (
     Cfg(3, 3, 1, 16, 1, 1, 0, 4, 1, (1, 1)),    # Monochrome conv_1

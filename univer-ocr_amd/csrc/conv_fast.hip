@@ -1,4 +1,5 @@
-// Shape-specialised direct convolution kernels (float32) for the skinny convs of my_model
+// Shape-specialised direct convolution kernels for the skinny convs of my_model, float32 or binary16 activations (every
+// table kernel is templated on the activation type TA; weights, accumulators and gradients of weights are float32)
 // (reference shapes: my_model/model.py:108-304; semantics: nn/layers/convolutional.py:62-145).
 //
 // Arithmetic intensity of these layers is 2.6-25 flop/byte: they are HBM-bound, so
@@ -54,6 +55,19 @@ __device__ __forceinline__ void store_vec(TA* __restrict__ p, const float (&v)[C
 struct FastDims {
     int n, h, w, oh, ow, ph, pw;
 };
+
+// the shapes that the kernels in front of the table (uocr_conv_*_fast) ask for; the two 5x5 ones take any output size
+// (conv_is5x5_pad2 of conv_dims.h also wants the full one)
+inline bool is_c16_same(const ConvDims& d, int cin, int cout) {          // 3x3, stride 1, output the size of the input
+    return d.kh == 3 && d.kw == 3 && d.cin == cin && d.cout == cout && d.sh == 1 && d.sw == 1 && d.oh == d.h &&
+           d.ow == d.w;
+}
+inline bool is_5x5_s2_pad2(const ConvDims& d) {
+    return d.kh == 5 && d.kw == 5 && d.sh == 2 && d.sw == 2 && d.ph == 2 && d.pw == 2;
+}
+inline bool is_5x5_s1_pad2(const ConvDims& d) {
+    return d.kh == 5 && d.kw == 5 && d.sh == 1 && d.sw == 1 && d.ph == 2 && d.pw == 2;
+}
 
 // dx epilogue: v[c] *= act'(y[off + c]) from the activation output y (ActMask, conv_dims.h)
 template <int C, typename TA>
@@ -947,8 +961,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_fast_finish(const float* __res
 // so that the 16 lanes of a row, which read columns 4 apart, touch consecutive 16-byte LDS words.
 // ---------------------------------------------------------------------------------------------
 namespace t542 {
-constexpr int TH = 16, TW = 64, WH = TH + 4, WW = TW + 4, NACC = 42, NP = 64;   // 40 dw of a tap row + db
+constexpr int TH = 16, TW = 64, WH = TH + 4, WW = TW + 4, NW = 40, NB = 2, NACC = NW + NB, NP = 64;   // a tap row of dw + db
 __device__ __forceinline__ int swz(int row, int c) { return row * WW + (c & 3) * (WW / 4) + (c >> 2); }
+struct Taprows {                                           // (for launch_wgrad_taprows: a wave stores its NACC sums packed)
+    static constexpr int TH = t542::TH, TW = t542::TW, NW = t542::NW, NB = t542::NB, ROW = NACC;
+};
 }  // namespace t542
 
 template <typename TA>
@@ -1027,24 +1044,6 @@ __global__ __launch_bounds__(320) void conv_wgrad_t542(const TA* __restrict__ x,
     if (lane < NACC) partial[(blk * 5 + ky) * NACC + lane] = acc[0];
 }
 
-// block a < 200: dw[a] (= tap row a / 40, accumulator a % 40); a = 200, 201: db (from tap row 0's waves)
-__global__ __launch_bounds__(256) void conv_wgrad_t542_finish(const float* __restrict__ partial, float* __restrict__ dw,
-                                                              float* __restrict__ db, int nblocks, int use_bias,
-                                                              int accumulate, float unscale) {
-    using namespace t542;
-    __shared__ double smem[16];
-    const int a = blockIdx.x;
-    const int ky = a < 200 ? a / 40 : 0, idx = a < 200 ? a % 40 : 40 + (a - 200);
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nblocks; i += blockDim.x) s += (double)partial[((size_t)i * 5 + ky) * NACC + idx];
-    s = block_reduce_sum(s, smem);
-    if (threadIdx.x != 0) return;
-    float* dst = a < 200 ? dw + a : db + (a - 200);
-    if (a >= 200 && !use_bias) s = 0.0;
-    s *= (double)unscale;                                  // UOCR_F16_SCALED(k): 2^-k, else 1
-    *dst = accumulate ? (float)((double)*dst + s) : (float)s;
-}
-
 // ---------------------------------------------------------------------------------------------
 // dw / db of the 5x5 / stride 2 / pad 2 encoder convs (Paragraph down_1/2: 1 -> 1, Line down_1: 1 -> 4,
 // down_2: 4 -> 4) with the structure of conv_wgrad_t542: a block of five waves stages an 8 x 32 tile of dy
@@ -1057,6 +1056,7 @@ struct S2Cfg {
     static constexpr int TH = 8, TW = 32, WH = 2 * TH + 3, WW = 2 * TW + 3;
     static constexpr int NW = 5 * CIN * COUT, NACC = NW + COUT;      // one tap row of dw + db
     static constexpr int NP = ((NACC + 63) / 64) * 64;
+    static constexpr int NB = COUT, ROW = NP;                        // (for launch_wgrad_taprows)
 };
 
 template <int CIN, int COUT, typename TA>
@@ -1145,17 +1145,18 @@ __global__ __launch_bounds__(320) void conv_wgrad_s2_tiled(const TA* __restrict_
     for (int q = 0; q < C::NP / 64; ++q) out[base + q] = acc[q];
 }
 
-// block a < 25 * CIN * COUT: dw[a] (tap row a / NW, accumulator a % NW); then COUT blocks for db
-template <int CIN, int COUT>
-__global__ __launch_bounds__(256) void conv_wgrad_s2_finish(const float* __restrict__ partial, float* __restrict__ dw,
-                                                            float* __restrict__ db, int nblocks, int use_bias,
-                                                            int accumulate, float unscale) {
-    using C = S2Cfg<CIN, COUT>;
+// The finish of both tiled producers (conv_wgrad_t542, conv_wgrad_s2_tiled): a block's partials are five tap rows of ROW
+// floats, NW of dw and then the db sums.  Block a < 5 * NW: dw[a] (tap row a / NW, accumulator a % NW); the blocks after
+// them: db (from tap row 0's waves).
+template <int ROW, int NW>
+__global__ __launch_bounds__(256) void conv_wgrad_taprows_finish(const float* __restrict__ partial, float* __restrict__ dw,
+                                                                 float* __restrict__ db, int nblocks, int use_bias,
+                                                                 int accumulate, float unscale) {
     __shared__ double smem[16];
-    const int a = blockIdx.x, ndw = 5 * C::NW;
-    const int ky = a < ndw ? a / C::NW : 0, idx = a < ndw ? a % C::NW : C::NW + (a - ndw);
+    const int a = blockIdx.x, ndw = 5 * NW;
+    const int ky = a < ndw ? a / NW : 0, idx = a < ndw ? a % NW : NW + (a - ndw);
     double s = 0.0;
-    for (int i = threadIdx.x; i < nblocks; i += blockDim.x) s += (double)partial[((size_t)i * 5 + ky) * C::NP + idx];
+    for (int i = threadIdx.x; i < nblocks; i += blockDim.x) s += (double)partial[((size_t)i * 5 + ky) * ROW + idx];
     s = block_reduce_sum(s, smem);
     if (threadIdx.x != 0) return;
     float* dst = a < ndw ? dw + a : db + (a - ndw);
@@ -1164,36 +1165,82 @@ __global__ __launch_bounds__(256) void conv_wgrad_s2_finish(const float* __restr
     *dst = accumulate ? (float)((double)*dst + s) : (float)s;
 }
 
-template <int CIN, int COUT>
-int launch_wgrad_s2(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw, void* db, const ConvDims& d,
-                    double pad_value, int use_bias, int accumulate) {
-    using C = S2Cfg<CIN, COUT>;
-    const int tiles_x = (d.ow + C::TW - 1) / C::TW, tiles_y = (d.oh + C::TH - 1) / C::TH;
-    // ~1024 blocks: a few tiles of one column strip each
-    const int per_block = uocr_tiles_per_block(tiles_x, tiles_y, d.n, uocr_budget(ctx, 1024));
-    const dim3 grid(tiles_x, (tiles_y + per_block - 1) / per_block, d.n);
+// Launches a tiled producer and its finish, and notes kernel_id.  C (t542::Taprows, S2Cfg): the TH x TW tile, the NW + NB
+// accumulators of a tap row and ROW, the floats from one tap row of a block's partials to the next; rows x cols: the
+// extent that the tiles cover; producer(TA{}, grid, partial, tiles_per_block) launches the kernel for activations of type TA.
+template <class C, class Producer>
+int launch_wgrad_taprows(uocr_ctx* ctx, int dtype, int kernel_id, int n, int rows, int cols, void* dw, void* db, int use_bias,
+                         int accumulate, Producer&& producer) {
+    const int tiles_x = (cols + C::TW - 1) / C::TW, tiles_y = (rows + C::TH - 1) / C::TH;
+    // ~1024 blocks: a few tiles of one column strip each (conv_wgrad_t542 measured at 32 x 256 x 512: 512 blocks 58 us,
+    // 1024 57, 2048 65, 4096 74)
+    const int per_block = uocr_tiles_per_block(tiles_x, tiles_y, n, uocr_budget(ctx, 1024));
+    const dim3 grid(tiles_x, (tiles_y + per_block - 1) / per_block, n);
     const int nblocks = (int)(grid.x * grid.y * grid.z);
-    uocr_note_split(ctx, nblocks, (long long)tiles_x * tiles_y * d.n);
+    uocr_note_split(ctx, nblocks, (long long)tiles_x * tiles_y * n);
     int rc = UOCR_OK;
-    float* partial = uocr_partial_buffer(ctx, (size_t)nblocks * 5 * C::NP * sizeof(float), &rc);
+    float* partial = uocr_partial_buffer(ctx, (size_t)nblocks * 5 * C::ROW * sizeof(float), &rc);
     if (rc) return rc;
-    UOCR_DISPATCH_TA(ctx, dtype, {
-        hipLaunchKernelGGL((conv_wgrad_s2_tiled<CIN, COUT, TA>), grid, dim3(320), 0, ctx->stream, (const TA*)x,
-                           (const TA*)dy, partial, d.h, d.w, d.oh, d.ow, (float)pad_value, per_block);
-    });
+    UOCR_DISPATCH_TA(ctx, dtype, { producer(TA{}, grid, partial, per_block); });
     UOCR_LAUNCH_CHECK(ctx);
     const float unscale = (float)uocr_grad_unscale(dtype);
-    const FinishDesc fd = finish_taprows(partial, nblocks, C::NP, C::NW, COUT, (float*)dw, (float*)db, use_bias, accumulate,
-                                         unscale);
-    return uocr_finish(ctx, fd, [&] {
-        hipLaunchKernelGGL((conv_wgrad_s2_finish<CIN, COUT>), dim3(5 * C::NW + COUT), dim3(256), 0, ctx->stream,
+    const FinishDesc fd = finish_taprows(partial, nblocks, C::ROW, C::NW, C::NB, (float*)dw, (float*)db, use_bias,
+                                         accumulate, unscale);
+    return uocr_noted_conv(ctx, 2, kernel_id, uocr_finish(ctx, fd, [&] {
+        hipLaunchKernelGGL((conv_wgrad_taprows_finish<C::ROW, C::NW>), dim3(5 * C::NW + C::NB), dim3(256), 0, ctx->stream,
                            (const float*)partial, (float*)dw, (float*)db, nblocks, use_bias, accumulate, unscale);
-    });
+    }));
 }
 
-template <int KH, int KW, int CIN, int COUT, int SH, int SW, int COB, int PY, int DPY, int KYR, int WCOB, int WPY, int FPX,
-          int DPX>
+// ---------------------------------------------------------------------------------------------
+// The table: one row per conv shape of my_model.  A row names, for each entry point, the kernel it runs and that
+// kernel's tuning numbers only; whatever the row never instantiates stays 0 and does not appear.
+//   forward  px:      conv_fwd_px, px pixels per thread           | cob, py: conv_fwd_fast, cob channels x py rows per thread
+//   dx       px:      conv_dgrad_px (stride 1), px pixels         | py:      conv_dgrad_fast, py rows per thread
+//   dw       kyr, cob, px: conv_wgrad_fast, kyr tap rows x cob channels per block, px pixels per thread
+// The per-pixel kernels still run Char conv_1 (forward in both dtypes, dx in binary16), Monochrome conv_1 forward in
+// binary16 or off the "same" padding, and the dx of every stride-2 row off the net's padding; everything else in the
+// table is a row-loop kernel.
+// ---------------------------------------------------------------------------------------------
+struct FastRow {
+    int kh, kw, cin, cout, sh, sw;
+    struct Fwd { int px = 0, cob = 0, py = 0; } fwd;
+    struct Dx { int px = 0, py = 0; } dx;
+    struct Dw { int kyr = 0, cob = 0, px = 0; } dw;
+};
+
+constexpr FastRow FAST_CONVS[] = {
+    {.kh = 3, .kw = 3, .cin = 1, .cout = 16, .sh = 1, .sw = 1,       // Monochrome conv_1: dgrad re-reads 16-ch dy
+     .fwd = {.cob = 4, .py = 2}, .dx = {.px = 4}, .dw = {.kyr = 3, .cob = 16, .px = 1}},
+    {.kh = 3, .kw = 3, .cin = 16, .cout = 1, .sh = 1, .sw = 1,       // Monochrome conv_2: fwd/wgrad re-read 16-ch x
+     .fwd = {.px = 4}, .dx = {.px = 2}, .dw = {.kyr = 1, .cob = 1, .px = 1}},
+    {.kh = 5, .kw = 5, .cin = 1, .cout = 1, .sh = 2, .sw = 2,        // Paragraph down_1/2
+     .fwd = {.px = 4}, .dx = {.py = 1}, .dw = {.kyr = 5, .cob = 1, .px = 4}},
+    {.kh = 5, .kw = 5, .cin = 1, .cout = 1, .sh = 1, .sw = 1,        // Paragraph up_2, up_1, end (px 8: fwd 22 -> 24,
+     .fwd = {.px = 4}, .dx = {.px = 8}, .dw = {.kyr = 5, .cob = 1, .px = 8}},   // dx 22 -> 17, dw 35 -> 28 us)
+    {.kh = 5, .kw = 5, .cin = 1, .cout = 4, .sh = 2, .sw = 2,        // Line down_1
+     .fwd = {.px = 4}, .dx = {.py = 1}, .dw = {.kyr = 5, .cob = 4, .px = 1}},
+    {.kh = 5, .kw = 5, .cin = 4, .cout = 4, .sh = 2, .sw = 2,        // Line down_2
+     .fwd = {.px = 4}, .dx = {.py = 1}, .dw = {.kyr = 1, .cob = 4, .px = 2}},
+    {.kh = 5, .kw = 5, .cin = 4, .cout = 4, .sh = 1, .sw = 1,        // Line up_2, up_1
+     .fwd = {.px = 4}, .dx = {.px = 4}, .dw = {.kyr = 1, .cob = 4, .px = 4}},
+    {.kh = 5, .kw = 5, .cin = 4, .cout = 2, .sh = 1, .sw = 1,        // Line end
+     .fwd = {.px = 4}, .dx = {.px = 4}, .dw = {.kyr = 1, .cob = 2, .px = 4}},
+    {.kh = 5, .kw = 3, .cin = 1, .cout = 64, .sh = 2, .sw = 1,       // Char conv_1
+     .fwd = {.cob = 4, .py = 1}, .dx = {.py = 1}, .dw = {.kyr = 5, .cob = 8, .px = 1}},
+};
+
+template <int I>
 struct FastConv {
+    static constexpr FastRow R = FAST_CONVS[I];
+    static constexpr int KH = R.kh, KW = R.kw, CIN = R.cin, COUT = R.cout, SH = R.sh, SW = R.sw;
+    // a row gives every number of the one forward and the one dx kernel it uses, no others, and all of conv_wgrad_fast's
+    static_assert(R.fwd.px > 0 ? !R.fwd.cob && !R.fwd.py : R.fwd.cob > 0 && R.fwd.py > 0, "forward: px, or cob and py");
+    static_assert(R.dx.px > 0 ? !R.dx.py && SH == 1 && SW == 1 : R.dx.py > 0, "dx: px (stride 1 only), or py");
+    static_assert(R.dw.kyr > 0 && R.dw.cob > 0 && R.dw.px > 0, "dw: kyr, cob and px");
+    static constexpr int FWD_KERNEL = R.fwd.px > 0 ? UOCR_CONV_TABLE_PX : UOCR_CONV_TABLE_FAST;   // (for uocr_noted_conv)
+    static constexpr int DX_KERNEL = R.dx.px > 0 ? UOCR_CONV_TABLE_PX : UOCR_CONV_TABLE_FAST;
+
     static bool match(const ConvDims& d) {
         return d.kh == KH && d.kw == KW && d.cin == CIN && d.cout == COUT && d.sh == SH && d.sw == SW;
     }
@@ -1205,16 +1252,16 @@ struct FastConv {
         return uocr_act_tags<0>(ctx, act, UOCR_ACT_NONE, [&](auto kinds) -> int {
         using K = ActKindsIf<COUT == 4, decltype(kinds)>;
         UOCR_DISPATCH_TA(ctx, dtype, {
-            if constexpr (FPX > 0) {
-                const int groups = (d.ow + FPX - 1) / FPX;
+            if constexpr (R.fwd.px > 0) {
+                const int groups = (d.ow + R.fwd.px - 1) / R.fwd.px;
                 const dim3 grid((groups + 63) / 64, (d.oh + 3) / 4, d.n), block(64, 4);
-                hipLaunchKernelGGL((conv_fwd_px<KH, KW, CIN, COUT, SH, SW, FPX, TA, K>), grid, block, 0, ctx->stream,
+                hipLaunchKernelGGL((conv_fwd_px<KH, KW, CIN, COUT, SH, SW, R.fwd.px, TA, K>), grid, block, 0, ctx->stream,
                                    (const TA*)x, (const float*)w, (const float*)b, (TA*)y, dims(d), (float)pad,
                                    use_bias, act, (float)alpha);
             } else {
-                constexpr int PXW = 64 / (COUT / COB);
-                const dim3 grid((d.ow + PXW - 1) / PXW, (d.oh + 4 * PY - 1) / (4 * PY), d.n), block(64, 4);
-                hipLaunchKernelGGL((conv_fwd_fast<KH, KW, CIN, COUT, SH, SW, COB, PY, TA>), grid, block, 0, ctx->stream,
+                constexpr int PXW = 64 / (COUT / R.fwd.cob);
+                const dim3 grid((d.ow + PXW - 1) / PXW, (d.oh + 4 * R.fwd.py - 1) / (4 * R.fwd.py), d.n), block(64, 4);
+                hipLaunchKernelGGL((conv_fwd_fast<KH, KW, CIN, COUT, SH, SW, R.fwd.cob, R.fwd.py, TA>), grid, block, 0, ctx->stream,
                                    (const TA*)x, (const float*)w, (const float*)b, (TA*)y, dims(d), (float)pad,
                                    use_bias, act, (float)alpha);
             }
@@ -1227,16 +1274,15 @@ struct FastConv {
     static int dgrad(uocr_ctx* ctx, int dtype, const void* dy, const void* w, void* dx, const ConvDims& d,
                      const ActMask& mask) {
         UOCR_DISPATCH_TA(ctx, dtype, {
-            if constexpr (DPX > 0) {
-                static_assert(DPX == 0 || (SH == 1 && SW == 1), "conv_dgrad_px is stride 1 only");
-                const int groups = (d.w + DPX - 1) / DPX;
+            if constexpr (R.dx.px > 0) {
+                const int groups = (d.w + R.dx.px - 1) / R.dx.px;
                 const dim3 grid((groups + 63) / 64, (d.h + 3) / 4, d.n), block(64, 4);
-                hipLaunchKernelGGL((conv_dgrad_px<KH, KW, CIN, COUT, DPX, TA>), grid, block, 0, ctx->stream,
+                hipLaunchKernelGGL((conv_dgrad_px<KH, KW, CIN, COUT, R.dx.px, TA>), grid, block, 0, ctx->stream,
                                    (const TA*)dy, (const float*)w, (TA*)dx, dims(d), (const TA*)mask.y, mask.act,
                                    (float)mask.alpha);
             } else {
-                const dim3 grid((d.w + 63) / 64, (d.h + 4 * DPY - 1) / (4 * DPY), d.n), block(64, 4);
-                hipLaunchKernelGGL((conv_dgrad_fast<KH, KW, CIN, COUT, SH, SW, DPY, TA>), grid, block, 0, ctx->stream,
+                const dim3 grid((d.w + 63) / 64, (d.h + 4 * R.dx.py - 1) / (4 * R.dx.py), d.n), block(64, 4);
+                hipLaunchKernelGGL((conv_dgrad_fast<KH, KW, CIN, COUT, SH, SW, R.dx.py, TA>), grid, block, 0, ctx->stream,
                                    (const TA*)dy, (const float*)w, (TA*)dx, dims(d), (const TA*)mask.y, mask.act,
                                    (float)mask.alpha);
             }
@@ -1247,7 +1293,7 @@ struct FastConv {
 
     static int wgrad(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw, void* db, const ConvDims& d,
                      double pad, int use_bias, int accumulate) {
-        using C = WgradCfg<KH, KW, CIN, COUT, SH, SW, KYR, WCOB>;
+        using C = WgradCfg<KH, KW, CIN, COUT, SH, SW, R.dw.kyr, R.dw.cob>;
         // bands of output rows: ~512 (or 64) blocks per (tap group, channel group), at least 4 rows each
         constexpr int RQ = 4;             // rows consumed per block iteration (one per wave)
         // (a wave ends in a reduce-scatter of its NP accumulators over the 64 lanes, ~3 instructions per accumulator: with 128
@@ -1265,34 +1311,43 @@ struct FastConv {
         float* partial = uocr_partial_buffer(ctx, bytes, &rc);
         if (rc) return rc;
         UOCR_DISPATCH_TA(ctx, dtype, {
-            hipLaunchKernelGGL((conv_wgrad_fast<KH, KW, CIN, COUT, SH, SW, KYR, WCOB, WPY, (CIN >= 4), TA>),
+            hipLaunchKernelGGL((conv_wgrad_fast<KH, KW, CIN, COUT, SH, SW, R.dw.kyr, R.dw.cob, R.dw.px, (CIN >= 4), TA>),
                                dim3(nblocks, ngroups), dim3(64, 4), 0, ctx->stream, (const TA*)x, (const TA*)dy,
                                partial, dims(d), (float)pad, rows, nbands);
         });
         UOCR_LAUNCH_CHECK(ctx);
         const float unscale = (float)uocr_grad_unscale(dtype);
-        const FinishDesc fd = finish_fast(partial, nblocks, ngroups, {C::NP, C::NW, KW, CIN, COUT, KYR, WCOB}, (float*)dw,
+        const FinishDesc fd = finish_fast(partial, nblocks, ngroups, {C::NP, C::NW, KW, CIN, COUT, R.dw.kyr, R.dw.cob}, (float*)dw,
                                           (float*)db, use_bias, accumulate, unscale);
         return uocr_finish(ctx, fd, [&] {
-            hipLaunchKernelGGL((conv_wgrad_fast_finish<KH, KW, CIN, COUT, KYR, WCOB, C::NW, C::NP>),
+            hipLaunchKernelGGL((conv_wgrad_fast_finish<KH, KW, CIN, COUT, R.dw.kyr, R.dw.cob, C::NW, C::NP>),
                                dim3(C::NACC, ngroups), dim3(256), 0, ctx->stream, (const float*)partial, (float*)dw,
                                (float*)db, nblocks, use_bias, accumulate, unscale);
         });
     }
 };
 
-// the my_model shapes:  KH KW CIN COUT SH SW | legacy fwd: COB PY | legacy dgrad: PY | wgrad: KYR COB PX |
-//                        row-loop kernels: fwd PX, dgrad PX (0 = use the legacy kernel)
-#define UOCR_FAST_CONVS(X)                                                                         \
-    X(3, 3, 1, 16, 1, 1, 4, 2, 4, 3, 16, 1, 0, 4) /* Monochrome conv_1: dgrad re-reads 16-ch dy */ \
-    X(3, 3, 16, 1, 1, 1, 1, 4, 1, 1, 1, 1, 4, 2)  /* Monochrome conv_2: fwd/wgrad re-read 16-ch x */ \
-    X(5, 5, 1, 1, 2, 2, 1, 1, 1, 5, 1, 4, 4, 0)   /* Paragraph down_1/2 */                         \
-    X(5, 5, 1, 1, 1, 1, 1, 4, 4, 5, 1, 8, 4, 8)   /* Paragraph up_2, up_1, end (PX 8: fwd 22 -> 24, dx 22 -> 17, dw 35 -> 28 us) */                \
-    X(5, 5, 1, 4, 2, 2, 4, 1, 1, 5, 4, 1, 4, 0)   /* Line down_1 */                                \
-    X(5, 5, 4, 4, 2, 2, 4, 2, 1, 1, 4, 2, 4, 0)   /* Line down_2 */                                \
-    X(5, 5, 4, 4, 1, 1, 4, 4, 4, 1, 4, 4, 4, 4)   /* Line up_2, up_1 */                            \
-    X(5, 5, 4, 2, 1, 1, 2, 4, 4, 1, 2, 4, 4, 4)   /* Line end */                                   \
-    X(5, 3, 1, 64, 2, 1, 4, 1, 1, 5, 8, 1, 0, 0)  /* Char conv_1 */
+// f(FastConv<I>{}) for the first row of the table whose shape is d's; false: no row matches, f was not called
+template <class F>
+bool with_fast_conv(const ConvDims& d, F&& f) {
+    return [&]<size_t... I>(std::index_sequence<I...>) {
+        return ((FastConv<I>::match(d) && (f(FastConv<I>{}), true)) || ...);
+    }(std::make_index_sequence<std::size(FAST_CONVS)>{});
+}
+
+// The launch of a conv_c16_expand / conv_c16_reduce kernel: forward (bias, activation, padding value; no mask) or dx
+// (mask; no bias, no activation, zero padding)
+struct C16Args { const void *src, *w, *bias; void* dst; float pad; int use_bias, act; float alpha; ActMask mask; };
+template <class Kernel>
+int launch_c16(uocr_ctx* ctx, Kernel kernel, int py, const C16Args& a, const ConvDims& d, int entry, int kernel_id) {
+    const dim3 grid((d.w + 15) / 16, (d.h + 4 * py - 1) / (4 * py), d.n), block(64, 4);
+    hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, (const float*)a.src, (const float*)a.w, (const float*)a.bias,
+                       (float*)a.dst, d.n, d.h, d.w, d.ph, d.pw, a.pad, a.use_bias, a.act, a.alpha,
+                       (const float*)a.mask.y, a.mask.act, (float)a.mask.alpha);
+    UOCR_LAUNCH_CHECK(ctx);
+    uocr_note_conv(ctx, entry, kernel_id);
+    return UOCR_OK;
+}
 
 }  // namespace
 
@@ -1302,78 +1357,35 @@ bool uocr_conv_fast_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d, const 
     if ((base != UOCR_F32 && base != UOCR_F16) || !ctx->opt_fast) return false;
     // p0, p1: the two activation tensors of the call (4-element accesses); p2: a float32 parameter tensor
     if (!uocr_aligned_act(p0, dtype) || !uocr_aligned_act(p1, dtype) || !uocr_aligned_act(p2, UOCR_F32)) return false;
-#define X(KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX) \
-    if (FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::match(d)) return true;
-    UOCR_FAST_CONVS(X)
-#undef X
-    return false;
+    return with_fast_conv(d, [](auto) {});
 }
-
-namespace {
-inline bool is_c16_same(const ConvDims& d, int cin, int cout) {
-    return d.kh == 3 && d.kw == 3 && d.cin == cin && d.cout == cout && d.sh == 1 && d.sw == 1 && d.oh == d.h &&
-           d.ow == d.w;
-}
-}  // namespace
 
 // (the 16-channel quad-lane kernels and the Char conv_1 dx kernel exist in float32 only: binary16 runs those
 // shapes -- none of them is on the page nets' fused path -- through the FastConv kernels of the table)
 int uocr_conv_fwd_fast(uocr_ctx* ctx, int dtype, const void* x, const void* w, const void* b, void* y,
                        const ConvDims& d, double pad_value, int use_bias, int act, double act_alpha) {
     const bool f32 = UOCR_DTYPE_BASE(dtype) == UOCR_F32;
-    if (f32 && is_c16_same(d, 1, 16)) {
-        constexpr int PY = 2;
-        const dim3 grid((d.w + 15) / 16, (d.h + 4 * PY - 1) / (4 * PY), d.n), block(64, 4);
-        hipLaunchKernelGGL((conv_c16_expand<3, 3, PY, false>), grid, block, 0, ctx->stream, (const float*)x,
-                           (const float*)w, (const float*)b, (float*)y, d.n, d.h, d.w, d.ph, d.pw, (float)pad_value,
-                           use_bias, act, (float)act_alpha, (const float*)nullptr, (int)UOCR_ACT_NONE, 0.f);
-        UOCR_LAUNCH_CHECK(ctx);
-        uocr_note_conv(ctx, 0, UOCR_CONV_C16_EXPAND);
-        return UOCR_OK;
-    }
-    if (f32 && is_c16_same(d, 16, 1)) {
-        constexpr int PY = 4;
-        const dim3 grid((d.w + 15) / 16, (d.h + 4 * PY - 1) / (4 * PY), d.n), block(64, 4);
-        hipLaunchKernelGGL((conv_c16_reduce<3, 3, PY, false>), grid, block, 0, ctx->stream, (const float*)x,
-                           (const float*)w, (const float*)b, (float*)y, d.n, d.h, d.w, d.ph, d.pw, (float)pad_value,
-                           use_bias, act, (float)act_alpha, (const float*)nullptr, (int)UOCR_ACT_NONE, 0.f);
-        UOCR_LAUNCH_CHECK(ctx);
-        uocr_note_conv(ctx, 0, UOCR_CONV_C16_REDUCE);
-        return UOCR_OK;
-    }
-#define X(KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX)                        \
-    if (FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::match(d))      \
-        return uocr_noted_conv(ctx, 0, FPX > 0 ? UOCR_CONV_TABLE_PX : UOCR_CONV_TABLE_FAST,                                       \
-                               FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::fwd(                  \
-                                   ctx, dtype, x, w, b, y, d, pad_value, use_bias, act, act_alpha));
-    UOCR_FAST_CONVS(X)
-#undef X
+    const C16Args c16{x, w, b, y, (float)pad_value, use_bias, act, (float)act_alpha, ActMask{nullptr, UOCR_ACT_NONE, 0.0}};
+    if (f32 && is_c16_same(d, 1, 16))
+        return launch_c16(ctx, conv_c16_expand<3, 3, 2, false>, 2, c16, d, 0, UOCR_CONV_C16_EXPAND);
+    if (f32 && is_c16_same(d, 16, 1))
+        return launch_c16(ctx, conv_c16_reduce<3, 3, 4, false>, 4, c16, d, 0, UOCR_CONV_C16_REDUCE);
+    int rc = UOCR_OK;
+    if (with_fast_conv(d, [&](auto fc) {
+            rc = uocr_noted_conv(ctx, 0, fc.FWD_KERNEL, fc.fwd(ctx, dtype, x, w, b, y, d, pad_value, use_bias, act, act_alpha));
+        }))
+        return rc;
     UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "no fast conv kernel for this shape");
 }
 
 int uocr_conv_dgrad_fast(uocr_ctx* ctx, int dtype, const void* dy, const void* w, void* dx, const ConvDims& d,
                          const ActMask& mask) {
     const bool f32 = UOCR_DTYPE_BASE(dtype) == UOCR_F32;
-    if (f32 && is_c16_same(d, 16, 1)) {
-        constexpr int PY = 2;
-        const dim3 grid((d.w + 15) / 16, (d.h + 4 * PY - 1) / (4 * PY), d.n), block(64, 4);
-        hipLaunchKernelGGL((conv_c16_expand<3, 3, PY, true>), grid, block, 0, ctx->stream, (const float*)dy,
-                           (const float*)w, (const float*)nullptr, (float*)dx, d.n, d.h, d.w, d.ph, d.pw, 0.f, 0,
-                           (int)UOCR_ACT_NONE, 0.f, (const float*)mask.y, mask.act, (float)mask.alpha);
-        UOCR_LAUNCH_CHECK(ctx);
-        uocr_note_conv(ctx, 1, UOCR_CONV_C16_EXPAND);
-        return UOCR_OK;
-    }
-    if (f32 && is_c16_same(d, 1, 16)) {
-        constexpr int PY = 4;
-        const dim3 grid((d.w + 15) / 16, (d.h + 4 * PY - 1) / (4 * PY), d.n), block(64, 4);
-        hipLaunchKernelGGL((conv_c16_reduce<3, 3, PY, true>), grid, block, 0, ctx->stream, (const float*)dy,
-                           (const float*)w, (const float*)nullptr, (float*)dx, d.n, d.h, d.w, d.ph, d.pw, 0.f, 0,
-                           (int)UOCR_ACT_NONE, 0.f, (const float*)mask.y, mask.act, (float)mask.alpha);
-        UOCR_LAUNCH_CHECK(ctx);
-        uocr_note_conv(ctx, 1, UOCR_CONV_C16_REDUCE);
-        return UOCR_OK;
-    }
+    const C16Args c16{dy, w, nullptr, dx, 0.f, 0, UOCR_ACT_NONE, 0.f, mask};
+    if (f32 && is_c16_same(d, 16, 1))
+        return launch_c16(ctx, conv_c16_expand<3, 3, 2, true>, 2, c16, d, 1, UOCR_CONV_C16_EXPAND);
+    if (f32 && is_c16_same(d, 1, 16))
+        return launch_c16(ctx, conv_c16_reduce<3, 3, 4, true>, 4, c16, d, 1, UOCR_CONV_C16_REDUCE);
     if (f32 && d.kh == 5 && d.kw == 3 && d.sh == 2 && d.sw == 1 && d.ph == 0 && d.pw == 1 && d.cin == 1 && d.cout == 64 &&
         d.h <= 65535 && d.n <= 65535) {                   // (rows and images are grid dimensions y and z)
         hipLaunchKernelGGL(conv_dgrad_c64s2, dim3((unsigned)((d.w + 15) / 16), d.h, d.n), dim3(256), 0, ctx->stream,
@@ -1383,8 +1395,7 @@ int uocr_conv_dgrad_fast(uocr_ctx* ctx, int dtype, const void* dy, const void* w
         uocr_note_conv(ctx, 1, UOCR_CONV_DGRAD_C64S2);
         return UOCR_OK;
     }
-    if (d.kh == 5 && d.kw == 5 && d.sh == 2 && d.sw == 2 && d.ph == 2 && d.pw == 2 &&
-        ((d.cin == 1 && (d.cout == 1 || d.cout == 4)) || (d.cin == 4 && d.cout == 4))) {
+    if (is_5x5_s2_pad2(d) && ((d.cin == 1 && (d.cout == 1 || d.cout == 4)) || (d.cin == 4 && d.cout == 4))) {
         const dim3 grid(((d.w + 1) / 2 + 63) / 64, ((d.h + 1) / 2 + 3) / 4, d.n), block(64, 4);
         const FastDims fd{d.n, d.h, d.w, d.oh, d.ow, d.ph, d.pw};
         const int rc = uocr_act_tags<1>(ctx, UOCR_ACT_NONE, mask.act, [&](auto kinds) -> int {
@@ -1406,39 +1417,10 @@ int uocr_conv_dgrad_fast(uocr_ctx* ctx, int dtype, const void* dy, const void* w
         uocr_note_conv(ctx, 1, UOCR_CONV_DGRAD_S2);
         return UOCR_OK;
     }
-#define X(KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX)                   \
-    if (FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::match(d)) \
-        return uocr_noted_conv(ctx, 1, DPX > 0 ? UOCR_CONV_TABLE_PX : UOCR_CONV_TABLE_FAST,     \
-                               FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::dgrad( \
-                                   ctx, dtype, dy, w, dx, d, mask));
-    UOCR_FAST_CONVS(X)
-#undef X
-    UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "no fast conv kernel for this shape");
-}
-
-static int launch_wgrad_t542(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw, void* db, const ConvDims& d,
-                             double pad_value, int use_bias, int accumulate) {
-    const int tiles_x = (d.w + t542::TW - 1) / t542::TW, tiles_y = (d.h + t542::TH - 1) / t542::TH;
-    // ~1024 blocks: a few tiles of one column strip each (measured at 32 x 256 x 512: 512 blocks 58 us, 1024 57, 2048 65, 4096 74)
-    const int per_block = uocr_tiles_per_block(tiles_x, tiles_y, d.n, uocr_budget(ctx, 1024));
-    const dim3 grid(tiles_x, (tiles_y + per_block - 1) / per_block, d.n);
-    const int nblocks = (int)(grid.x * grid.y * grid.z);
-    uocr_note_split(ctx, nblocks, (long long)tiles_x * tiles_y * d.n);
     int rc = UOCR_OK;
-    float* partial = uocr_partial_buffer(ctx, (size_t)nblocks * 5 * t542::NACC * sizeof(float), &rc);
-    if (rc) return rc;
-    UOCR_DISPATCH_TA(ctx, dtype, {
-        hipLaunchKernelGGL((conv_wgrad_t542<TA>), grid, dim3(320), 0, ctx->stream, (const TA*)x, (const TA*)dy, partial,
-                           d.h, d.w, (float)pad_value, per_block);
-    });
-    UOCR_LAUNCH_CHECK(ctx);
-    const float unscale = (float)uocr_grad_unscale(dtype);
-    const FinishDesc fd = finish_taprows(partial, nblocks, t542::NACC, 40, 2, (float*)dw, (float*)db, use_bias, accumulate,
-                                         unscale);
-    return uocr_finish(ctx, fd, [&] {
-        hipLaunchKernelGGL(conv_wgrad_t542_finish, dim3(202), dim3(256), 0, ctx->stream, (const float*)partial, (float*)dw,
-                           (float*)db, nblocks, use_bias, accumulate, unscale);
-    });
+    if (with_fast_conv(d, [&](auto fc) { rc = uocr_noted_conv(ctx, 1, fc.DX_KERNEL, fc.dgrad(ctx, dtype, dy, w, dx, d, mask)); }))
+        return rc;
+    UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "no fast conv kernel for this shape");
 }
 
 int uocr_conv_wgrad_fast(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw, void* db,
@@ -1464,22 +1446,28 @@ int uocr_conv_wgrad_fast(uocr_ctx* ctx, int dtype, const void* x, const void* dy
         uocr_note_conv(ctx, 2, UOCR_CONV_C16_WGRAD);
         return UOCR_OK;
     }
-    if (d.kh == 5 && d.kw == 5 && d.sh == 2 && d.sw == 2 && d.ph == 2 && d.pw == 2 && ctx->opt_tiled == 1) {
-        // (measured against conv_wgrad_fast on one box: 1 -> 4 20 vs 25 us; 1 -> 1 17 vs 15 and 4 -> 4 34 vs 29 us
-        // lose -- too little work per staged tile -- and stay on the register kernels)
-        if (d.cin == 1 && d.cout == 4)
-            return uocr_noted_conv(ctx, 2, UOCR_CONV_WGRAD_S2_TILED,
-                                   launch_wgrad_s2<1, 4>(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate));
-    }
-    if (d.kh == 5 && d.kw == 5 && d.cin == 4 && d.cout == 2 && d.sh == 1 && d.sw == 1 && d.ph == 2 && d.pw == 2)
-        return uocr_noted_conv(ctx, 2, UOCR_CONV_WGRAD_T542,
-                               launch_wgrad_t542(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate));
-#define X(KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX)                   \
-    if (FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::match(d)) \
-        return uocr_noted_conv(ctx, 2, UOCR_CONV_TABLE_FAST,                                    \
-                               FastConv<KH, KW, CIN, COUT, SH, SW, COB, PY, DPY, KYR, WCOB, WPY, FPX, DPX>::wgrad( \
-                                   ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate));
-    UOCR_FAST_CONVS(X)
-#undef X
+    // (conv_wgrad_s2_tiled measured against conv_wgrad_fast on one box: 1 -> 4 20 vs 25 us; 1 -> 1 17 vs 15 and 4 -> 4
+    // 34 vs 29 us lose -- too little work per staged tile -- and stay on the register kernels)
+    if (is_5x5_s2_pad2(d) && ctx->opt_tiled == 1 && d.cin == 1 && d.cout == 4)
+        return launch_wgrad_taprows<S2Cfg<1, 4>>(
+            ctx, dtype, UOCR_CONV_WGRAD_S2_TILED, d.n, d.oh, d.ow, dw, db, use_bias, accumulate,
+            [&](auto ta, dim3 grid, float* partial, int per_block) {
+                using TA = decltype(ta);
+                hipLaunchKernelGGL((conv_wgrad_s2_tiled<1, 4, TA>), grid, dim3(320), 0, ctx->stream, (const TA*)x,
+                                   (const TA*)dy, partial, d.h, d.w, d.oh, d.ow, (float)pad_value, per_block);
+            });
+    if (is_5x5_s1_pad2(d) && d.cin == 4 && d.cout == 2)
+        return launch_wgrad_taprows<t542::Taprows>(
+            ctx, dtype, UOCR_CONV_WGRAD_T542, d.n, d.h, d.w, dw, db, use_bias, accumulate,
+            [&](auto ta, dim3 grid, float* partial, int per_block) {
+                using TA = decltype(ta);
+                hipLaunchKernelGGL((conv_wgrad_t542<TA>), grid, dim3(320), 0, ctx->stream, (const TA*)x, (const TA*)dy,
+                                   partial, d.h, d.w, (float)pad_value, per_block);
+            });
+    int rc = UOCR_OK;
+    if (with_fast_conv(d, [&](auto fc) {
+            rc = uocr_noted_conv(ctx, 2, UOCR_CONV_TABLE_FAST, fc.wgrad(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate));
+        }))
+        return rc;
     UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "no fast conv kernel for this shape");
 }
