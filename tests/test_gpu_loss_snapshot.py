@@ -460,12 +460,12 @@ def test_trainer_past_one_lap(ring_len):
             runs.append((trainer, kept))
         truth, (trainer, kept) = runs[0][1], runs[1]
         assert len({tuple(step['Line']) for step in truth}) == steps          # every step has losses of its own
-        rings = {name: entry['arena'].ring is not None for name, entry in trainer._captured.items()}
+        rings = {name: entry.arena.ring is not None for name, entry in trainer._captured.items()}
         assert rings['Line'] and set(rings) == set(truth[0])
         stale = fresh = 0
         for name in rings:
             backed = [rings[name] and not (name == 'Line' and i in eager_at) for i in range(steps)]
-            arena = trainer._captured[name]['arena']
+            arena = trainer._captured[name].arena
             if rings[name]:
                 device = int(CP.asnumpy(arena.counter)[0])
                 assert arena.rows == device == 1 + sum(backed), f'{name}: host {arena.rows}, device {device}'

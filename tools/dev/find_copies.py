@@ -26,7 +26,7 @@ context = trainer.make_context(layers)
 phase[0] = 'capture'
 trainer.capture(context)
 for name, entry in trainer._captured.items():
-    print(name, 'ring' if entry['arena'].ring is not None else 'NO RING', flush=True)
+    print(name, 'ring' if entry.arena.ring is not None else 'NO RING', flush=True)
 phase[0] = 'step'
 trainer.step(context)
 trainer.step(context)

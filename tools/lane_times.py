@@ -73,10 +73,10 @@ for _ in range(reps):
     for comp in trainer._lane_order():               # the enqueue order of PageTrainer.step
         with rt.lane(trainer.lanes[comp.name]) as stream:
             stream.wait_event(start)
-            trainer._captured[comp.name]['begin'].replay()
+            trainer._captured[comp.name].replay_begin()
             mids[comp.name] = torch.cuda.Event(enable_timing=True)
             mids[comp.name].record(stream)
-            trainer._captured[comp.name]['finish'].replay()
+            trainer._captured[comp.name].finish.replay()
             ends[comp.name] = torch.cuda.Event(enable_timing=True)
             ends[comp.name].record(stream)
     torch.cuda.synchronize()

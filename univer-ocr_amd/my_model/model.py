@@ -405,6 +405,13 @@ class Modes(Enum):
     TRAIN_PAGE = 6        # this backend: all four nets on device-resident page / line batches
 
 
+# {context label: dataset layer tag} of Modes.TRAIN_PAGE (make_context_maker, trainer.PageTrainer.make_context)
+TRAIN_PAGE_CONTEXT = {'monochrome_X': 'image', 'monochrome_y': 'monochrome',
+                      'paragraph_X': 'monochrome', 'paragraph_y': 'paragraph',
+                      'line_X': 'monochrome', 'line_y': 'line',
+                      'char_X': 'char_lines', 'char_y': 'char_labels'}
+
+
 def _context_maker(mapping):
     """dataset layers -> context dict {label: the layer `tag` on the device} for mapping = {label: tag}"""
     def make_context(dataset_get_func, args=(), kwargs={}):
@@ -418,10 +425,7 @@ def make_context_maker(mode=Modes.PREDICT):
     wanted = {
         Modes.TRAIN_MONOCHROME: {'monochrome_X': 'image', 'monochrome_y': 'monochrome'},
         Modes.TRAIN_PARAGRAPH: {'paragraph_X': 'monochrome', 'paragraph_y': 'paragraph'},
-        Modes.TRAIN_PAGE: {'monochrome_X': 'image', 'monochrome_y': 'monochrome',
-                           'paragraph_X': 'monochrome', 'paragraph_y': 'paragraph',
-                           'line_X': 'monochrome', 'line_y': 'line',
-                           'char_X': 'char_lines', 'char_y': 'char_labels'},
+        Modes.TRAIN_PAGE: TRAIN_PAGE_CONTEXT,
         # model.py:438-447 keeps these three on the host (`*_cpu`) for its host crop stage; here the crop runs on the device
         Modes.TRAIN_LINE: {'monochrome_pred': 'monochrome', 'paragraph_pred': 'paragraph', 'line': 'line'},
         Modes.PREDICT: {'monochrome_X': 'image'},

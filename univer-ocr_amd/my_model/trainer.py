@@ -8,14 +8,15 @@
                   passes, lr decay, NaN rollback to the last (then best) weights, best-weights
                   callback.  Host orchestration only.
 """
+import contextlib
 import os
 
 import numpy as np
 import torch.distributed as dist
 
-from ..nn.gpu import CP
+from ..nn.gpu import CP, DeviceScalar
 from ..nn.optimizers import Adam, Momentum
-from .model import CHAR_INPUT_HEIGHT, Modes, make_model_system
+from .model import CHAR_INPUT_HEIGHT, TRAIN_PAGE_CONTEXT, Modes, make_model_system
 
 
 def make_optimizer(name, lr):
@@ -26,15 +27,82 @@ def make_optimizer(name, lr):
     raise ValueError(f'unknown optimizer {name}')
 
 
-class GraphSequence:
-    """The graphs of one net's forward + loss + backward, in order (two when its gradient tail is reduced early)."""
+def _wgrad_nets(argument, variable, default, names):
+    """Which of the nets `names` an option like side_wgrad selects: the constructor argument (a tuple of net names, 'all'
+    = every net), else the comma-separated environment variable, else `default`."""
+    if argument is None:
+        argument = tuple(n for n in os.environ.get(variable, default).split(',') if n)
+    return {name for name in names if name in argument or 'all' in argument}
 
-    def __init__(self, parts):
-        self.parts = list(parts)
 
-    def replay(self):
-        for part in self.parts:
+@contextlib.contextmanager
+def _collectives_off(model):
+    """Take the data-parallel hooks off `model` for a graph capture; they are back on every way out of the block."""
+    sync, model.grad_sync = model.grad_sync, None         # collectives are not captured
+    hook, model.bucket_hook = model.bucket_hook, None     # (replays reduce the whole buffer at once)
+    try:
+        yield
+    finally:
+        model.grad_sync = sync
+        model.bucket_hook = hook                              # (eager steps of this net keep reducing the tail early)
+
+
+class _CutCapture:
+    """`with _CutCapture(rt, pool) as cap:` records what runs inside on the current lane into cap.graphs: one graph, and
+    one more for every cap.cut() called inside."""
+
+    def __init__(self, rt, pool):
+        self.rt, self.pool, self.graphs = rt, pool, []
+        self._open = contextlib.ExitStack()
+
+    def _start(self):
+        self.graphs.append(self._open.enter_context(self.rt.capture(self.pool)))
+
+    def __enter__(self):
+        self._start()
+        return self
+
+    def cut(self):
+        self.rt.flush_deferred()           # (recorded weight gradients of the tail: into THIS graph)
+        self._open.close()
+        self._start()
+
+    def __exit__(self, *exc):
+        return self._open.__exit__(*exc)
+
+
+class CapturedNet:
+    """One net's step as HIP graphs (PageTrainer._capture_net) and the static arrays they write.
+    begin: the graphs of forward + loss + backward, in order (two when the gradient tail is reduced early);
+    finish: the graph of L2 + optimizer + gradient reset; arena: the LossArena of the loss slots, slot_index their places
+    in it (output losses, then the regularization loss); output_losses / regularization_loss: the slots' tensors;
+    prediction: the published output, or None."""
+
+    __slots__ = ('begin', 'finish', 'arena', 'slot_index', 'output_losses', 'regularization_loss', 'prediction')
+
+    def __init__(self, begin, finish, arena, output_losses, regularization_loss, prediction):
+        self.begin, self.finish, self.arena, self.prediction = list(begin), finish, arena, prediction
+        self.output_losses, self.regularization_loss = list(output_losses), regularization_loss
+        self.slot_index = [arena.index_of(t) for t in self.output_losses + [regularization_loss]]
+
+    def replay_begin(self, dp=None, model=None):
+        """Replay the begin graphs on the current lane; a cut net hands its gradient tail to `dp` between its two."""
+        self.begin[0].replay()
+        for part in self.begin[1:]:                       # the gradient tail is final: its all-reduce starts now
+            if dp is not None:
+                dp.tail_ready(model)
             part.replay()
+
+    def step_losses(self, snapshot):
+        """{'output_losses', 'regularization_loss'} of the finish graph just replayed on the current lane."""
+        if snapshot:                                      # the row of the ring the replayed optimizer tail wrote to,
+            arena = self.arena                            # or (no fused tail) one 8-byte-per-loss copy on the lane
+            snap = arena.next_row() if arena.ring is not None else arena.snapshot()
+            ringed = arena if arena.ring is not None else None                           # (a ring row is recycled: stamped)
+            values = [DeviceScalar(snap.t[i], arena=ringed) for i in self.slot_index]
+        else:                                             # aliases of the static slots: read before the next step()
+            values = [DeviceScalar(t) for t in self.output_losses] + [DeviceScalar(self.regularization_loss)]
+        return {'output_losses': values[:-1], 'regularization_loss': values[-1]}
 
 
 class PageTrainer:
@@ -59,45 +127,27 @@ class PageTrainer:
         for model in self.models.values():
             model.enable_fusion(fuse, windows=os.environ.get('UOCR_WINDOWS_FUSION', '1') != '0')   # conv + LeakyReLU / Sigmoid as one forward kernel
             model.skip_input_grads(not input_grads)   # False: drop the page-input gradient nobody reads
+        if data_parallel is None:
+            data_parallel = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         # side_wgrad: nets whose weight-gradient kernels run on a side stream of their lane (Runtime.side): the dX chain of
         # the backward pass does not wait for them.  Measured (tools/dev/side_ab.sh): the Char net
         # ALONE gains (0.433 -> 0.397 ms/step), but the page step with its three lanes loses badly (0.845 -> 1.18 ms with
         # the Char net forked, 2.3 ms with all nets): every fork adds a stream to the captured graphs and the device
         # time-slices the hardware queues beyond the few it runs at once.  Off by default; results are bit-identical.
-        if side_wgrad is None:
-            side_wgrad = tuple(n for n in os.environ.get('UOCR_SIDE_WGRAD', '').split(',') if n)
-        for name, model in self.models.items():
-            model.side_wgrad = CP.has_device() and (name in side_wgrad or 'all' in side_wgrad)
+        side_wgrad = _wgrad_nets(side_wgrad, 'UOCR_SIDE_WGRAD', '', self.models)
         # group_wgrad: nets whose backward pass runs inside Runtime.defer_wgrad (uocr_wgrad_defer_*): the finish kernels of
         # the weight-gradient producers (five per step in the Paragraph and Line nets) become ONE launch at the end of the
         # pass, and so do the small weight-gradient GEMMs (the Char net's five).  Default: every net
         # (under data parallelism only the Char net: in the one-rank RCCL rehearsal the page nets' late finish launches cost
         # more than they save -- 0.865 ms/step with 'Char', 0.880 with 'all', 0.905 with none; without it 0.835 / 0.822 / 0.852)
-        if data_parallel is None:
-            data_parallel = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-        if group_wgrad is None:
-            group_wgrad = tuple(n for n in os.environ.get('UOCR_GROUP_WGRAD', 'Char' if data_parallel else 'all').split(',') if n)
+        group_wgrad = _wgrad_nets(group_wgrad, 'UOCR_GROUP_WGRAD', 'Char' if data_parallel else 'all', self.models)
         for name, model in self.models.items():
-            model.group_wgrad = CP.has_device() and (name in group_wgrad or 'all' in group_wgrad)
+            model.side_wgrad = CP.has_device() and name in side_wgrad
+            model.group_wgrad = CP.has_device() and name in group_wgrad
         # one stream (lane) per net: the nets are independent until the optimizer step
         self.lanes = None
         if lanes and CP.has_device() and len(self.models) > 1:
-            rt = CP.runtime()
-            # (high-priority streams for the latency-bound nets were tried: 1.44 -> 2.54 ms/step)
-            # Nets of one group share a lane and run one after the other in it.  Default: 3 lanes of about
-            # equal length (Monochrome + Paragraph ~ Line ~ Char): the GPU keeps 4 hardware queues running at
-            # a time, and with 4 lanes the 5th stream that has work (main in the joined mode, RCCL's stream
-            # under data parallelism) gets time-sliced against them (1.3 -> 2.6 ms/step measured)
-            self.lanes = {}
-            # lane_xcds: one tuple of XCD numbers per lane group -- CU-partitioned lanes (uocr_ctx_create_cu_mask)
-            for gi, group in enumerate(lane_groups or [(name,) for name in self.models]):
-                members = [name for name in group if name in self.models]
-                if members:
-                    lane = rt.add_lane(xcds=None if not lane_xcds else lane_xcds[gi])
-                    self.lanes.update({name: lane for name in members})
-            for name in self.models:                   # nets not named in any group: a lane each
-                if name not in self.lanes:
-                    self.lanes[name] = rt.add_lane()
+            self.lanes = self._make_lanes(lane_groups, lane_xcds)
         # HIP graphs: each net's forward+loss+backward and its L2+optimizer tail are captured once and
         # replayed (two hipGraphLaunch per net and step instead of ~40 launches); needs lanes
         self.graphs = bool(graphs) and self.lanes is not None
@@ -119,13 +169,13 @@ class PageTrainer:
         self._lane_done = {}
         self._event_rings = {}
         self.eager_nets = tuple(eager_nets)          # nets kept out of the graphs (e.g. to time one kernel)
-        self._captured = None
+        self._captured = None                        # {net: CapturedNet} once the step is captured
         self._eager_override = set()
         self._eager_steps = 0
         self._input_buffers = {}
+        self._statics, self._clones = {}, {}         # {context label: the array the graphs read}, {id(foreign array): clone}
+        self._fwd_captured = None                    # forward(): {net: (graph, input, prediction)}
         self.dp = None
-        if data_parallel is None:
-            data_parallel = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         if data_parallel:
             from ..parallel import DataParallel
             # construction order = the order the collectives of a step are issued in on every rank = the order the
@@ -138,6 +188,26 @@ class PageTrainer:
             self.dp_backend = self.dp.backend
             for model in self.models.values():
                 model.defer_grad_sync = overlap
+
+    def _make_lanes(self, lane_groups, lane_xcds):
+        """{net: lane index of the runtime}."""
+        rt = CP.runtime()
+        # (high-priority streams for the latency-bound nets were tried: 1.44 -> 2.54 ms/step)
+        # Nets of one group share a lane and run one after the other in it.  Default: 3 lanes of about
+        # equal length (Monochrome + Paragraph ~ Line ~ Char): the GPU keeps 4 hardware queues running at
+        # a time, and with 4 lanes the 5th stream that has work (main in the joined mode, RCCL's stream
+        # under data parallelism) gets time-sliced against them (1.3 -> 2.6 ms/step measured)
+        lanes = {}
+        # lane_xcds: one tuple of XCD numbers per lane group -- CU-partitioned lanes (uocr_ctx_create_cu_mask)
+        for gi, group in enumerate(lane_groups or [(name,) for name in self.models]):
+            members = [name for name in group if name in self.models]
+            if members:
+                lane = rt.add_lane(xcds=None if not lane_xcds else lane_xcds[gi])
+                lanes.update({name: lane for name in members})
+        for name in self.models:                   # nets not named in any group: a lane each
+            if name not in lanes:
+                lanes[name] = rt.add_lane()
+        return lanes
 
     def reinit_weights(self, seed):
         """Zero-mean He initialisation (the reference's kaiming_normal, initializers.py:16-19) drawn from a
@@ -158,10 +228,7 @@ class PageTrainer:
 
     def make_context(self, layers):
         """Host layer dict (synthetic.make_page_batch) -> device-resident context."""
-        mapping = {'monochrome_X': 'image', 'monochrome_y': 'monochrome',
-                   'paragraph_X': 'monochrome', 'paragraph_y': 'paragraph',
-                   'line_X': 'monochrome', 'line_y': 'line',
-                   'char_X': 'char_lines', 'char_y': 'char_labels'}
+        mapping = TRAIN_PAGE_CONTEXT
         if self.graphs:
             # graph replay reads fixed addresses: the trainer owns one input buffer per layer tag and
             # every make_context refills them in place (no device-to-device copy in step())
@@ -184,21 +251,31 @@ class PageTrainer:
 
     def step(self, context):
         """Train every net once.  Returns {net: {'output_losses': [...], 'regularization_loss': r}}."""
-        comps = self.model_system.components
         if self.lanes is not None:
             return self._step_lanes(context)
         if self.dp is None or not self.dp.overlap:
             self.model_system.train(context)
             return context['losses']
+        comps = self.model_system.components
         context['losses'] = {}
         for comp in comps:                          # enqueue fwd+bwd of every net, all-reduces in flight
-            comp.selector(context)
-            X, y = next(comp.selector.get())
-            comp.model.train_begin(X, y)
-            comp._publish()
+            self._begin(comp, context)
         for comp in comps:                          # then finish: wait, L2, optimizer
-            context['losses'][comp.name] = comp.model.train_finish()
+            context['losses'][comp.name] = self._finish(comp)
         return context['losses']
+
+    # the two phases of one net's eager step (on the current stream; `stream` = its lane's, if it has one)
+    def _begin(self, comp, context, stream=None):
+        comp.selector(context)
+        X, y = next(comp.selector.get())
+        if self.pipelined:                          # the caller may drop these arrays before the lane is done
+            X.t.record_stream(stream)
+            y.t.record_stream(stream)
+        comp.model.train_begin(X, y)
+        comp._publish()
+
+    def _finish(self, comp):
+        return comp.model.train_finish()
 
     def _lane_order(self):
         """Enqueue order of the nets: the nets that are long chains of short kernels first (their chain is the
@@ -210,33 +287,60 @@ class PageTrainer:
     def _step_lanes(self, context):
         """Every net on its own stream.  The lanes start after everything already queued on the main
         stream (the inputs) and the main stream ends the step by waiting for all of them.  With data
-        parallelism each net's all-reduce is issued from its lane right after its backward."""
-        if self.graphs:
-            if self._captured is None and self._eager_steps >= 2:     # lazy initialisation is over
+        parallelism each net's all-reduce is issued from its lane right after its backward.
+        A net in `replayed` replays its CapturedNet, every other one runs _begin / _finish."""
+        if self.graphs and self._captured is None:
+            if self._eager_steps >= 2:                 # lazy initialisation is over
                 self._capture(context)
-            if self._captured is not None:
-                return self._step_graphs(context)
-            self._eager_steps += 1
+            else:
+                self._eager_steps += 1
         rt = CP.runtime()
+        replayed = {}
+        if self._captured is not None:
+            replayed = {name: net for name, net in self._captured.items() if name not in self._eager_override}
+            self.optimizer.refresh_hyper()             # lr / betas changed since the last step? (device array)
+            self._fill_statics(context)
         start = self._event('start').record()              # (on the main stream: after the inputs queued there)
-        context['losses'] = {}
         comps = self._lane_order()
         for comp in comps:
+            net, model = replayed.get(comp.name), comp.model
             with rt.lane(self.lanes[comp.name]) as stream:
                 start.wait()
-                comp.selector(context)
-                X, y = next(comp.selector.get())
-                if self.pipelined:                     # the caller may drop these arrays before the lane is done
-                    X.t.record_stream(stream)
-                    y.t.record_stream(stream)
-                comp.model.train_begin(X, y)
-                comp._publish()
+                if net is None:
+                    self._begin(comp, context, stream)
+                    continue
+                net.replay_begin(self.dp, model)
+                if model.grad_sync is not None:
+                    model.grad_sync(model)             # RCCL all-reduce of the (rest of the) flat gradient
+        context['losses'] = {}
         for comp in comps:
+            net, model = replayed.get(comp.name), comp.model
             with rt.lane(self.lanes[comp.name]):
-                context['losses'][comp.name] = comp.model.train_finish()
+                if net is None:
+                    losses = self._finish(comp)
+                else:
+                    if model.grad_sync is not None and model.defer_grad_sync:
+                        self.dp.wait(model)
+                    net.finish.replay()
+                    losses = net.step_losses(self.snapshot_losses)
                 done = self._event(comp.name).record()
-            self._finish_lane(comp.name, done, context['losses'][comp.name])
+            if net is not None and net.prediction is not None:
+                context[comp.selector.pred_label] = net.prediction
+            context['losses'][comp.name] = losses
+            self._finish_lane(comp.name, done, losses)
         return context['losses']
+
+    def _fill_statics(self, context):
+        """New batch -> the static inputs of the graphs (nothing to do for the arrays that ARE the statics)."""
+        rt = CP.runtime()
+        if self.pipelined and any(context[label] is not static for label, static in self._statics.items()):
+            self.join()                                      # the copies below overwrite what the lanes read
+        copied = set()
+        for label, static in self._statics.items():
+            fresh = context[label]
+            if fresh is not static and (id(fresh), id(static)) not in copied:
+                rt.call('uocr_d2d', static.ptr, fresh.ptr, static.nbytes)
+                copied.add((id(fresh), id(static)))
 
     def _event(self, key):
         """Events of the C ABI, a ring of four per key: an event that is recorded again still stands for "at least
@@ -252,7 +356,6 @@ class PageTrainer:
             done.wait()                                    # the main stream waits for the lane
             return
         self._lane_done[name] = done
-        from ..nn.gpu import DeviceScalar
         for value in list(losses['output_losses']) + [losses['regularization_loss']]:
             if isinstance(value, DeviceScalar):
                 value.ready = done
@@ -273,19 +376,17 @@ class PageTrainer:
         slots (consecutive in one LossArena per net) and the published outputs are static outputs.  PyTorch only
         provides the memory: one MemPool per net keeps what a graph's kernels read and write apart from every later
         allocation."""
-        import torch
-        from ..nn.gpu import DeviceScalar, LossArena
         if not CP.lazy_losses:
             raise RuntimeError('PageTrainer(graphs=True) needs CP.lazy_losses = True: a loss read with float() '
                                'inside the step is a host sync, which a HIP graph cannot contain')
-        rt = CP.runtime()
-        captured = {}
-        for comp in self.model_system.components:
-            model = comp.model
-            if comp.name in self.eager_nets:
-                continue
-            sync, model.grad_sync = model.grad_sync, None         # collectives are not captured
-            hook, model.bucket_hook = model.bucket_hook, None     # (replays reduce the whole buffer at once)
+        self._captured = {comp.name: self._capture_net(comp, context)
+                          for comp in self.model_system.components if comp.name not in self.eager_nets}
+
+    def _capture_net(self, comp, context):
+        import torch
+        from ..nn.gpu import LossArena
+        rt, model = CP.runtime(), comp.model
+        with _collectives_off(model):
             comp.selector(context)
             labels = (comp.selector.X_label, comp.selector.y_label)
             X, y = (self._static_input(label, context[label]) for label in labels)
@@ -293,7 +394,6 @@ class PageTrainer:
             # data parallel, a net whose gradient tail is final early (parallel.DataParallel.split_node: the Char net's
             # dense block): graph A is cut there, so that the replay can reduce the tail while the rest of A runs
             split = self.dp.split_node(model) if self.dp is not None else None
-            parts = []
             try:
                 with rt.lane(self.lanes[comp.name]):
                     # the loss slots and their snapshot ring live as long as the graphs: allocated BEFORE the first capture
@@ -303,25 +403,14 @@ class PageTrainer:
                         arena = CP.loss_arena = LossArena(16, ring_len=self.snapshot_ring_len)
                         if ring:
                             arena.arm()
-                    cap = [rt.capture(pool)]
-                    cap[0].__enter__()
-
-                    def cut(_model, node, cap=cap, parts=parts, split=split):
-                        if node == split:
-                            rt.flush_deferred()           # (recorded weight gradients of the tail: into THIS graph)
-                            cap[0].__exit__(None, None, None)
-                            parts.append(cap[0].graph)
-                            cap[0] = rt.capture(pool)
-                            cap[0].__enter__()
-                    model.bucket_hook = cut if split is not None else None
-                    try:
+                    with _CutCapture(rt, pool) as begin:
+                        def cut_at_split(_model, node):
+                            if node == split:
+                                begin.cut()
+                        model.bucket_hook = cut_at_split if split is not None else None
                         model.train_begin(X, y)
                         comp._publish()
-                    finally:
-                        model.bucket_hook = None
-                        cap[0].__exit__(None, None, None)
-                    parts.append(cap[0].graph)
-                    begin = GraphSequence(parts)
+                    model.bucket_hook = None
                     pending = model._pending_losses
                     with rt.capture(pool) as finish:
                         if ring:                              # the optimizer tail itself snapshots the loss slots
@@ -333,17 +422,11 @@ class PageTrainer:
             finally:
                 CP.loss_arena = None
             slots = pending + [losses['regularization_loss']]
-            for value in slots:
-                if not isinstance(value, DeviceScalar):
-                    raise RuntimeError('graph capture: a loss was materialised on the host')
-            captured[comp.name] = dict(begin=begin, finish=finish, arena=arena,
-                                       slot_index=[arena.index_of(v.t) for v in slots],
-                                       output_losses=[v.t for v in pending],
-                                       regularization_loss=losses['regularization_loss'].t,
-                                       prediction=context.get(comp.selector.pred_label))
-            model.grad_sync = sync
-            model.bucket_hook = hook                              # (eager steps of this net keep reducing the tail early)
-        self._captured = captured
+            if not all(isinstance(value, DeviceScalar) for value in slots):
+                raise RuntimeError('graph capture: a loss was materialised on the host')
+            return CapturedNet(begin.graphs, finish, arena, output_losses=[v.t for v in pending],
+                               regularization_loss=losses['regularization_loss'].t,
+                               prediction=context.get(comp.selector.pred_label))
 
     def capture(self, context):
         """Run the eager steps still needed for lazy initialisation, then record the graphs now (step()
@@ -367,8 +450,6 @@ class PageTrainer:
     def _static_input(self, label, array):
         """The array the graphs read for `label`: the trainer's own input buffer if the caller uses
         make_context(), otherwise a private clone (a foreign array is never written to)."""
-        if not hasattr(self, '_statics'):
-            self._statics, self._clones = {}, {}
         if any(array is own for own in self._input_buffers.values()):
             static = array
         else:
@@ -377,67 +458,6 @@ class PageTrainer:
                 static = self._clones[id(array)] = array.copy()
         self._statics[label] = static
         return static
-
-    def _step_graphs(self, context):
-        from ..nn.gpu import DeviceArray, DeviceScalar
-        rt = CP.runtime()
-        comps = self._lane_order()
-        self.optimizer.refresh_hyper()                   # lr / betas changed since the last step? (device array)
-        if self.pipelined and any(context[label] is not static for label, static in self._statics.items()):
-            self.join()                                      # the copies below overwrite what the lanes read
-        copied = set()
-        for label, static in self._statics.items():          # new batch -> the graphs' static inputs
-            fresh = context[label]
-            if fresh is not static and (id(fresh), id(static)) not in copied:
-                rt.call('uocr_d2d', static.ptr, fresh.ptr, static.nbytes)
-                copied.add((id(fresh), id(static)))
-        start = self._event('start').record()
-        captured = {n: e for n, e in self._captured.items() if n not in self._eager_override}
-        for comp in comps:
-            entry = captured.get(comp.name)
-            with rt.lane(self.lanes[comp.name]):
-                start.wait()
-                if entry is None:                             # eager net
-                    comp.selector(context)
-                    X, y = next(comp.selector.get())
-                    comp.model.train_begin(X, y)
-                    comp._publish()
-                    continue
-                parts = entry['begin'].parts
-                parts[0].replay()
-                if len(parts) == 2:                           # the gradient tail is final: its all-reduce starts now
-                    comp.model.grad_sync.__self__.tail_ready(comp.model)
-                    parts[1].replay()
-                if comp.model.grad_sync is not None:
-                    comp.model.grad_sync(comp.model)          # RCCL all-reduce of the (rest of the) flat gradient
-        context['losses'] = {}
-        for comp in comps:
-            entry, model = captured.get(comp.name), comp.model
-            snap = None
-            with rt.lane(self.lanes[comp.name]):
-                if entry is None:
-                    context['losses'][comp.name] = model.train_finish()
-                else:
-                    if model.grad_sync is not None and model.defer_grad_sync:
-                        model.grad_sync.__self__.wait(model)
-                    entry['finish'].replay()
-                    if self.snapshot_losses:                  # the row of the ring the replayed optimizer tail wrote to,
-                        arena = entry['arena']                # or (no fused tail) one 8-byte-per-loss copy on the lane
-                        snap = arena.next_row() if arena.ring is not None else arena.snapshot()
-                done = self._event(comp.name).record()
-            if entry is None:
-                self._finish_lane(comp.name, done, context['losses'][comp.name])
-                continue
-            if entry['prediction'] is not None:
-                context[comp.selector.pred_label] = entry['prediction']
-            if snap is not None:
-                ringed = entry['arena'] if entry['arena'].ring is not None else None     # (a ring row is recycled: stamped)
-                values = [DeviceScalar(snap.t[i], arena=ringed) for i in entry['slot_index']]
-            else:                                             # aliases of the static slots: read before the next step()
-                values = [DeviceScalar(t) for t in entry['output_losses']] + [DeviceScalar(entry['regularization_loss'])]
-            context['losses'][comp.name] = {'output_losses': values[:-1], 'regularization_loss': values[-1]}
-            self._finish_lane(comp.name, done, context['losses'][comp.name])
-        return context['losses']
 
     def forward(self, context):
         """Forward pass of every net (reference: ModelSystem.predict -> Model.predict = forward, models.py:270-271).
@@ -452,8 +472,8 @@ class PageTrainer:
         # (one graph per net, replayed on the net's lane.  ONE multi-stream graph for the whole step -- the lanes
         # joining the capture through events -- was measured and lost: 0.30 ms per step against 0.17, the
         # branches of a replayed graph do not overlap the way free-running streams do)
-        if self.graphs and getattr(self, '_fwd_graphs', None) is None:
-            self._fwd_graphs, self._fwd_inputs, self._fwd_preds = {}, {}, {}
+        if self.graphs and self._fwd_captured is None:
+            self._fwd_captured = {}
             for comp in self.model_system.components:                 # warm-up (lazy initialisation), then capture
                 comp.model.predict(context[comp.selector.X_label])
             torch.cuda.synchronize()
@@ -462,7 +482,7 @@ class PageTrainer:
                     X = context[comp.selector.X_label]
                     with rt.capture(torch.cuda.MemPool()) as graph:
                         pred = comp.model.predict(X)[0]
-                    self._fwd_graphs[comp.name], self._fwd_inputs[comp.name], self._fwd_preds[comp.name] = graph, X, pred
+                    self._fwd_captured[comp.name] = (graph, X, pred)
         start = self._event('fwd_start').record()
         done = {}
         for comp in self._lane_order():
@@ -470,11 +490,11 @@ class PageTrainer:
                 start.wait()
                 X = context[comp.selector.X_label]
                 if self.graphs:
-                    static = self._fwd_inputs[comp.name]
+                    graph, static, pred = self._fwd_captured[comp.name]
                     if X is not static:
                         rt.call('uocr_d2d', static.ptr, X.ptr, static.nbytes)
-                    self._fwd_graphs[comp.name].replay()
-                    context[comp.selector.pred_label] = self._fwd_preds[comp.name]
+                    graph.replay()
+                    context[comp.selector.pred_label] = pred
                 else:
                     context[comp.selector.pred_label] = comp.model.predict(X)[0]
                 done[comp.name] = self._event('fwd_' + comp.name).record()

@@ -113,6 +113,7 @@ class Model(BaseModel):
         self._plan = None
         self._pack = None
         self.grad_sync = None            # set by parallel.DataParallel
+        self.grad_wait = None            # ... with it: this lane waits for the reduction grad_sync queued
         self.defer_grad_sync = False     # True: the all-reduce is waited for in train_finish()
         self._pending_losses = None
         self.bucket_hook = None
@@ -386,8 +387,7 @@ class Model(BaseModel):
 
     def compute_loss_and_gradients(self, X, y):
         losses = self._forward_loss_backward(X, y)
-        if self.grad_sync is not None and self.defer_grad_sync:
-            self.grad_sync.__self__.wait(self)
+        self._wait_deferred_sync()
         return {'output_losses': losses, 'regularization_loss': self.regularize()}
 
     def train(self, X, y):
@@ -400,9 +400,12 @@ class Model(BaseModel):
     def train_begin(self, X, y):
         self._pending_losses = self._forward_loss_backward(X, y)
 
-    def train_finish(self):
+    def _wait_deferred_sync(self):
         if self.grad_sync is not None and self.defer_grad_sync:
-            self.grad_sync.__self__.wait(self)
+            self.grad_wait(self)
+
+    def train_finish(self):
+        self._wait_deferred_sync()
         fused = self._fused_tail()
         if fused is not None:                         # regularize + update + clear_grads in one pass
             losses = {'output_losses': self._pending_losses, 'regularization_loss': fused}

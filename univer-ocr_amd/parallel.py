@@ -245,7 +245,7 @@ class DataParallel:
                     self._ev_tail_ready[id(m)] = self.comm.event()
                     self._ev_tail_done[id(m)] = self.comm.event()
         for model in self.models:
-            model.grad_sync = self._sync
+            model.grad_sync, model.grad_wait = self._sync, self.wait
             model.bucket_hook = self._bucket if id(model) in self._split else None
 
     # -- one flat value / gradient buffer for all models ------------------------------------------------------------
@@ -436,6 +436,6 @@ class DataParallel:
 
     def close(self):
         for model in self.models:
-            model.grad_sync = None
+            model.grad_sync = model.grad_wait = None
             model.bucket_hook = None
         self.comm.close()
