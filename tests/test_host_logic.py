@@ -29,6 +29,48 @@ def test_abi_library_exports_every_declared_symbol():
     assert lib.uocr_abi_version() == 4
 
 
+# name -> arguments, the context included: the counts the page stages pinned when they added their entry points
+PINNED_ARGUMENTS = {
+    'uocr_label_components': 12, 'uocr_masked_crop': 17, 'uocr_ctx_last_label': 4,
+    'uocr_label_batch': 14, 'uocr_ctx_last_label_batch': 5,
+    'uocr_char_label': 11, 'uocr_ctx_last_char_label': 5,
+    'uocr_line_crop': 16, 'uocr_ctx_last_line_crop': 5,
+    'uocr_rotated_extent': 13, 'uocr_rotate_crop': 15, 'uocr_ctx_last_rotate': 5,
+    'uocr_rotation_search': 13, 'uocr_rotation_search_workspace': 2, 'uocr_ctx_last_rotation_search': 4,
+    'uocr_pred_to_text': 10, 'uocr_ctx_last_pred_to_text': 4,
+    'uocr_pack_lines': 10, 'uocr_zero_gaps': 9, 'uocr_ctx_last_pack_lines': 4,
+}
+
+
+def test_header_and_binding_declare_the_same_arguments():
+    """every `int uocr_*(...)` of the header has as many parameters as its ctypes prototype; the pinned counts hold in both"""
+    from univer_ocr_amd.hip import lib as hiplib
+    header = open(os.path.join(ROOT, 'include', 'univer_hip.h')).read()
+    code = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', header, flags=re.S)
+    declared = {name: 0 if parameters.strip() == 'void' else len(parameters.split(','))
+                for name, parameters in re.findall(r'\bint\s+(uocr_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', code)}
+    bound = {**hiplib._PROTOS, **{name: argtypes for name, (restype, argtypes) in hiplib._SPECIAL.items()
+                                  if restype is ctypes.c_int}}
+    assert sorted(declared) == sorted(bound), 'the int functions of the header and of the binding are not the same set'
+    for name, arguments in declared.items():
+        assert len(bound[name]) == arguments, f'{name}: {arguments} parameters in univer_hip.h, {len(bound[name])} in lib.py'
+    for name, arguments in PINNED_ARGUMENTS.items():
+        assert declared[name] == arguments and len(hiplib._PROTOS[name]) == arguments, name
+    assert re.search(r'#define\s+UOCR_ABI_VERSION\s+4\b', header), 'symbols are added, the ABI version stays'
+
+
+def launch_report_getters():
+    from univer_ocr_amd.hip import lib as hiplib
+    return sorted(name for name in hiplib._PROTOS if name.startswith('uocr_ctx_last_'))
+
+
+@pytest.mark.parametrize('name', launch_report_getters())
+def test_launch_report_getter_refuses_a_null_context(name):
+    from univer_ocr_amd.hip import lib as hiplib
+    outs = [None] * (len(hiplib._PROTOS[name]) - 1)
+    assert getattr(hiplib.get_lib(), name)(None, *outs) == -1
+
+
 @pytest.mark.parametrize('net_name', ['Monochrome', 'Paragraph', 'Line', 'Char'])
 def test_net_structure_matches_reference(net_name):
     """Layer / parameter names and counts of the flattened nets equal the reference's (golden)."""

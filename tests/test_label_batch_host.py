@@ -5,30 +5,16 @@ runtime that writes counts and rows where the library would, the flood fill of t
 on strided channel views (what the GPU tests use as expected value), and the keyword's way through the systems.
 Nothing here needs a GPU."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
 from test_label_host import flood_fill
 
-NEW_SYMBOLS = {'uocr_label_batch': 14, 'uocr_ctx_last_label_batch': 5}    # name -> arguments, the context included
+NEW_SYMBOLS = ('uocr_label_batch', 'uocr_ctx_last_label_batch')
 
 
 # ---- ABI ---------------------------------------------------------------------------------------------------------------
-def test_header_and_binding_declare_the_new_entry_points():
-    from univer_ocr_amd.hip import lib as hiplib
-    header = open(os.path.join(ROOT, 'include', 'univer_hip.h')).read()
-    for name, arguments in NEW_SYMBOLS.items():
-        declaration = re.search(r'\bint\s+' + name + r'\s*\(([^)]*)\)', header)
-        assert declaration, f'{name} is not declared in univer_hip.h'
-        assert len(declaration.group(1).split(',')) == arguments
-        assert name in hiplib.ABI_SYMBOLS and len(hiplib._PROTOS[name]) == arguments
-    assert re.search(r'#define\s+UOCR_ABI_VERSION\s+4\b', header), 'symbols are added, the ABI version stays'
-
-
 def test_library_exports_the_new_entry_points():
     from univer_ocr_amd.hip import lib as hiplib
     lib = hiplib.get_lib()

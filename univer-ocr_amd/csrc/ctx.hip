@@ -17,47 +17,11 @@ int uocr_ctx_create(int device, size_t workspace_bytes, uocr_ctx** out) {
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || device >= count) return UOCR_ERR_HIP;
     if (hipSetDevice(device) != hipSuccess) return UOCR_ERR_HIP;
-    uocr_ctx* ctx = new uocr_ctx();
+    uocr_ctx* ctx = new uocr_ctx();   // every default is in the struct (uocr_common.h)
     ctx->device = device;
-    ctx->err[0] = 0;
-    ctx->workspace = nullptr;
-    ctx->workspace_bytes = 0;
-    ctx->sync = nullptr;
-    ctx->gemm_defer = nullptr;
-    ctx->snap_src = nullptr;
-    ctx->snap_count = 0;
-    ctx->snap_ring = nullptr;
-    ctx->snap_ring_len = 0;
-    ctx->snap_counter = nullptr;
-    ctx->finish_defer = nullptr;
-    ctx->owns_stream = true;
-    ctx->opt_mfma = 1;
-    ctx->opt_fast = 1;
-    ctx->opt_tiled = 1;
-    ctx->opt_split = 1024;
-    ctx->opt_split_min = 3;
-    ctx->opt_bm = 0;
-    ctx->opt_h16 = 1;
-    ctx->opt_t32 = 2;    // measured: only the 4-channel backward-data beats its vector kernel in the step (conv_t32.hip,
-                         // conv_t32w.hip: bits 64 / 128 = the float32-MFMA weight gradients, 37.0 -> 36.1 k images/s with both)
-    ctx->opt_xcd = 1;
-    ctx->opt_pair_band = 0;
-    ctx->opt_pair_g = 4;
-    ctx->opt_group_blocks = 0;
-    ctx->opt_wgrad_bands = 0;
-    ctx->opt_max_blocks = 0;
-    ctx->opt_act_dispatch = 1;
-    ctx->split_blocks = 0;
-    ctx->split_items = 0;
-    ctx->gemm_bm = ctx->gemm_gm = ctx->gemm_gn = ctx->gemm_nsplit = 0;
-    ctx->gemm_group_count = ctx->gemm_group_split = 0;
-    uocr_note_pair(ctx, 0, 0, 0, 0, 0, 0, 0, 0);
-    uocr_note_conv(ctx, 0, UOCR_CONV_NONE);
-    ctx->opt_h3 = 0;
 #ifdef UOCR_EXPERIMENTS
     if (const char* e = getenv("UOCR_H3")) ctx->opt_h3 = atoi(e);            // development override (tools/dev/h3_ab.sh)
 #endif
-    ctx->opt_pair_pf = -1;   // auto: float32 one step ahead (49.5 us; 50.8 pinned in the loop, 51.8 three ahead), binary16 three (72.1; 73.8 / 75.5)
     if (const char* e = getenv("UOCR_PAIR_PF")) ctx->opt_pair_pf = atoi(e);   // development override (tools/dev/pf_ab.sh)
     if (const char* e = getenv("UOCR_WGRAD_BANDS")) ctx->opt_wgrad_bands = atoi(e);   // development override (tools/dev/bands_ab.sh)
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -65,7 +29,6 @@ int uocr_ctx_create(int device, size_t workspace_bytes, uocr_ctx** out) {
         return UOCR_ERR_HIP;
     }
     hipDeviceProp_t prop;
-    ctx->cu_count = 256;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->cu_count = prop.multiProcessorCount;
     if (workspace_bytes) {
         if (hipMalloc(&ctx->workspace, workspace_bytes) != hipSuccess) {
@@ -168,52 +131,24 @@ int uocr_ctx_set_option(uocr_ctx* ctx, const char* key, int value) {
 }
 
 int uocr_ctx_last_split(uocr_ctx* ctx, int* blocks, long long* items) {
-    UOCR_CHECK_CTX(ctx);
-    UOCR_REQUIRE(ctx, blocks && items);
-    *blocks = ctx->split_blocks;
-    *items = ctx->split_items;
-    return UOCR_OK;
+    return uocr_report_read(ctx, UOCR_REPORT_SPLIT, blocks, items);
 }
 
 int uocr_ctx_last_gemm(uocr_ctx* ctx, int* bm, int* gm, int* gn, int* nsplit) {
-    UOCR_CHECK_CTX(ctx);
-    UOCR_REQUIRE(ctx, bm && gm && gn && nsplit);
-    *bm = ctx->gemm_bm;
-    *gm = ctx->gemm_gm;
-    *gn = ctx->gemm_gn;
-    *nsplit = ctx->gemm_nsplit;
-    return UOCR_OK;
+    return uocr_report_read(ctx, UOCR_REPORT_GEMM, bm, gm, gn, nsplit);
 }
 
 int uocr_ctx_last_gemm_group(uocr_ctx* ctx, int* problems, int* split_problems) {
-    UOCR_CHECK_CTX(ctx);
-    UOCR_REQUIRE(ctx, problems && split_problems);
-    *problems = ctx->gemm_group_count;
-    *split_problems = ctx->gemm_group_split;
-    return UOCR_OK;
+    return uocr_report_read(ctx, UOCR_REPORT_GEMM_GROUP, problems, split_problems);
 }
 
 int uocr_ctx_last_pair(uocr_ctx* ctx, int* kernel, int* g, int* mode, int* pf, int* nw, int* blocks_x, int* bands,
                        int* band_h) {
-    UOCR_CHECK_CTX(ctx);
-    UOCR_REQUIRE(ctx, kernel && g && mode && pf && nw && blocks_x && bands && band_h);
-    *kernel = ctx->pair_kernel;
-    *g = ctx->pair_g;
-    *mode = ctx->pair_mode;
-    *pf = ctx->pair_pf;
-    *nw = ctx->pair_nw;
-    *blocks_x = ctx->pair_blocks_x;
-    *bands = ctx->pair_bands;
-    *band_h = ctx->pair_band_h;
-    return UOCR_OK;
+    return uocr_report_read(ctx, UOCR_REPORT_PAIR, kernel, g, mode, pf, nw, blocks_x, bands, band_h);
 }
 
 int uocr_ctx_last_conv(uocr_ctx* ctx, int* entry, int* kernel) {
-    UOCR_CHECK_CTX(ctx);
-    UOCR_REQUIRE(ctx, entry && kernel);
-    *entry = ctx->conv_entry;
-    *kernel = ctx->conv_kernel;
-    return UOCR_OK;
+    return uocr_report_read(ctx, UOCR_REPORT_CONV, entry, kernel);
 }
 
 void* uocr_ctx_get_stream(uocr_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }

@@ -867,10 +867,7 @@ int launch_mfma(uocr_ctx* ctx, const ALoader& A, const BLoader& B, const Epilogu
     const int tps = (ntiles + nsplit - 1) / nsplit;
     nsplit = (ntiles + tps - 1) / tps;
     float* slabs = nsplit > 1 ? ws_slabs(ctx) : nullptr;
-    ctx->gemm_bm = bm;
-    ctx->gemm_gm = gm;
-    ctx->gemm_gn = gn;
-    ctx->gemm_nsplit = nsplit;
+    uocr_note(ctx, UOCR_REPORT_GEMM, bm, gm, gn, nsplit);
     const dim3 grid(gm, gn, nsplit), block(256);
     if (bm == 128)
         hipLaunchKernelGGL((mfma_gemm_kernel<128, ALoader, BLoader>), grid, block, 0, ctx->stream, A, B, ep, M, N, ntiles, tps,
@@ -1077,11 +1074,8 @@ int defer_flush(uocr_ctx* ctx) {
     }
     int max_split = 1;
     for (int p = 0; p < g.count; ++p) max_split = std::max(max_split, g.shape[p].gz);
-    ctx->gemm_bm = 64;
-    ctx->gemm_gm = ctx->gemm_gn = 0;
-    ctx->gemm_nsplit = max_split;
-    ctx->gemm_group_count = g.count;
-    ctx->gemm_group_split = r.count;
+    uocr_note(ctx, UOCR_REPORT_GEMM, 64, 0, 0, max_split);
+    uocr_note(ctx, UOCR_REPORT_GEMM_GROUP, g.count, r.count);
     hipLaunchKernelGGL(mfma_gemm_group_kernel, dim3(nblocks), dim3(256), 0, ctx->stream, g);
     UOCR_LAUNCH_CHECK(ctx);
     if (r.count > 0) {

@@ -252,7 +252,7 @@ int uocr_label_components(uocr_ctx* ctx, int dtype, const void* x, int n, int h,
                        (const int*)root, labels, table, max_components, n);
     UOCR_LAUNCH_CHECK(ctx);
     launches += 4;
-    ctx->label_th = LTH, ctx->label_tw = LTW, ctx->label_launches = launches;
+    uocr_note(ctx, UOCR_REPORT_LABEL, LTH, LTW, launches);
     return UOCR_OK;
 }
 
@@ -288,12 +288,7 @@ int uocr_masked_crop(uocr_ctx* ctx, int dtype, const void* image, const int* lab
 }
 
 int uocr_ctx_last_label(uocr_ctx* ctx, int* tile_h, int* tile_w, int* launches) {
-    UOCR_CHECK_CTX(ctx);
-    UOCR_REQUIRE(ctx, tile_h && tile_w && launches);
-    *tile_h = ctx->label_th;
-    *tile_w = ctx->label_tw;
-    *launches = ctx->label_launches;
-    return UOCR_OK;
+    return uocr_report_read(ctx, UOCR_REPORT_LABEL, tile_h, tile_w, launches);
 }
 
 }  // extern "C"

@@ -290,18 +290,12 @@ int uocr_label_batch(uocr_ctx* ctx, int dtype, int n_entries, const void* const*
         UOCR_LAUNCH_CHECK(ctx);
         launches += 4;
     }
-    ctx->lb_th = LTH, ctx->lb_tw = LTW, ctx->lb_entries = LB_ENTRIES, ctx->lb_launches = launches;
+    uocr_note(ctx, UOCR_REPORT_LABEL_BATCH, LTH, LTW, LB_ENTRIES, launches);
     return UOCR_OK;
 }
 
 int uocr_ctx_last_label_batch(uocr_ctx* ctx, int* tile_h, int* tile_w, int* entries_per_launch, int* launches) {
-    UOCR_CHECK_CTX(ctx);
-    UOCR_REQUIRE(ctx, tile_h && tile_w && entries_per_launch && launches);
-    *tile_h = ctx->lb_th;
-    *tile_w = ctx->lb_tw;
-    *entries_per_launch = ctx->lb_entries;
-    *launches = ctx->lb_launches;
-    return UOCR_OK;
+    return uocr_report_read(ctx, UOCR_REPORT_LABEL_BATCH, tile_h, tile_w, entries_per_launch, launches);
 }
 
 }  // extern "C"

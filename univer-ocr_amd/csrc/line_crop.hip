@@ -183,18 +183,12 @@ int uocr_line_crop(uocr_ctx* ctx, int dtype, int n_entries, const void* const* s
         });
         launches += 1;
     }
-    ctx->lc_chunk = LC_CHUNK, ctx->lc_vec_bytes = 16, ctx->lc_entries = LC_ENTRIES, ctx->lc_launches = launches;
+    uocr_note(ctx, UOCR_REPORT_LINE_CROP, LC_CHUNK, 16, LC_ENTRIES, launches);
     return UOCR_OK;
 }
 
 int uocr_ctx_last_line_crop(uocr_ctx* ctx, int* elements_per_block, int* store_bytes, int* entries_per_launch, int* launches) {
-    UOCR_CHECK_CTX(ctx);
-    UOCR_REQUIRE(ctx, elements_per_block && store_bytes && entries_per_launch && launches);
-    *elements_per_block = ctx->lc_chunk;
-    *store_bytes = ctx->lc_vec_bytes;
-    *entries_per_launch = ctx->lc_entries;
-    *launches = ctx->lc_launches;
-    return UOCR_OK;
+    return uocr_report_read(ctx, UOCR_REPORT_LINE_CROP, elements_per_block, store_bytes, entries_per_launch, launches);
 }
 
 }  // extern "C"

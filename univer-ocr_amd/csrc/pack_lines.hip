@@ -145,7 +145,7 @@ int pl_launch(uocr_ctx* ctx, int dtype, int n_entries, void* strip, int h, int s
         });
         launches += 1;
     }
-    ctx->pl_chunk = PL_CHUNK, ctx->pl_entries = PL_ENTRIES, ctx->pl_launches = launches;
+    uocr_note(ctx, UOCR_REPORT_PACK_LINES, PL_CHUNK, PL_ENTRIES, launches);
     return UOCR_OK;
 }
 
@@ -185,12 +185,7 @@ int uocr_zero_gaps(uocr_ctx* ctx, int dtype, void* x, int h, int strip_w, int c,
 }
 
 int uocr_ctx_last_pack_lines(uocr_ctx* ctx, int* elements_per_block, int* entries_per_launch, int* launches) {
-    UOCR_CHECK_CTX(ctx);
-    UOCR_REQUIRE(ctx, elements_per_block && entries_per_launch && launches);
-    *elements_per_block = ctx->pl_chunk;
-    *entries_per_launch = ctx->pl_entries;
-    *launches = ctx->pl_launches;
-    return UOCR_OK;
+    return uocr_report_read(ctx, UOCR_REPORT_PACK_LINES, elements_per_block, entries_per_launch, launches);
 }
 
 }  // extern "C"

@@ -279,17 +279,12 @@ int uocr_pred_to_text(uocr_ctx* ctx, int dtype, int n_lines, const void* const* 
         UOCR_LAUNCH_CHECK(ctx);
         launches += 2;
     }
-    ctx->pt_rows = PT_ROWS, ctx->pt_lines = PT_LINES, ctx->pt_launches = launches;
+    uocr_note(ctx, UOCR_REPORT_PRED_TO_TEXT, PT_ROWS, PT_LINES, launches);
     return UOCR_OK;
 }
 
 int uocr_ctx_last_pred_to_text(uocr_ctx* ctx, int* rows_per_block, int* lines_per_launch, int* launches) {
-    UOCR_CHECK_CTX(ctx);
-    UOCR_REQUIRE(ctx, rows_per_block && lines_per_launch && launches);
-    *rows_per_block = ctx->pt_rows;
-    *lines_per_launch = ctx->pt_lines;
-    *launches = ctx->pt_launches;
-    return UOCR_OK;
+    return uocr_report_read(ctx, UOCR_REPORT_PRED_TO_TEXT, rows_per_block, lines_per_launch, launches);
 }
 
 }  // extern "C"

@@ -307,7 +307,7 @@ int uocr_rotated_extent(uocr_ctx* ctx, const int* labels, int n, int h, int w, i
         UOCR_LAUNCH_CHECK(ctx);
         launches += 2;
     }
-    ctx->rt_band = RT_BAND, ctx->rt_block = RT_NT, ctx->rt_entries = RT_ENTRIES, ctx->rt_launches = launches;
+    uocr_note(ctx, UOCR_REPORT_ROTATE, RT_BAND, RT_NT, RT_ENTRIES, launches);
     return UOCR_OK;
 }
 
@@ -369,7 +369,7 @@ int uocr_rotate_crop(uocr_ctx* ctx, int dtype, int n_entries, const void* const*
         });
         launches += 1;
     }
-    ctx->rt_band = RT_BAND, ctx->rt_block = RT_NT, ctx->rt_entries = RT_ENTRIES, ctx->rt_launches = launches;
+    uocr_note(ctx, UOCR_REPORT_ROTATE, RT_BAND, RT_NT, RT_ENTRIES, launches);
     return UOCR_OK;
 }
 
@@ -430,27 +430,16 @@ int uocr_rotation_search(uocr_ctx* ctx, const int* labels, int n, int h, int w, 
             launches += 2;
         }
     }
-    ctx->rs_rounds = rounds, ctx->rs_paragraphs = RS_PARAGRAPHS, ctx->rs_launches = launches;
+    uocr_note(ctx, UOCR_REPORT_ROTATION_SEARCH, rounds, RS_PARAGRAPHS, launches);
     return UOCR_OK;
 }
 
 int uocr_ctx_last_rotation_search(uocr_ctx* ctx, int* rounds, int* paragraphs_per_launch, int* launches) {
-    UOCR_CHECK_CTX(ctx);
-    UOCR_REQUIRE(ctx, rounds && paragraphs_per_launch && launches);
-    *rounds = ctx->rs_rounds;
-    *paragraphs_per_launch = ctx->rs_paragraphs;
-    *launches = ctx->rs_launches;
-    return UOCR_OK;
+    return uocr_report_read(ctx, UOCR_REPORT_ROTATION_SEARCH, rounds, paragraphs_per_launch, launches);
 }
 
 int uocr_ctx_last_rotate(uocr_ctx* ctx, int* rows_per_band, int* pixels_per_block, int* entries_per_launch, int* launches) {
-    UOCR_CHECK_CTX(ctx);
-    UOCR_REQUIRE(ctx, rows_per_band && pixels_per_block && entries_per_launch && launches);
-    *rows_per_band = ctx->rt_band;
-    *pixels_per_block = ctx->rt_block;
-    *entries_per_launch = ctx->rt_entries;
-    *launches = ctx->rt_launches;
-    return UOCR_OK;
+    return uocr_report_read(ctx, UOCR_REPORT_ROTATE, rows_per_band, pixels_per_block, entries_per_launch, launches);
 }
 
 }  // extern "C"

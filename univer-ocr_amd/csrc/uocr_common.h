@@ -9,54 +9,71 @@
 
 #include "univer_hip.h"
 
+// ---- launch reports: what the last accepted call of a kind chose, read back by the uocr_ctx_last_* getters.
+// To add one: (1) an entry in this enum, (2) uocr_note(ctx, UOCR_REPORT_X, v0, v1, ...) at the end of the launcher, after
+// its launches and never on an error path, (3) a getter next to the launcher that is one `return uocr_report_read(ctx,
+// UOCR_REPORT_X, out0, out1, ...)` with the outs in the order of the noted values, (4) its declaration and comment in
+// include/univer_hip.h, (5) its line in _PROTOS of hip/lib.py, (6) a Runtime.last_x in nn/gpu.py that returns
+// self._report('uocr_ctx_last_x').  A new context reports all zeros.  (The two GEMM launchers of gemm_mfma.hip note just
+// before their launch, not after it: a launch that fails there leaves the new report behind.  Not a pattern to copy.)
+enum uocr_report_id {
+    UOCR_REPORT_SPLIT,            // blocks and work items of the last launch with a run-time split
+    UOCR_REPORT_GEMM,             // row tile, output-tile grid, slabs of the last MFMA GEMM
+    UOCR_REPORT_GEMM_GROUP,       // problems / split problems of the last group flush
+    UOCR_REPORT_PAIR,             // the form of the last Monochrome pair launch (kernel, g, mode, pf) and its geometry
+                                  // (waves per block, grid x, grid y, rows per band)
+    UOCR_REPORT_CONV,             // entry point and kernel family of the last accepted conv call
+    UOCR_REPORT_LABEL,            // tile and launch count of the last labelling call
+    UOCR_REPORT_LABEL_BATCH,      // tile, entries per launch and launch count of the last batched labelling call
+    UOCR_REPORT_CHAR_LABEL,       // sizes and launch count of the last char-label call
+    UOCR_REPORT_LINE_CROP,        // sizes and launch count of the last line-crop call
+    UOCR_REPORT_ROTATE,           // sizes and launch count of the last rotation call
+    UOCR_REPORT_ROTATION_SEARCH,  // rounds, paragraphs per launch and launch count of the last search
+    UOCR_REPORT_PRED_TO_TEXT,     // sizes and launch count of the last pred-to-text call
+    UOCR_REPORT_PACK_LINES,       // sizes and launch count of the last pack-lines or zero-gaps call
+    UOCR_REPORT_COUNT
+};
+constexpr int UOCR_REPORT_VALUES = 8;   // the most values of one report (pair); 64-bit for the item count of split
+
+// Every field states its default here; uocr_ctx_create sets only what depends on its arguments, the environment or the device.
 struct uocr_ctx {
-    int device;
-    hipStream_t stream;
-    bool owns_stream;
-    void* workspace;
-    size_t workspace_bytes;
-    const double* snap_src;   // uocr_ctx_set_loss_snapshot: loss slots the fused optimizer kernels copy into ...
-    int snap_count;
-    double* snap_ring;        // ... row (counter++ % snap_ring_len) of this ring, or snap_src == null
-    int snap_ring_len;
-    unsigned* snap_counter;
-    void* gemm_defer;    // recorded weight-gradient GEMMs of an open deferred group (gemm_mfma.hip), or null
-    void* finish_defer;  // recorded finish kernels + their partial region (finish_group.hip), or null
-    unsigned* sync;      // UOCR_SYNC_WORDS arrival counters of the single-launch reductions (loss.hip): zero between launches
-    int cu_count;
-    int opt_mfma;        // 0 = never, 1 = auto (default), 2 = whenever eligible (tests)
-    int opt_fast;        // 0 = generic kernels only, 1 = shape-specialised fast paths (default)
-    int opt_tiled;       // 0 = no LDS-tiled conv kernels, 1 = use them where instantiated (default)
-    int opt_split;       // MFMA GEMMs split their depth until there are about this many blocks (0 = never)
-    int opt_split_min;   // ... but only when that takes at least this many slabs (a 2-way split rarely pays its reduce)
-    int opt_xcd;         // 1 = MFMA GEMM blocks are renumbered so that neighbours share an XCD (L2)
-    int opt_bm;          // 0 = choose the MFMA GEMM row tile automatically, 64 / 128 = force it (experiments)
-    int opt_h16;         // 1 = binary16-MFMA kernels for the small-channel convs in UOCR_F16 mode (default)
-    int opt_t32;         // float32 vertical-Toeplitz MFMA kernels for the small-channel convs: bit 0 forward, bit 1 backward-data
-    int opt_pair_band;   // rows per band of the strip kernels (0 = about one block per CU)
-    int opt_pair_pf;     // row prefetch of the pair forward kernels (-1 auto / 0 / 1 / 2, see conv_pair_strip.hip)
-    int opt_h3;          // 1 = the float32 Line output conv forward on error-compensated binary16 MFMAs (conv_h3.hip; experiment)
-    int opt_group_blocks; // blocks of a deferred weight-gradient group (0 = four per CU)
-    int opt_wgrad_bands;  // row bands per tap / channel group of the direct weight-gradient kernels (0 = by accumulator count)
-    int opt_pair_g;      // groups of 16 columns per wave of the strip kernels: 4 (8 waves per block) or 2 (16 waves)
-    int opt_act_dispatch; // 1 = activation / mask kinds the nets use are compile-time tags of the kernel (default), 0 = the run-time switch
-    int opt_max_blocks;  // k > 0 lowers every run-time block budget to k (tests: several tiles per block at small shapes)
-    int split_blocks;    // uocr_ctx_last_split: blocks and work items of the last launch with a run-time split
-    long long split_items;
-    int gemm_bm, gemm_gm, gemm_gn, gemm_nsplit;   // uocr_ctx_last_gemm: row tile, output-tile grid, slabs of the last MFMA GEMM
-    int gemm_group_count, gemm_group_split;      // uocr_ctx_last_gemm_group: problems / split problems of the last group flush
-    int pair_kernel, pair_g, pair_mode, pair_pf;  // uocr_ctx_last_pair: the form of the last Monochrome pair launch ...
-    int pair_nw, pair_blocks_x, pair_bands, pair_band_h;   // ... and its geometry (waves per block, grid x, grid y, rows per band)
-    int conv_entry, conv_kernel;                  // uocr_ctx_last_conv: entry point and kernel family of the last accepted conv call
-    int label_th, label_tw, label_launches;       // uocr_ctx_last_label: tile and launch count of the last labelling call
-    int cl_cols, cl_chunk, cl_lines, cl_launches; // uocr_ctx_last_char_label: sizes and launch count of the last char-label call
-    int lc_chunk, lc_vec_bytes, lc_entries, lc_launches;   // uocr_ctx_last_line_crop: sizes and launch count of the last line-crop call
-    int rt_band, rt_block, rt_entries, rt_launches;        // uocr_ctx_last_rotate: sizes and launch count of the last rotation call
-    int rs_rounds, rs_paragraphs, rs_launches;             // uocr_ctx_last_rotation_search: rounds, paragraphs per launch and launch count of the last search
-    int pt_rows, pt_lines, pt_launches;                    // uocr_ctx_last_pred_to_text: sizes and launch count of the last pred-to-text call
-    int lb_th, lb_tw, lb_entries, lb_launches;             // uocr_ctx_last_label_batch: tile, entries per launch and launch count of the last batched labelling call
-    int pl_chunk, pl_entries, pl_launches;                 // uocr_ctx_last_pack_lines: sizes and launch count of the last pack-lines or zero-gaps call
-    char err[512];
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool owns_stream = true;
+    void* workspace = nullptr;
+    size_t workspace_bytes = 0;
+    const double* snap_src = nullptr;   // uocr_ctx_set_loss_snapshot: loss slots the fused optimizer kernels copy into ...
+    int snap_count = 0;
+    double* snap_ring = nullptr;        // ... row (counter++ % snap_ring_len) of this ring, or snap_src == null
+    int snap_ring_len = 0;
+    unsigned* snap_counter = nullptr;
+    void* gemm_defer = nullptr;    // recorded weight-gradient GEMMs of an open deferred group (gemm_mfma.hip), or null
+    void* finish_defer = nullptr;  // recorded finish kernels + their partial region (finish_group.hip), or null
+    unsigned* sync = nullptr;      // UOCR_SYNC_WORDS arrival counters of the single-launch reductions (loss.hip): zero between launches
+    int cu_count = 256;            // (the device's, once uocr_ctx_create could ask it)
+    int opt_mfma = 1;        // 0 = never, 1 = auto (default), 2 = whenever eligible (tests)
+    int opt_fast = 1;        // 0 = generic kernels only, 1 = shape-specialised fast paths (default)
+    int opt_tiled = 1;       // 0 = no LDS-tiled conv kernels, 1 = use them where instantiated (default)
+    int opt_split = 1024;    // MFMA GEMMs split their depth until there are about this many blocks (0 = never)
+    int opt_split_min = 3;   // ... but only when that takes at least this many slabs (a 2-way split rarely pays its reduce)
+    int opt_xcd = 1;         // 1 = MFMA GEMM blocks are renumbered so that neighbours share an XCD (L2)
+    int opt_bm = 0;          // 0 = choose the MFMA GEMM row tile automatically, 64 / 128 = force it (experiments)
+    int opt_h16 = 1;         // 1 = binary16-MFMA kernels for the small-channel convs in UOCR_F16 mode (default)
+    int opt_t32 = 2;         // float32 vertical-Toeplitz MFMA kernels for the small-channel convs: bit 0 forward, bit 1 backward-data
+                             // (2 was measured: only the 4-channel backward-data beats its vector kernel in the step; conv_t32.hip,
+                             // conv_t32w.hip: bits 64 / 128 = the float32-MFMA weight gradients, 37.0 -> 36.1 k images/s with both)
+    int opt_pair_band = 0;   // rows per band of the strip kernels (0 = about one block per CU)
+    int opt_pair_pf = -1;    // row prefetch of the pair forward kernels (-1 auto / 0 / 1 / 2, see conv_pair_strip.hip)
+                             // (auto: float32 one step ahead (49.5 us; 50.8 pinned in the loop, 51.8 three ahead), binary16 three (72.1;
+                             // 73.8 / 75.5))
+    int opt_h3 = 0;          // 1 = the float32 Line output conv forward on error-compensated binary16 MFMAs (conv_h3.hip; experiment)
+    int opt_group_blocks = 0; // blocks of a deferred weight-gradient group (0 = four per CU)
+    int opt_wgrad_bands = 0;  // row bands per tap / channel group of the direct weight-gradient kernels (0 = by accumulator count)
+    int opt_pair_g = 4;      // groups of 16 columns per wave of the strip kernels: 4 (8 waves per block) or 2 (16 waves)
+    int opt_act_dispatch = 1; // 1 = activation / mask kinds the nets use are compile-time tags of the kernel (default), 0 = the run-time switch
+    int opt_max_blocks = 0;  // k > 0 lowers every run-time block budget to k (tests: several tiles per block at small shapes)
+    long long report[UOCR_REPORT_COUNT][UOCR_REPORT_VALUES] = {};   // uocr_note writes, uocr_report_read reads
+    char err[512] = {};
 };
 
 constexpr int UOCR_SYNC_WORDS = 1 << 18;   // 1 MB
@@ -98,6 +115,24 @@ constexpr int UOCR_T32_BUILT = 2;
     do {                    \
         if (!(ctx)) return UOCR_ERR_ARG; \
     } while (0)
+
+// the one writer and the one reader of ctx->report (the recipe is above uocr_report_id)
+template <typename... V>
+static inline void uocr_note(uocr_ctx* ctx, uocr_report_id id, V... v) {
+    static_assert(sizeof...(V) >= 1 && sizeof...(V) <= UOCR_REPORT_VALUES, "a report holds 1 to UOCR_REPORT_VALUES values");
+    long long* slot = ctx->report[id];
+    ((*slot++ = (long long)v), ...);
+}
+// a null out pointer is an error before anything is written; every value is cast to the type its pointer points to
+template <typename... T>
+static inline int uocr_report_read(uocr_ctx* ctx, uocr_report_id id, T*... out) {
+    static_assert(sizeof...(T) >= 1 && sizeof...(T) <= UOCR_REPORT_VALUES, "a report holds 1 to UOCR_REPORT_VALUES values");
+    UOCR_CHECK_CTX(ctx);
+    if (!(out && ...)) UOCR_FAIL(ctx, UOCR_ERR_ARG, "bad argument: null out pointer of launch report %d", (int)id);
+    const long long* slot = ctx->report[id];
+    ((*out = (T)*slot++), ...);
+    return UOCR_OK;
+}
 
 // dtype dispatch: BODY sees the type alias T
 #define UOCR_DISPATCH(ctx, dtype, ...)                                   \
@@ -155,8 +190,7 @@ static inline long uocr_budget(const uocr_ctx* ctx, long budget) {
     return ctx->opt_max_blocks > 0 && ctx->opt_max_blocks < budget ? ctx->opt_max_blocks : budget;
 }
 static inline void uocr_note_split(uocr_ctx* ctx, long long blocks, long long items) {
-    ctx->split_blocks = (int)blocks;
-    ctx->split_items = items;
+    uocr_note(ctx, UOCR_REPORT_SPLIT, blocks, items);
 }
 
 // blocks of `kernel` (`threads` threads, no dynamic LDS) that one CU holds, asked once per `cache` (the caller's static
@@ -196,14 +230,13 @@ static inline int uocr_tiles_per_block(int tiles_x, int tiles_y, int n, long bud
 // what a pair launch chose (uocr_ctx_last_pair; kernel 1-5 as in univer_hip.h), noted once the launch was accepted
 static inline void uocr_note_pair(uocr_ctx* ctx, int kernel, int g, int mode, int pf, int nw, int blocks_x, int bands,
                                   int band_h) {
-    ctx->pair_kernel = kernel, ctx->pair_g = g, ctx->pair_mode = mode, ctx->pair_pf = pf;
-    ctx->pair_nw = nw, ctx->pair_blocks_x = blocks_x, ctx->pair_bands = bands, ctx->pair_band_h = band_h;
+    uocr_note(ctx, UOCR_REPORT_PAIR, kernel, g, mode, pf, nw, blocks_x, bands, band_h);
 }
 
 // which kernel family took a uocr_conv2d_* call (uocr_ctx_last_conv; entry 0 fwd / 1 bwd_data / 2 bwd_weight, kernel =
 // UOCR_CONV_* of univer_hip.h), noted once the call was accepted: uocr_noted_conv passes a launcher's code through
 static inline void uocr_note_conv(uocr_ctx* ctx, int entry, int kernel) {
-    ctx->conv_entry = entry, ctx->conv_kernel = kernel;
+    uocr_note(ctx, UOCR_REPORT_CONV, entry, kernel);
 }
 static inline int uocr_noted_conv(uocr_ctx* ctx, int entry, int kernel, int rc) {
     if (rc == UOCR_OK) uocr_note_conv(ctx, entry, kernel);

@@ -12,6 +12,7 @@ op raises `HipError` when no MI355X is present.  Without a GPU, DeviceArrays can
 (storage-only, on the host) so that model construction, weight I/O and the data-parallel
 bucketing logic are testable; any kernel call then fails loudly.
 """
+import ctypes as C
 import os
 
 import numpy as np
@@ -48,7 +49,6 @@ class Runtime:
         torch.cuda.set_device(self.device)
         self.stream = torch.cuda.Stream(device=self.device)
         torch.cuda.set_stream(self.stream)
-        import ctypes as C
         handle = C.c_void_p()
         ws = int(os.environ.get('UOCR_WORKSPACE_MB', '256')) << 20
         rc = self.lib.uocr_ctx_create(device_index, ws, C.byref(handle))
@@ -70,7 +70,6 @@ class Runtime:
         nets run under the bandwidth-bound kernels of the large ones.
         xcds: an iterable of XCD numbers (0..7) -- the lane's stream is created by the library on those XCDs only
         (uocr_ctx_create_cu_mask); torch merely wraps it (ExternalStream) for its allocator's bookkeeping."""
-        import ctypes as C
         handle = C.c_void_p()
         if xcds is not None:
             cus = self.device_info()['cu_count']
@@ -114,7 +113,6 @@ class Runtime:
 
     def use_stream(self, torch_stream):
         """Route kernels to another torch stream (used while capturing a HIP graph)."""
-        import ctypes as C
         self.call('uocr_ctx_set_stream', C.c_void_p(torch_stream.cuda_stream))
 
     def set_option(self, key, value):
@@ -130,111 +128,79 @@ class Runtime:
         self._options = getattr(self, '_options', {})
         self._options[key] = int(value)              # (replayed on contexts made later: side streams)
 
+    def _report(self, symbol):
+        """The values of the launch report `symbol` (a uocr_ctx_last_* getter) on the current lane: one out parameter per
+        POINTER(T) that its prototype in hip.lib declares after the context."""
+        outs = [pointer._type_() for pointer in hiplib._PROTOS[symbol][1:]]
+        self.call(symbol, *[C.byref(out) for out in outs])
+        return tuple(out.value for out in outs)
+
     def last_split(self):
         """(blocks, work items) of the most recent launch on the current lane whose split was decided at run time
         (persistent tile walks, rows or tiles per block: the launches the 'max_blocks' option lowers)."""
-        import ctypes as C
-        blocks, items = C.c_int(), C.c_longlong()
-        self.call('uocr_ctx_last_split', C.byref(blocks), C.byref(items))
-        return blocks.value, items.value
+        return self._report('uocr_ctx_last_split')
 
     def last_gemm(self):
         """(row tile, row tiles, column tiles, depth slabs) of the most recent float32 MFMA GEMM on the current lane
         (uocr_ctx_last_gemm); a deferred weight-gradient group flush reports (64, 0, 0, its largest split)."""
-        import ctypes as C
-        v = [C.c_int() for _ in range(4)]
-        self.call('uocr_ctx_last_gemm', *[C.byref(x) for x in v])
-        return tuple(x.value for x in v)
+        return self._report('uocr_ctx_last_gemm')
 
     def last_gemm_group(self):
         """(problems, split problems) of the most recent deferred weight-gradient group flush on the current lane."""
-        import ctypes as C
-        problems, split = C.c_int(), C.c_int()
-        self.call('uocr_ctx_last_gemm_group', C.byref(problems), C.byref(split))
-        return problems.value, split.value
+        return self._report('uocr_ctx_last_gemm_group')
 
     def last_pair(self):
         """(kernel, g, mode, pf, waves per block, blocks_x, bands, band_h) of the most recent Monochrome pair launch
         accepted on the current lane (uocr_ctx_last_pair): kernel 1 / 2 = float32 forward / backward, 3 = binary16
         forward, 4 / 5 = binary16 backward as one cooperative block / on independent waves; all 0 before the first."""
-        import ctypes as C
-        v = [C.c_int() for _ in range(8)]
-        self.call('uocr_ctx_last_pair', *[C.byref(x) for x in v])
-        return tuple(x.value for x in v)
+        return self._report('uocr_ctx_last_pair')
 
     def last_conv(self):
         """(entry, kernel) of the most recent uocr_conv2d_* call accepted on the current lane (uocr_ctx_last_conv): entry
         0 / 1 / 2 = forward / backward-data / backward-weight, kernel = a UOCR_CONV_* value (hip.lib.CONV_KERNELS names
         them); (0, 0) before the first."""
-        import ctypes as C
-        entry, kernel = C.c_int(), C.c_int()
-        self.call('uocr_ctx_last_conv', C.byref(entry), C.byref(kernel))
-        return entry.value, kernel.value
+        return self._report('uocr_ctx_last_conv')
 
     def last_label(self):
         """(tile rows, tile columns, kernel launches) of the most recent uocr_label_components call on the current lane
         (uocr_ctx_last_label); all 0 before the first."""
-        import ctypes as C
-        v = [C.c_int() for _ in range(3)]
-        self.call('uocr_ctx_last_label', *[C.byref(x) for x in v])
-        return tuple(x.value for x in v)
+        return self._report('uocr_ctx_last_label')
 
     def last_label_batch(self):
         """(tile rows, tile columns, entries per launch group, kernel launches) of the most recent uocr_label_batch call
         on the current lane (uocr_ctx_last_label_batch); all 0 before the first."""
-        import ctypes as C
-        v = [C.c_int() for _ in range(4)]
-        self.call('uocr_ctx_last_label_batch', *[C.byref(x) for x in v])
-        return tuple(x.value for x in v)
+        return self._report('uocr_ctx_last_label_batch')
 
     def last_char_label(self):
         """(columns per vote block, elements per statistics chunk, lines per launch, kernel launches) of the most recent
         uocr_char_label call on the current lane (uocr_ctx_last_char_label); all 0 before the first."""
-        import ctypes as C
-        v = [C.c_int() for _ in range(4)]
-        self.call('uocr_ctx_last_char_label', *[C.byref(x) for x in v])
-        return tuple(x.value for x in v)
+        return self._report('uocr_ctx_last_char_label')
 
     def last_line_crop(self):
         """(output elements per block, bytes per vector store, entries per launch, kernel launches) of the most recent
         uocr_line_crop call on the current lane (uocr_ctx_last_line_crop); all 0 before the first."""
-        import ctypes as C
-        v = [C.c_int() for _ in range(4)]
-        self.call('uocr_ctx_last_line_crop', *[C.byref(x) for x in v])
-        return tuple(x.value for x in v)
+        return self._report('uocr_ctx_last_line_crop')
 
     def last_rotate(self):
         """(output rows per block of a probe, output pixels per block of an entry, probes / entries per launch, kernel
         launches) of the most recent uocr_rotated_extent or uocr_rotate_crop call on the current lane
         (uocr_ctx_last_rotate); all 0 before the first."""
-        import ctypes as C
-        v = [C.c_int() for _ in range(4)]
-        self.call('uocr_ctx_last_rotate', *[C.byref(x) for x in v])
-        return tuple(x.value for x in v)
+        return self._report('uocr_ctx_last_rotate')
 
     def last_rotation_search(self):
         """(rounds, paragraphs per launch, kernel launches) of the most recent uocr_rotation_search call on the current
         lane (uocr_ctx_last_rotation_search); all 0 before the first."""
-        import ctypes as C
-        v = [C.c_int() for _ in range(3)]
-        self.call('uocr_ctx_last_rotation_search', *[C.byref(x) for x in v])
-        return tuple(x.value for x in v)
+        return self._report('uocr_ctx_last_rotation_search')
 
     def last_pred_to_text(self):
         """(rows of a line per block, lines per launch, kernel launches) of the most recent uocr_pred_to_text call on the
         current lane (uocr_ctx_last_pred_to_text); all 0 before the first."""
-        import ctypes as C
-        v = [C.c_int() for _ in range(3)]
-        self.call('uocr_ctx_last_pred_to_text', *[C.byref(x) for x in v])
-        return tuple(x.value for x in v)
+        return self._report('uocr_ctx_last_pred_to_text')
 
     def last_pack_lines(self):
         """(elements of an entry per block at most, entries per launch, kernel launches) of the most recent uocr_pack_lines
         or uocr_zero_gaps call on the current lane (uocr_ctx_last_pack_lines); all 0 before the first."""
-        import ctypes as C
-        v = [C.c_int() for _ in range(3)]
-        self.call('uocr_ctx_last_pack_lines', *[C.byref(x) for x in v])
-        return tuple(x.value for x in v)
+        return self._report('uocr_ctx_last_pack_lines')
 
     def set_loss_snapshot(self, arena):
         """From now on the fused optimizer tails launched on the CURRENT lane end by copying `arena`'s slots into the next
@@ -301,7 +267,6 @@ class Runtime:
         return _Capture(self, pool)
 
     def device_info(self):
-        import ctypes as C
         name = C.create_string_buffer(256)
         cus, hbm = C.c_int(), C.c_size_t()
         self.call('uocr_device_info', name, 256, C.byref(cus), C.byref(hbm))
@@ -315,7 +280,6 @@ class Event:
     __slots__ = ('rt', 'handle')
 
     def __init__(self, rt):
-        import ctypes as C
         self.rt, self.handle = rt, C.c_void_p()
         if rt.lib.uocr_event_create(C.byref(self.handle)) != 0:
             raise HipError('uocr_event_create failed')
@@ -372,7 +336,6 @@ class _Capture:
         return self.graph
 
     def __exit__(self, exc_type, exc, tb):
-        import ctypes as C
         handle = C.c_void_p()
         try:
             self.rt.join_side()                      # a forked side stream must be back before the capture ends
@@ -466,7 +429,6 @@ class _Side:
     """Side stream of one lane: its own uocr_ctx (stream + workspace)."""
 
     def __init__(self, rt):
-        import ctypes as C
         self.handle = C.c_void_p()
         rc = rt.lib.uocr_ctx_create(rt.device_index, int(os.environ.get('UOCR_SIDE_WORKSPACE_MB', '128')) << 20,
                                     C.byref(self.handle))
