@@ -374,14 +374,13 @@ def workspace_of(CP, nbytes):
     rt = CP.runtime()
     handle = C.c_void_p()
     assert rt.lib.uocr_ctx_create(rt.device_index, nbytes, C.byref(handle)) == 0
-    main = rt.ctx
+    from univer_ocr_amd.nn.gpu import Lane
     try:
-        rt.ctx = handle
-        rt.call('uocr_ctx_set_stream', C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        yield
-        rt.call('uocr_stream_sync')
+        with rt.on(Lane(torch.cuda.current_stream(), handle)):
+            rt.call('uocr_ctx_set_stream', C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            yield
+            rt.call('uocr_stream_sync')
     finally:
-        rt.ctx = main
         rt.lib.uocr_ctx_destroy(handle)
 
 

@@ -518,16 +518,15 @@ def small_workspace(CP, mb=1):
     rt = CP.runtime()
     handle = C.c_void_p()
     assert rt.lib.uocr_ctx_create(rt.device_index, mb << 20, C.byref(handle)) == 0
-    main = rt.ctx
+    from univer_ocr_amd.nn.gpu import Lane
     try:
-        rt.ctx = handle
-        rt.call('uocr_ctx_set_stream', C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        for key, value in (('mfma', 2), ('fast_paths', 0)) + GEMM_DEFAULTS:
-            rt.call('uocr_ctx_set_option', key.encode(), value)
-        yield (mb << 20) // 2
-        rt.call('uocr_stream_sync')
+        with rt.on(Lane(torch.cuda.current_stream(), handle)):
+            rt.call('uocr_ctx_set_stream', C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            for key, value in (('mfma', 2), ('fast_paths', 0)) + GEMM_DEFAULTS:
+                rt.call('uocr_ctx_set_option', key.encode(), value)
+            yield (mb << 20) // 2
+            rt.call('uocr_stream_sync')
     finally:
-        rt.ctx = main
         rt.lib.uocr_ctx_destroy(handle)
 
 

@@ -35,7 +35,7 @@ launch = rt.lib.uocr_graph_launch
 jobs = {}          # lane -> [(ctx, [handles])]
 for comp in trainer._lane_order():
     e = trainer._captured[comp.name]
-    ctx = rt._lanes[trainer.lanes[comp.name]][0]
+    ctx = rt.lanes[trainer.lanes[comp.name]].handle
     handles = [g.handle for g in e.begin] + [e.finish.handle]
     jobs.setdefault(trainer.lanes[comp.name], []).append((comp.name, ctx, handles))
 # (1) host time per launch, one thread

@@ -3,7 +3,7 @@
 Mirrors the reference's backend switch `CP` (web_app/components/nn/gpu.py:5-29): `CP.cp`,
 `CP.is_gpu_used`, `CP.use_gpu()`, `CP.copy(obj)` (host -> device), `CP.asnumpy(obj)` (device ->
 host).  Where the reference binds `CP.cp` to CuPy and launches numba.cuda kernels, this backend
-owns a `Runtime` (one HIP context of libuniver_hip.so per process = per GPU) and `DeviceArray`s
+owns a `Runtime` (one per process = per GPU, with one `Lane` per context of libuniver_hip.so) and `DeviceArray`s
 whose memory comes from PyTorch-ROCm's caching allocator (plumbing only: no torch op computes
 anything on the hot path).
 
@@ -12,6 +12,7 @@ op raises `HipError` when no MI355X is present.  Without a GPU, DeviceArrays can
 (storage-only, on the host) so that model construction, weight I/O and the data-parallel
 bucketing logic are testable; any kernel call then fails loudly.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -33,100 +34,152 @@ _CODE = {torch.float32: hiplib.F32, torch.float64: hiplib.F64, torch.float16: hi
 _NP_DT = {v: k for k, v in _TORCH_DT.items()}
 
 
+class Lane:
+    """What belongs to one uocr_ctx of the library: the handle (null until Runtime._open has made the context), the torch
+    stream its kernels go to, its side stream (a Lane of its own, made at the first Runtime.side on this lane) and the
+    arrays held for its open deferred weight-gradient group (None: no group is open).
+    A side Lane also has the events that order it with its lane (`fork_ev`, `join_ev`), the arrays its kernels read
+    (`keep`, held until the join) and `dirty`: kernels have gone to it since the last join."""
+
+    __slots__ = ('handle', 'stream', 'side', 'held', 'fork_ev', 'join_ev', 'keep', 'dirty')
+
+    def __init__(self, stream=None, handle=None):
+        self.handle = C.c_void_p() if handle is None else handle
+        self.stream = stream
+        self.side = self.held = self.fork_ev = self.join_ev = None
+        self.keep, self.dirty = [], False
+
+
+_NO_SCOPE = contextlib.nullcontext()
+
+
 class Runtime:
-    """One HIP context (stream + workspace) of libuniver_hip.so; all kernels of the process go
-    through `call`.  The stream is a dedicated torch stream made current, so torch's allocator,
-    H2D/D2H copies, HIP-graph capture and RCCL collectives are ordered with the kernels."""
+    """The HIP contexts (stream + workspace each) of libuniver_hip.so in this process, one Lane per context; all kernels
+    go through `call`, to the lane that is `current`.  Lane 0 is the main one: its stream is a dedicated torch stream made
+    current, so torch's allocator, H2D/D2H copies, HIP-graph capture and RCCL collectives are ordered with the kernels."""
 
     def __init__(self, device_index=None):
         if not torch.cuda.is_available():
             raise HipError('no HIP device visible: the univer-ocr MI355X backend has no host fallback')
-        self.lib = hiplib.get_lib()
         if device_index is None:
             device_index = int(os.environ.get('LOCAL_RANK', '0')) % max(1, torch.cuda.device_count())
         self.device_index = device_index
         self.device = torch.device('cuda', device_index)
         torch.cuda.set_device(self.device)
-        self.stream = torch.cuda.Stream(device=self.device)
+        self.stream = self._stream()
         torch.cuda.set_stream(self.stream)
-        handle = C.c_void_p()
-        ws = int(os.environ.get('UOCR_WORKSPACE_MB', '256')) << 20
-        rc = self.lib.uocr_ctx_create(device_index, ws, C.byref(handle))
-        if rc != 0:
-            raise HipError(f'uocr_ctx_create(device={device_index}) failed with code {rc}')
-        self.ctx = handle
+        main = Lane(self.stream)
+        self._init_state(hiplib.get_lib(), main)
+        self._open(main, f'main context on device {device_index}', int(os.environ.get('UOCR_WORKSPACE_MB', '256')) << 20)
+
+    def _init_state(self, lib, main):
+        """Everything but the device: `main` becomes lane 0 and the current one (its context need not exist yet)."""
+        self.lib = lib
         self._fn = {}
         self.launches = 0
-        self.call('uocr_ctx_set_stream', C.c_void_p(self.stream.cuda_stream))
-        self._lanes = [(self.ctx, self.stream)]      # lane 0 = the main stream
-        self._sides = {}                             # lane ctx -> its side stream (weight gradients), made on demand
-        self._deferred = {}                          # lane ctx -> arrays held for its open deferred weight-gradient group
+        self.lanes = [main]                          # lane 0 = the main stream
+        self.current = main                          # the Lane `call` sends to; switched by `on` and by nothing else
         self.side_on = False                         # Model.backward turns it on for models with side_wgrad
+        self.comm_lane = None                        # index of the communication lane (parallel.py), made on demand
+        self._options = {}                           # what set_option has set, replayed on side streams made later
+
+    @property
+    def ctx(self):
+        """The handle of the current lane (read only: `on` switches lanes)."""
+        return self.current.handle
+
+    def _stream(self, priority=0, external=None):
+        """A new torch stream, or torch's wrapper of the stream `external` that the library made."""
+        if external is not None:
+            return torch.cuda.ExternalStream(external, device=self.device)
+        return torch.cuda.Stream(device=self.device, priority=priority)   # -1 = high
+
+    def _open(self, lane, what, workspace, cu_mask=None, options=False):
+        """Make `lane`'s context, with `workspace` bytes: on its torch stream, or with cu_mask (words of CU bits) on a
+        stream that the library creates on those CUs and torch merely wraps for its allocator's bookkeeping.  options:
+        replay what set_option has set so far.  A context whose set-up fails is destroyed again."""
+        if cu_mask is None:
+            rc = self.lib.uocr_ctx_create(self.device_index, workspace, C.byref(lane.handle))
+        else:
+            rc = self.lib.uocr_ctx_create_cu_mask(self.device_index, workspace, cu_mask, len(cu_mask), C.byref(lane.handle))
+        if rc != 0:
+            raise HipError(f'uocr_ctx_create ({what}) failed with code {rc}')
+        try:
+            if cu_mask is not None:
+                lane.stream = self._stream(external=self.lib.uocr_ctx_get_stream(lane.handle))
+            with self.on(lane):
+                if cu_mask is None:
+                    self.call('uocr_ctx_set_stream', C.c_void_p(lane.stream.cuda_stream))
+                for key, value in self._options.items() if options else ():
+                    self.call('uocr_ctx_set_option', key.encode(), value)
+        except BaseException as error:
+            self.lib.uocr_ctx_destroy(lane.handle)
+            lane.handle = C.c_void_p()
+            if isinstance(error, HipError):
+                raise HipError(f'{what}: {error}') from error
+            raise
+        return lane
+
+    @contextlib.contextmanager
+    def on(self, lane):
+        """`with rt.on(lane):` -- `call` sends to `lane` inside and to the lane before it afterwards, however the block
+        ends.  Switches the library's context only, not torch's current stream (`lane` does both)."""
+        previous = self.current
+        self.current = lane
+        try:
+            yield lane
+        finally:
+            self.current = previous
 
     # -- lanes: extra (context, stream) pairs so independent models run concurrently ---------------
     def add_lane(self, workspace_mb=256, priority=0, xcds=None):
-        """A further HIP context of the library with its own stream and workspace.  The four my_model
-        nets are independent, so each trains on its own lane: the latency-bound kernels of the small
+        """A further HIP context of the library with its own stream and workspace; returns its index in `lanes`.  The
+        four my_model nets are independent, so each trains on its own lane: the latency-bound kernels of the small
         nets run under the bandwidth-bound kernels of the large ones.
-        xcds: an iterable of XCD numbers (0..7) -- the lane's stream is created by the library on those XCDs only
-        (uocr_ctx_create_cu_mask); torch merely wraps it (ExternalStream) for its allocator's bookkeeping."""
-        handle = C.c_void_p()
-        if xcds is not None:
+        xcds: an iterable of XCD numbers (0..7) -- the lane's stream is created by the library on those XCDs only.
+        A new lane starts from the library's default options: what set_option set earlier is NOT replayed on it.
+        Lanes are never released: every caller's lanes stay with the process-wide runtime."""
+        if xcds is None:
+            lane = self._open(Lane(self._stream(priority)), 'lane', int(workspace_mb) << 20)
+        else:
             cus = self.device_info()['cu_count']
-            words = (cus + 31) // 32
-            mask = (C.c_uint32 * words)()
+            mask = (C.c_uint32 * ((cus + 31) // 32))()
             for i in range(cus):
                 if i % 8 in set(xcds):
                     mask[i // 32] |= 1 << (i % 32)
-            rc = self.lib.uocr_ctx_create_cu_mask(self.device_index, int(workspace_mb) << 20, mask, words, C.byref(handle))
-            if rc != 0:
-                raise HipError(f'uocr_ctx_create_cu_mask (lane on XCDs {sorted(set(xcds))}) failed with code {rc}')
-            stream = torch.cuda.ExternalStream(self.lib.uocr_ctx_get_stream(handle), device=self.device)
-            self._lanes.append((handle, stream))
-            return len(self._lanes) - 1
-        rc = self.lib.uocr_ctx_create(self.device_index, int(workspace_mb) << 20, C.byref(handle))
-        if rc != 0:
-            raise HipError(f'uocr_ctx_create (lane) failed with code {rc}')
-        stream = torch.cuda.Stream(device=self.device, priority=priority)   # -1 = high
-        main = self.ctx
-        self.ctx = handle
-        self.call('uocr_ctx_set_stream', C.c_void_p(stream.cuda_stream))
-        self.ctx = main
-        self._lanes.append((handle, stream))
-        return len(self._lanes) - 1
+            lane = self._open(Lane(), f'lane on XCDs {sorted(set(xcds))}', int(workspace_mb) << 20, cu_mask=mask)
+        self.lanes.append(lane)
+        return len(self.lanes) - 1
 
+    @contextlib.contextmanager
     def lane(self, index):
-        return _Lane(self, index)
-
-    def lane_stream(self, index):
-        return self._lanes[index][1]
+        """`with runtime.lane(i) as stream:` -- kernels, allocations and copies inside go to lane i's stream."""
+        lane, previous = self.lanes[index], torch.cuda.current_stream()
+        with self.on(lane):
+            torch.cuda.set_stream(lane.stream)
+            try:
+                yield lane.stream
+            finally:
+                torch.cuda.set_stream(previous)
 
     def call(self, name, *args):
         fn = self._fn.get(name)
         if fn is None:
             fn = self._fn[name] = getattr(self.lib, name)
-        rc = fn(self.ctx, *args)
+        rc = fn(self.current.handle, *args)
         self.launches += 1
         if rc != 0:
-            msg = self.lib.uocr_last_error(self.ctx)
+            msg = self.lib.uocr_last_error(self.current.handle)
             raise HipError(f'{name} failed ({rc}): {msg.decode() if msg else "?"}')
-
-    def use_stream(self, torch_stream):
-        """Route kernels to another torch stream (used while capturing a HIP graph)."""
-        self.call('uocr_ctx_set_stream', C.c_void_p(torch_stream.cuda_stream))
 
     def set_option(self, key, value):
         """Kernel selection knobs of the C ABI: 'mfma' (0 never / 1 auto / 2 whenever eligible),
-        'fast_paths' (0 generic kernels only / 1 shape-specialised).  Applied to every lane."""
-        current = self.ctx
-        try:
-            for handle in [h for h, _ in self._lanes] + [s.handle for s in self._sides.values()]:
-                self.ctx = handle
+        'fast_paths' (0 generic kernels only / 1 shape-specialised).  Applied to every lane, then to every side stream
+        there is; recorded (for the side streams made later) once all of them have accepted it."""
+        for lane in self.lanes + [lane.side for lane in self.lanes if lane.side is not None]:
+            with self.on(lane):
                 self.call('uocr_ctx_set_option', key.encode(), int(value))
-        finally:
-            self.ctx = current
-        self._options = getattr(self, '_options', {})
-        self._options[key] = int(value)              # (replayed on contexts made later: side streams)
+        self._options[key] = int(value)
 
     def _report(self, symbol):
         """The values of the launch report `symbol` (a uocr_ctx_last_* getter) on the current lane: one out parameter per
@@ -212,21 +265,39 @@ class Runtime:
                       arena.counter.ptr)
 
     # -- deferred weight gradients (uocr_wgrad_defer_begin / _flush): one launch for the small GEMMs of a backward pass --
+    @contextlib.contextmanager
     def defer_wgrad(self):
         """`with rt.defer_wgrad():` -- the weight-gradient GEMMs issued inside on the current lane that are too small
         to fill the chip are recorded by the library and run as ONE grid (+ one reduction) at the end of the block, or
         earlier at `flush_deferred()`.  The arrays they read are held until then (`keep`)."""
-        return _DeferScope(self)
+        lane = self.current
+        if lane.held is not None:
+            raise HipError('defer_wgrad: a deferred group is already open on this lane')
+        self.call('uocr_wgrad_defer_begin')
+        lane.held = held = []
+        failed = True
+        try:
+            yield
+            failed = False
+        finally:
+            lane.held = None
+            try:
+                self.call('uocr_wgrad_defer_flush', 0)
+            except HipError:
+                if not failed:
+                    raise
+            finally:
+                held.clear()
 
     def keep(self, *arrays):
         """Hold `arrays` until the deferred weight gradients of the current lane have been flushed (no-op otherwise)."""
-        held = self._deferred.get(self.ctx.value)
+        held = self.current.held
         if held is not None:
             held.extend(arrays)
 
     def flush_deferred(self):
         """Run what has been recorded on the current lane now and keep recording (a gradient bucket is due)."""
-        held = self._deferred.get(self.ctx.value)
+        held = self.current.held
         if held is not None:
             self.call('uocr_wgrad_defer_flush', 1)
             held.clear()
@@ -237,17 +308,31 @@ class Runtime:
         everything enqueued on the lane so far (device-side event); the lane does not wait for them until
         `join_side()`.  `keep`: the arrays the side kernels read -- held until the join so that the allocator cannot
         hand their memory to a later kernel of the lane.  No-op (the calls stay on the lane) unless `side_on`."""
-        return _SideScope(self, keep)
+        return self._fork_side(keep) if self.side_on else _NO_SCOPE
+
+    @contextlib.contextmanager
+    def _fork_side(self, keep):
+        lane = self.current
+        if lane.side is None:                        # its own uocr_ctx (stream + workspace), made at the first use
+            side = Lane(self._stream())
+            side.fork_ev, side.join_ev = Event(self), Event(self)
+            lane.side = self._open(side, 'side stream', int(os.environ.get('UOCR_SIDE_WORKSPACE_MB', '128')) << 20,
+                                   options=True)
+        side = lane.side
+        side.fork_ev.record()                        # on the lane
+        with self.on(side):
+            side.fork_ev.wait()                      # the side stream waits for the lane up to here
+            side.keep.extend(keep)
+            side.dirty = True
+            yield
 
     def join_side(self):
         """The current lane waits (on the device) for its side stream."""
-        side = self._sides.get(self.ctx.value)
+        side = self.current.side
         if side is None or not side.dirty:
             return
-        lane = self.ctx
-        self.ctx = side.handle
-        side.join_ev.record()
-        self.ctx = lane
+        with self.on(side):
+            side.join_ev.record()
         side.join_ev.wait()
         side.dirty = False
         side.keep.clear()
@@ -400,92 +485,6 @@ class LossArena:
         k = self.rows % self.ring_len
         self.rows += 1
         return DeviceArray(self.ring.t[k * capacity:(k + 1) * capacity])
-
-
-class _DeferScope:
-    def __init__(self, rt):
-        self.rt = rt
-
-    def __enter__(self):
-        self.key = self.rt.ctx.value
-        if self.key in self.rt._deferred:
-            raise HipError('defer_wgrad: a deferred group is already open on this lane')
-        self.rt.call('uocr_wgrad_defer_begin')
-        self.rt._deferred[self.key] = []
-
-    def __exit__(self, exc_type, exc, tb):
-        held = self.rt._deferred.pop(self.key)
-        try:
-            self.rt.call('uocr_wgrad_defer_flush', 0)
-        except HipError:
-            if exc_type is None:
-                raise
-        finally:
-            held.clear()
-        return False
-
-
-class _Side:
-    """Side stream of one lane: its own uocr_ctx (stream + workspace)."""
-
-    def __init__(self, rt):
-        self.handle = C.c_void_p()
-        rc = rt.lib.uocr_ctx_create(rt.device_index, int(os.environ.get('UOCR_SIDE_WORKSPACE_MB', '128')) << 20,
-                                    C.byref(self.handle))
-        if rc != 0:
-            raise HipError(f'uocr_ctx_create (side stream) failed with code {rc}')
-        self.stream = torch.cuda.Stream(device=rt.device)
-        lane = rt.ctx
-        rt.ctx = self.handle
-        rt.call('uocr_ctx_set_stream', C.c_void_p(self.stream.cuda_stream))
-        for key, value in getattr(rt, '_options', {}).items():
-            rt.call('uocr_ctx_set_option', key.encode(), value)
-        rt.ctx = lane
-        self.fork_ev, self.join_ev = Event(rt), Event(rt)
-        self.keep, self.dirty = [], False
-
-
-class _SideScope:
-    def __init__(self, rt, keep):
-        self.rt, self.keep = rt, keep
-
-    def __enter__(self):
-        rt = self.rt
-        self.lane = None
-        if not rt.side_on:
-            return
-        side = rt._sides.get(rt.ctx.value)
-        if side is None:
-            side = rt._sides[rt.ctx.value] = _Side(rt)
-        side.fork_ev.record()                      # on the lane
-        self.lane = rt.ctx
-        rt.ctx = side.handle
-        side.fork_ev.wait()                        # the side stream waits for the lane up to here
-        side.keep.extend(self.keep)
-        side.dirty = True
-
-    def __exit__(self, *exc):
-        if self.lane is not None:
-            self.rt.ctx = self.lane
-        return False
-
-
-class _Lane:
-    """`with runtime.lane(i):` -- kernels, allocations and copies inside go to lane i's stream."""
-
-    def __init__(self, rt, index):
-        self.rt, self.index = rt, index
-
-    def __enter__(self):
-        self.prev_ctx, self.prev_stream = self.rt.ctx, torch.cuda.current_stream()
-        self.rt.ctx, stream = self.rt._lanes[self.index]
-        torch.cuda.set_stream(stream)
-        return stream
-
-    def __exit__(self, *exc):
-        self.rt.ctx = self.prev_ctx
-        torch.cuda.set_stream(self.prev_stream)
-        return False
 
 
 class DeviceArray:

@@ -82,9 +82,9 @@ class _Rccl:
             self.rank, self.world, raw = 0, 1, ident.raw          # a ONE-rank communicator (rehearsal)
         # one communication lane per process, reused by every communicator made later (train.py builds a DataParallel per
         # stage: a lane per stage would leak a context, a stream and a workspace each time)
-        if getattr(rt, '_comm_lane', None) is None:
-            rt._comm_lane = rt.add_lane(workspace_mb=1)
-        self.lane = rt._comm_lane
+        if rt.comm_lane is None:
+            rt.comm_lane = rt.add_lane(workspace_mb=1)
+        self.lane = rt.comm_lane
         with rt.lane(self.lane):
             rt.call('uocr_dp_init', self.rank, self.world, C.c_char_p(raw))
             try:
