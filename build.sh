@@ -25,3 +25,7 @@ done
 for p in "${pids[@]:-}"; do [[ -n "$p" ]] && wait "$p"; done
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$OBJ"/*.o
 echo "built $OUT"
+# the glyph atlas of the page generator: the package reads its own copy; the committed bytes lie where the repository keeps
+# binary data, the licence of the fonts they were drawn from beside them
+cp "$ROOT/tests/golden/glyphs.npz" "$ROOT/tests/golden/glyphs.LICENSE.txt" "$ROOT/univer-ocr_amd/my_model/"
+echo "installed $ROOT/univer-ocr_amd/my_model/glyphs.npz"

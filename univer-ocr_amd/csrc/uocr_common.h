@@ -31,6 +31,7 @@ enum uocr_report_id {
     UOCR_REPORT_ROTATION_SEARCH,  // rounds, paragraphs per launch and launch count of the last search
     UOCR_REPORT_PRED_TO_TEXT,     // sizes and launch count of the last pred-to-text call
     UOCR_REPORT_PACK_LINES,       // sizes and launch count of the last pack-lines or zero-gaps call
+    UOCR_REPORT_PAGE_GEN,         // tile, pages per launch and launch count of the last page-layout or page-render call
     UOCR_REPORT_COUNT
 };
 constexpr int UOCR_REPORT_VALUES = 8;   // the most values of one report (pair); 64-bit for the item count of split

@@ -5,7 +5,10 @@ from and saving to `model_weights.json` (flat {"<layer name>": {"<param>": neste
 compact separators, train.py:132-141).  The reference's stages that chain nets through the host
 crop/rotate code (TRAIN_LINE / TRAIN_CHAR / TRAIN_ALL) are replaced by TRAIN_PAGE, which trains all
 four nets on device-resident page and line-strip batches.  Data: seeded synthetic pages
-(my_model/synthetic.py); the reference's generate_data needs Windows fonts and stays outside."""
+(my_model/synthetic.py) by default.  data='generated' (or UOCR_TRAIN_DATA=generated) takes pages made on the device
+instead (my_model/pages.py: random text in the atlas fonts with every label layer, the device form of the reference's
+generate_data) and, in place of TRAIN_PAGE, runs the reference's own TRAIN_LINE and TRAIN_CHAR stages page by page
+through the device crop stages, so that the Char net sees glyphs with their true labels."""
 import json
 import os
 from pathlib import Path
@@ -13,7 +16,8 @@ from pathlib import Path
 from ..nn.gpu import CP
 from ..nn.optimizers import Adam
 from ..nn.progress_tracker import ProgressTracker
-from .model import Modes, make_context_maker, make_model_system
+from .model import (CHAR_INPUT_HEIGHT, Modes, make_context_maker, make_model_system, make_train_char_context_maker,
+                    make_train_char_system)
 from .synthetic import SyntheticPages
 from .trainer import Trainer
 
@@ -56,7 +60,10 @@ def _init_data_parallel():
 
 
 def train_model(use_gpu=True, show_progress_bar=False, save_train_progress=False, epochs_scale=None,
-                batch=1, height=None, width=None, dp_backend=None):
+                batch=1, height=None, width=None, dp_backend=None, data=None):
+    data = data or os.environ.get('UOCR_TRAIN_DATA', 'synthetic')
+    if data not in ('synthetic', 'generated'):
+        raise ValueError(f"train_model: data must be 'synthetic' or 'generated', got {data!r}")
     if not use_gpu:
         CP.use_cpu()          # raises: the NumPy path is the reference itself
     rank, world, local_rank = _init_data_parallel()
@@ -74,8 +81,16 @@ def train_model(use_gpu=True, show_progress_bar=False, save_train_progress=False
     stages = [(Modes.TRAIN_MONOCHROME, 0.0015, 0.995, 100), (Modes.TRAIN_PARAGRAPH, 0.0015, 0.995, 100),
               (Modes.TRAIN_PAGE, 0.001, 0.9, 10)]
     # data parallel: every rank trains on its own pages (the batch is sharded by rank: seeds differ)
-    train_set = SyntheticPages(batch, height, width, seed=1234 + 1000 * rank, length=4)
-    val_set = SyntheticPages(batch, height, width, seed=9999 + 1000 * rank, length=2)
+    if data == 'generated':
+        from .pages import GeneratedPages, PagesWithText
+        stages[2:] = [(Modes.TRAIN_LINE, 0.001, 0.9, 10), (Modes.TRAIN_CHAR, 0.001, 0.9, 10)]
+        train_set = GeneratedPages(batch, height, width, seed=1234 + 1000 * rank, length=4)
+        val_set = GeneratedPages(batch, height, width, seed=9999 + 1000 * rank, length=2)
+        # the stages that crop paragraphs and lines take one page at a time, and only pages that hold a line
+        train_pages, val_pages = PagesWithText(train_set, 4 * batch), PagesWithText(val_set, 2 * batch)
+    else:
+        train_set = SyntheticPages(batch, height, width, seed=1234 + 1000 * rank, length=4)
+        val_set = SyntheticPages(batch, height, width, seed=9999 + 1000 * rank, length=2)
     results = {}
     watchdog = None
     for mode, lr, lr_step, epochs in stages:
@@ -83,9 +98,15 @@ def train_model(use_gpu=True, show_progress_bar=False, save_train_progress=False
         message(f'Training mode: {mode.name}')
         weights = load_weights()
         optimizer = Adam(lr=lr)
-        input_shape = (batch, height, width, 1)
-        model_system, models, names = make_model_system(input_shape, optimizer, tracker, weights, mode=mode,
-                                                        char_input_shape=(batch, 32, 64, 1))
+        paged = mode in (Modes.TRAIN_LINE, Modes.TRAIN_CHAR)
+        input_shape = (1 if paged else batch, height, width, 1)
+        if mode is Modes.TRAIN_CHAR:
+            model_system, models, names = make_train_char_system((1, CHAR_INPUT_HEIGHT, 64, 1), optimizer, tracker, weights)
+            context_maker = make_train_char_context_maker()
+        else:
+            model_system, models, names = make_model_system(input_shape, optimizer, tracker, weights, mode=mode,
+                                                            char_input_shape=(batch, 32, 64, 1))
+            context_maker = make_context_maker(mode)
         message(f'Input shape: {input_shape}; parameters: {sum(m.count_parameters() for m in models.values())}')
 
         def save_weights(better, models=models):
@@ -110,8 +131,8 @@ def train_model(use_gpu=True, show_progress_bar=False, save_train_progress=False
                 watchdog = Watchdog(float(os.environ.get('UOCR_STEP_TIMEOUT', '600')), rank, 'train watchdog')
             # rank 0's weights everywhere; UOCR_DP_BACKEND=gloo: several ranks on one card (rehearsal)
             dp = DataParallel(models, overlap=False, backend=dp_backend or os.environ.get('UOCR_DP_BACKEND'))
-        trainer = Trainer(model_system, make_context_maker(mode), models, train_set, val_set, tracker,
-                          show_progress_bar, optimizer, lr_step, save_weights, data_parallel=dp, watchdog=watchdog)
+        trainer = Trainer(model_system, context_maker, models, *((train_pages, val_pages) if paged else (train_set, val_set)),
+                          tracker, show_progress_bar, optimizer, lr_step, save_weights, data_parallel=dp, watchdog=watchdog)
         results[mode.name] = trainer.train(epochs)
         if dp is not None:
             dp.close()

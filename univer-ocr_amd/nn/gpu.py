@@ -184,7 +184,8 @@ class Runtime:
     def _report(self, symbol):
         """The values of the launch report `symbol` (a uocr_ctx_last_* getter) on the current lane: one out parameter per
         POINTER(T) that its prototype in hip.lib declares after the context."""
-        outs = [pointer._type_() for pointer in hiplib._PROTOS[symbol][1:]]
+        protos = hiplib._PROTOS[symbol] if symbol in hiplib._PROTOS else hiplib._SPECIAL[symbol][1]
+        outs = [pointer._type_() for pointer in protos[1:]]
         self.call(symbol, *[C.byref(out) for out in outs])
         return tuple(out.value for out in outs)
 
@@ -254,6 +255,11 @@ class Runtime:
         """(elements of an entry per block at most, entries per launch, kernel launches) of the most recent uocr_pack_lines
         or uocr_zero_gaps call on the current lane (uocr_ctx_last_pack_lines); all 0 before the first."""
         return self._report('uocr_ctx_last_pack_lines')
+
+    def last_page_gen(self):
+        """(tile rows, tile columns, pages per launch, kernel launches) of the most recent uocr_page_layout or
+        uocr_page_render call on the current lane (uocr_ctx_last_page_gen); all 0 before the first."""
+        return self._report('uocr_ctx_last_page_gen')
 
     def set_loss_snapshot(self, arena):
         """From now on the fused optimizer tails launched on the CURRENT lane end by copying `arena`'s slots into the next

@@ -1069,6 +1069,63 @@ def zero_gaps(x, segments):
     return x
 
 
+# ---- training pages made on the device (image_generator/generate.py: add_paragraph) ---------------
+PAGE_TABLES = (('paragraphs', 32, 8), ('lines', 32 * 30, 5), ('glyphs', 32 * 30 * 11, 2))    # name, rows per page, ints per row
+PAGE_LAYERS = (('image', 1), ('monochrome', 1), ('paragraph', 1), ('line', 2), ('char', 9))  # name, channels
+
+
+def _atlas_arrays(atlas, who):
+    """(metrics, adv, offset, cells) of an atlas: int32 (F, 7), (F, 162), (F, 162) and uint8 (n,) DeviceArrays"""
+    arrays = [atlas[key] for key in ('metrics', 'adv', 'offset', 'cells')]
+    faces = arrays[0].shape[0] if isinstance(arrays[0], DeviceArray) and arrays[0].ndim == 2 else 0
+    wanted = (((faces, 7), np.int32), ((faces, 162), np.int32), ((faces, 162), np.int32), (arrays[3].shape[:1], np.uint8))
+    for a, (shape, dtype) in zip(arrays, wanted):
+        if not isinstance(a, DeviceArray) or faces < 1 or a.shape != shape or a.dtype != dtype:
+            raise ValueError(f'{who}: the atlas holds metrics (F, 7), adv (F, 162), offset (F, 162) int32 and cells (n,) uint8 '
+                             f'device arrays, got {[(getattr(a, "shape", type(a)), getattr(a, "dtype", None)) for a in arrays]}')
+    return arrays
+
+
+def page_layout(atlas, seed, first_page, n_pages, height, width):
+    """The tables of pages first_page .. first_page + n_pages - 1 (Python ints, taken mod 2^64 like the seed) of
+    height x width pixels: {'paragraphs': (n, 32, 8), 'lines': (n, 960, 5), 'glyphs': (n, 10560, 2), 'counts': (n, 4)} int32
+    DeviceArrays; rows past a page's counts hold whatever the allocation held.  ONE uocr_page_layout call (none for no
+    page); nothing is read back."""
+    metrics, adv, _, _ = _atlas_arrays(atlas, 'page_layout')
+    n_pages, height, width = int(n_pages), int(height), int(width)
+    if n_pages < 0 or height < 1 or width < 1:
+        raise ValueError(f'page_layout: {n_pages} pages of {height} x {width}')
+    tables = {name: CP.empty((n_pages, rows, ints), np.int32) for name, rows, ints in PAGE_TABLES}
+    tables['counts'] = CP.empty((n_pages, 4), np.int32)
+    if n_pages:
+        _rt().call('uocr_page_layout', int(seed) % 2 ** 64, int(first_page) % 2 ** 64, n_pages, height, width, metrics.shape[0],
+                   metrics.ptr, adv.ptr, *(tables[name].ptr for name in ('paragraphs', 'lines', 'glyphs', 'counts')))
+    return tables
+
+
+def page_render(atlas, tables, height, width, lut):
+    """The five label layers of the pages in `tables` (the dict page_layout returns, or hand-built tables of the same
+    shapes): {'image', 'monochrome', 'paragraph': (n, H, W, 1), 'line': (n, H, W, 2), 'char': (n, H, W, 9)} DeviceArrays in
+    the dtype of `lut`, the (256,) DeviceArray of np.arange(256) / 255.  ONE uocr_page_render call (none for no page)."""
+    metrics, adv, offset, cells = _atlas_arrays(atlas, 'page_render')
+    height, width = int(height), int(width)
+    n_pages = tables['counts'].shape[0]
+    for name, rows, ints in PAGE_TABLES + (('counts', 4, None),):
+        a, shape = tables[name], (n_pages, rows) + ((ints,) if ints else ())
+        if not isinstance(a, DeviceArray) or a.shape != shape or a.dtype != np.int32:
+            raise ValueError(f'page_render: table {name!r} must be an int32 device array of shape {shape}, got '
+                             f'{getattr(a, "shape", type(a))} {getattr(a, "dtype", "")}')
+    if not isinstance(lut, DeviceArray) or lut.shape != (256,) or height < 1 or width < 1:
+        raise ValueError(f'page_render: lut must be a (256,) device array and the page at least 1 x 1, got '
+                         f'{getattr(lut, "shape", type(lut))}, {height} x {width}')
+    out = {name: CP.empty((n_pages, height, width, c), lut.dtype) for name, c in PAGE_LAYERS}
+    if n_pages:
+        _rt().call('uocr_page_render', lut.code & 0xff, n_pages, height, width,
+                   *(tables[name].ptr for name in ('paragraphs', 'lines', 'glyphs', 'counts')), metrics.shape[0], metrics.ptr,
+                   adv.ptr, offset.ptr, cells.ptr, cells.shape[0], lut.ptr, *(out[name].ptr for name, _ in PAGE_LAYERS))
+    return out
+
+
 class _Ops:
     add = staticmethod(add)
 
