@@ -18,6 +18,13 @@
     GPU test, as every other mutant is;
   * binary16: every stored input and every S lies in the normal range;
   * conv pair backward: at most 1 % of the dx pixels are left unjudged for an undecided LeakyReLU slope.
+
+The Sigmoid cases, the Sigmoid derivative taken from a stored output and the pair's dx with every pixel judged have
+tests of their own below: what their inputs must offer, the float32 restatement within the bound (its largest err /
+tol is printed), and the wrong implementations each bound must reject -- a Sigmoid by tanh with a binary16 argument,
+expf clamped at |v| = 16, y (1 - y) from a y rounded once more to binary16, and for the pair's dx a dropped tap at a
+strip border, a flipped decided slope, d_a1 rounded twice and the mask read one row off.  Where rel_linf accepts a
+mutant that the bound rejects the output says so.
 """
 import numpy as np
 import pytest
@@ -67,6 +74,167 @@ def test_the_table_holds_every_family():
             assert not {'t32', 'tiled'} & set(c.kernels.values()), c
         if c.id.endswith('-h16_0'):
             assert 'h16' not in c.kernels.values() and not c.operand16, c
+
+
+def test_sigmoid_tolerance_terms():
+    u, k = 2.0 ** -24, B.SIGMOID_K
+    v, e = np.array([0.0, -30.0, 30.0, -100.0, 3.0]), np.array([0.0, 0.0, 0.0, 0.0, 1.0])
+    s = 1.0 / (1.0 + np.exp(-v))
+    want = s * ((1.0 - s) * k * u + 2 * u) + 2.0 ** -126
+    want[4] += 1.0 * (1.0 / (1.0 + np.exp(-2.0))) * (1.0 - 1.0 / (1.0 + np.exp(-2.0)))      # E sigma'(|v| - E)
+    assert np.allclose(B.sigmoid_tolerance(v, e), want, rtol=1e-12, atol=0.0)
+    assert B.sigmoid_tolerance(v, e)[3] == pytest.approx(2.0 ** -126, rel=1e-3)              # sigma(-100) = 4e-44
+    assert np.allclose(B.sigmoid_tolerance(v, e, store16=True), want + 2.0 ** -11 * s + 2.0 ** -25, rtol=1e-12, atol=0.0)
+    assert B.sigmoid_tolerance(np.array([0.5]), np.array([2.0]))[0] > 2.0 * 0.25                # the interval holds 0
+    # the float64 Sigmoid keeps its relative accuracy on both sides
+    assert B.sigmoid(np.array([-700.0]))[0] == pytest.approx(np.exp(-700.0), rel=1e-15)
+    assert 1.0 - B.sigmoid(np.array([40.0]))[0] == 0.0 and B.sigmoid(np.array([-40.0]))[0] == pytest.approx(np.exp(-40.0))
+    # the float32 restatement overflows where the kernels' expf does
+    assert B.sigmoid(np.array([-88.73, -88.0], np.float32), np.float32)[0] == 0.0
+    assert B.sigmoid(np.array([-88.73, -88.0], np.float32), np.float32)[1] > 0.0
+
+
+def test_the_sigmoid_table_holds_every_family():
+    ids = set(B.SIGMOID_IDS)
+    assert len(ids) == len(B.SIGMOID_CASES)
+    linear = {c.id for c in B.CASES if not isinstance(c.problem, B.WindowsProblem)}
+    assert ids == {i + '-sigmoid' for i in linear}
+    assert {'32-up4-sigmoid', '32-up1-sigmoid', '32-pair-sigmoid', '16-pair-sigmoid', '32-dense-sigmoid',
+            '32-mfma-mfma2-sigmoid', '32-generic-sigmoid', '16-up4-h16_0-sigmoid'} <= ids
+    by_id = {c.id: c for c in B.CASES}
+    for c in B.SIGMOID_CASES:
+        base = by_id[c.id[:-len('-sigmoid')]]
+        assert c.opts == base.opts and c.outputs == ('y_sigmoid',) and c.problem.base is base.problem
+        assert c.kernels.get('y_sigmoid') == base.kernels.get('y')
+        assert bool(c.operand16) == ('y' in base.operand16)
+
+
+@pytest.mark.parametrize('index', range(len(B.SIGMOID_CASES)), ids=B.SIGMOID_IDS)
+def test_sigmoid_case_inputs_room_and_mutations(index):
+    """The inputs offer what a test of the Sigmoid needs (SigmoidProblem.check_inputs: >= 30 % of the outputs with
+    |v| <= 4, >= 5 % each with v >= 20 and v <= -20, float32: some v < -88.72, binary16: some Sigmoid below the
+    subnormals, regions of order one and saturated ones); the float32 restatement 1 / (1 + exp(-v)) of the float32
+    linear restatement keeps to the bound; the tanh form with a binary16 argument and expf clamped at |v| = 16 do not."""
+    c = B.SIGMOID_CASES[index]
+    p = c.problem
+    p.check_ranges()
+    info = p.check_inputs()
+    name = 'y_sigmoid'
+    ref, tol = p.ref[name], p.tolerances(c.operand16)[name]
+    assert tol.shape == ref.shape and np.all(tol > 0) and np.all((ref >= 0) & (ref <= 1))
+    room = B.worst_ratio(p.restated(store=False)[name], ref, p.tolerances(c.operand16, store=False)[name])
+    stored = B.worst_ratio(p.restated()[name], ref, tol)
+    allow = B.ALLOW[p.dtype]
+    fine = float(np.mean(tol < allow * np.abs(ref).max() / 16))
+    print(f'{c.id}: w x 2^{info["shift"]}, |v| <= 4 on {info["mid"]:.1%}, v >= 20 on {info["high"]:.1%}, v <= -20 on '
+          f'{info["low"]:.1%}, v in [{info["vmin"]:.3g}, {info["vmax"]:.3g}], region medians of |v| {info["median_min"]:.2g} .. '
+          f'{info["median_max"]:.2g}; restatement / tol {room:.3f} (stored {stored:.3f}), tol < allowance / 16 on {fine:.1%}')
+    failures = []
+    if not room <= 1.0:
+        failures.append(f'the float32 restatement reaches {room:.3f} of the bound')
+    if not stored <= 1.0:
+        failures.append(f'the float32 restatement, stored, reaches {stored:.3f} of the bound')
+    exact32 = p.v.astype(np.float32)
+    for what, act in (('tanh form with a binary16 argument', B.sigmoid_by_tanh16), ('expf clamped at |v| = 16', B.sigmoid_clamped)):
+        ratio = B.worst_ratio(p.restated(act=act)[name], ref, tol)
+        own = act(exact32, np.float32).astype(np.float64)       # the mutant on the oracle's v: its own error alone
+        lin = rel_linf(B.r16(own) if p.half else own, ref)
+        print(f'    {what}: {ratio:.3g} of the bound; rel_linf of the mutant alone {lin:.1e}')
+        assert ratio > 1.0, f'{c.id}: the mutation "{what}" passes the bound ({ratio:.3g})' + \
+            (f' -- and rel_linf = {lin:.1e} accepts it' if lin <= allow else '')
+        if lin <= allow:
+            print(f'    rel_linf <= {allow:g} accepts this mutant; the bound rejects it')
+    assert not failures, '\n'.join(failures)
+
+
+def test_the_pair_dx_table():
+    ids = set(B.PAIR_DX_IDS)
+    assert len(ids) == len(B.PAIR_DX_CASES)
+    seen = {(c.problem.dtype, c.problem.q['x'].shape[1:3], c.problem.pad1, c.problem.sig) for c in B.PAIR_DX_CASES}
+    for sig in (False, True):
+        assert ('float32', (37, 141), 0.25, sig) in seen                  # the module's float32 pair problem
+        for pad1 in (0.0, 0.25):
+            assert ('float16', (37, 141), pad1, sig) in seen              # the module's shape
+        assert ('float16', (21, 128), 0.0, sig) in seen                   # whole waves, pad1 = 0: MODE 0 of the kernel
+    assert ('float16', (19, 71), 0.25, False) in seen and 71 % 16 and 141 % 16
+    assert B.r16(0.25) == 0.25
+
+
+@pytest.mark.parametrize('index', range(len(B.PAIR_DX_CASES)), ids=B.PAIR_DX_IDS)
+def test_pair_dx_case_widens_little_has_room_and_rejects_the_mutations(index):
+    """dx of the conv pair with every pixel judged: the widened pixels (a slope the kernel may take otherwise than the
+    oracle reaches them) are at most 5 % and their tolerance stays below 1/16 of the rel_linf allowance; the kernel's
+    rounding points restated in float32 keep to the bound; four wrong kernels do not."""
+    c = B.PAIR_DX_CASES[index]
+    p = c.problem
+    p.check_ranges()
+    ref, tol, t = p.ref['dx'], p.tolerances()['dx'], p.parts
+    assert tol.shape == ref.shape and np.all(tol > 0)
+    allow = B.ALLOW[p.dtype] * np.abs(ref).max()
+    widened = p.widened
+    share = float(widened.mean())
+    worst = float((tol[widened] / allow).max()) if widened.any() else 0.0
+    fine = float(np.mean(tol < allow / 16))
+    room = B.worst_ratio(p.restated(store=False)['dx'], ref, p.tolerances(store=False)['dx'])
+    stored = B.worst_ratio(p.restated()['dx'], ref, tol)
+    exact = B.worst_ratio(p.kernel_steps(p.q, np.float64)[3], ref, p.tolerances(store=False)['dx'])
+    print(f'{c.id}: {int((~t["decided"]).sum())} undecided and {int(t["flip"].sum())} contested slopes of {t["flip"].size}, '
+          f'widened pixels {share:.2%}, their largest tolerance {worst:.2g} of the rel_linf allowance; tol < allowance / 16 on '
+          f'{fine:.1%}; restatement / tol {room:.3f} (stored {stored:.3f}; rounding points in exact arithmetic {exact:.3f})')
+    assert share <= 0.05, f'{share:.2%} of the dx pixels widened (> 5 %)'
+    assert worst < 1 / 16, f'a widened pixel has {worst:.3g} of the rel_linf allowance (>= 1/16)'
+    if p.half:
+        assert widened.any(), 'no contested slope: the rule is not exercised'
+    assert room <= 1.0 and stored <= 1.0 and exact <= 1.0, (room, stored, exact)
+    failures = []
+    for what, mutate in B.pair_dx_mutants(p).items():
+        got = p.restated(mutate=mutate)['dx']
+        ratio, lin = B.worst_ratio(got, ref, tol), rel_linf(got, ref)
+        accepted = lin <= B.ALLOW[p.dtype]
+        print(f'    {what}: {ratio:.3g} of the bound, rel_linf {lin:.1e}' +
+              (f' <= {B.ALLOW[p.dtype]:g}: rel_linf accepts this mutant, the bound rejects it' if accepted else ''))
+        if not ratio > 1.0:
+            failures.append(f'{what} passes the bound ({ratio:.3g})' + (f' -- and rel_linf = {lin:.1e} accepts it' if accepted else ''))
+    assert not failures, '\n'.join(failures)
+
+
+def test_the_from_output_table():
+    ids = set(B.FROM_OUTPUT_IDS)
+    assert len(ids) == len(B.FROM_OUTPUT_CASES)
+    vec = {}
+    for c in B.FROM_OUTPUT_CASES:
+        p = c.problem
+        if p.kind != 'act':
+            vec.setdefault((p.dtype, p.kind, p.shape[3]), set()).add(p.check_inputs())
+    for dtype in B.STORE:
+        assert f'{dtype[5:]}-act-37x141x1' in ids
+        for kind in ('dice', 'jaccard'):
+            # 16 | hw c elem on one shape and not on the other, where the element size leaves the choice (c elem < 16)
+            assert vec[dtype, kind, 1] == vec[dtype, kind, 2] == {True, False}
+            assert vec[dtype, kind, 4] == ({True} if dtype == 'float32' else {True, False})
+            assert vec[dtype, kind, 3] == {False}
+
+
+@pytest.mark.parametrize('index', range(len(B.FROM_OUTPUT_CASES)), ids=B.FROM_OUTPUT_IDS)
+def test_from_output_case_has_room_and_rejects_the_mutation(index):
+    """y (1 - y) of a stored y: the float32 restatement keeps to 3 u |ref| (+ the coefficient terms of seg_loss); the
+    same from a y rounded once more to binary16 does not, and rel_linf accepts it."""
+    c = B.FROM_OUTPUT_CASES[index]
+    p = c.problem
+    p.check_inputs()
+    ref, tol = p.ref['dx'], p.tolerances()['dx']
+    assert tol.shape == ref.shape and np.all(tol > 0)
+    zero = (p.q['y'] == 0) | (p.q['y'] == 1)
+    assert zero.any() and np.all(ref[zero] == 0) and np.all(ref[~zero] != 0)
+    room = B.worst_ratio(p.restated(store=False)['dx'], ref, p.tolerances(store=False)['dx'])
+    stored = B.worst_ratio(p.restated()['dx'], ref, tol)
+    mutant = p.mutated()
+    ratio, lin, allow = B.worst_ratio(mutant, ref, tol), rel_linf(mutant, ref), B.ALLOW[p.dtype]
+    print(f'{c.id}: restatement / tol {room:.3f} (stored {stored:.3f}); y rounded to binary16: {ratio:.3g} of the bound, '
+          f'rel_linf {lin:.1e}' + (f' <= {allow:g}: rel_linf accepts this mutant, the bound rejects it' if lin <= allow else ''))
+    assert room <= 1.0 and stored <= 1.0, (room, stored)
+    assert ratio > 1.0, f'{c.id}: y (1 - y) from a binary16 y passes the bound ({ratio:.3g})' + \
+        (f' -- and rel_linf = {lin:.1e} accepts it' if lin <= allow else '')
 
 
 @pytest.mark.parametrize('index', range(len(B.CASES)), ids=B.CASE_IDS)
