@@ -22,7 +22,7 @@ def read_all(lib, hiplib, handle):
 
 
 def assert_all_zero(reports):
-    assert len(reports) == 13
+    assert len(reports) == 14
     for name, values in reports.items():
         assert values == (0,) * len(values), f'{name} of a new context: {values}'
 

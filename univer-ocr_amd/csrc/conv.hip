@@ -190,15 +190,15 @@ __global__ __launch_bounds__(256) void conv_wgrad_finish(const double* __restric
 }
 
 template <typename TS, typename T>
-int fwd_generic(uocr_ctx* ctx, const void* x, const void* w, const void* b, void* y, const ConvDims& d,
-                double pad_value, int use_bias, int act, double act_alpha) {
+int run_generic(uocr_ctx* ctx, const ConvFwd& c) {
+    const ConvDims& d = c.d;
     int cb = (d.cout % 4 == 0) ? 4 : (d.cout % 2 == 0 ? 2 : 1);
-    while (cb > 1 && (reinterpret_cast<uintptr_t>(y) % (sizeof(TS) * cb))) cb >>= 1;
+    while (cb > 1 && (reinterpret_cast<uintptr_t>(c.y) % (sizeof(TS) * cb))) cb >>= 1;
     const size_t total = (size_t)d.n * d.oh * d.ow * (d.cout / cb);
     const dim3 grid(uocr_blocks_for(total, 256, 1u << 20)), block(256);
-#define LAUNCH_FWD(CB)                                                                                      \
-    hipLaunchKernelGGL((conv_fwd_generic<TS, T, CB>), grid, block, 0, ctx->stream, (const TS*)x, (const T*)w, \
-                       (const T*)b, (TS*)y, d, (T)pad_value, use_bias, act, (T)act_alpha)
+#define LAUNCH_FWD(CB)                                                                                          \
+    hipLaunchKernelGGL((conv_fwd_generic<TS, T, CB>), grid, block, 0, ctx->stream, (const TS*)c.x, (const T*)c.w, \
+                       (const T*)c.b, (TS*)c.y, d, (T)c.pad_value, c.use_bias, c.act, (T)c.act_alpha)
     if (cb == 4) LAUNCH_FWD(4);
     else if (cb == 2) LAUNCH_FWD(2);
     else LAUNCH_FWD(1);
@@ -208,14 +208,15 @@ int fwd_generic(uocr_ctx* ctx, const void* x, const void* w, const void* b, void
 }
 
 template <typename TS, typename T>
-int dgrad_generic(uocr_ctx* ctx, const void* dy, const void* w, void* dx, const ConvDims& d, const ActMask& mask) {
+int run_generic(uocr_ctx* ctx, const ConvDgrad& c) {
+    const ConvDims& d = c.d;
     int cb = (d.cin % 4 == 0) ? 4 : (d.cin % 2 == 0 ? 2 : 1);
-    while (cb > 1 && (reinterpret_cast<uintptr_t>(dx) % (sizeof(TS) * cb))) cb >>= 1;
+    while (cb > 1 && (reinterpret_cast<uintptr_t>(c.dx) % (sizeof(TS) * cb))) cb >>= 1;
     const size_t total = (size_t)d.n * d.h * d.w * (d.cin / cb);
     const dim3 grid(uocr_blocks_for(total, 256, 1u << 20)), block(256);
 #define LAUNCH_DG(CB) \
-    hipLaunchKernelGGL((conv_dgrad_generic<TS, T, CB>), grid, block, 0, ctx->stream, (const TS*)dy, (const T*)w, (TS*)dx, d, \
-                       (const TS*)mask.y, mask.act, (T)mask.alpha)
+    hipLaunchKernelGGL((conv_dgrad_generic<TS, T, CB>), grid, block, 0, ctx->stream, (const TS*)c.dy, (const T*)c.w, \
+                       (TS*)c.dx, d, (const TS*)c.mask.y, c.mask.act, (T)c.mask.alpha)
     if (cb == 4) LAUNCH_DG(4);
     else if (cb == 2) LAUNCH_DG(2);
     else LAUNCH_DG(1);
@@ -225,11 +226,11 @@ int dgrad_generic(uocr_ctx* ctx, const void* dy, const void* w, void* dx, const 
 }
 
 template <typename TS, typename T>
-int wgrad_generic(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw, void* db, const ConvDims& d,
-                  double pad_value, int use_bias, int accumulate) {
+int run_generic(uocr_ctx* ctx, const ConvWgrad& c) {
+    const ConvDims& d = c.d;
     const int K = d.kh * d.kw * d.cin;
     const int kc = K * d.cout;
-    const int npairs = kc + (use_bias ? d.cout : 0);
+    const int npairs = kc + (c.use_bias ? d.cout : 0);
     const size_t npix = (size_t)d.n * d.oh * d.ow;
     // blocks: ~512 pixels each, at most 2048, partial buffer at most half the workspace
     size_t nblk = (npix + 511) / 512;
@@ -241,35 +242,25 @@ int wgrad_generic(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void*
     nblk = (npix + ppb - 1) / ppb;
     double* partial = (double*)ctx->workspace;
     hipLaunchKernelGGL((conv_wgrad_partial_generic<TS, T>), dim3((unsigned)nblk), dim3(256), 0, ctx->stream,
-                       (const TS*)x, (const TS*)dy, partial, d, (T)pad_value, npairs, ppb);
+                       (const TS*)c.x, (const TS*)c.dy, partial, d, (T)c.pad_value, npairs, ppb);
     UOCR_LAUNCH_CHECK(ctx);
     hipLaunchKernelGGL((conv_wgrad_finish<T>), dim3((npairs + 255) / 256), dim3(256), 0, ctx->stream,
-                       (const double*)partial, (T*)dw, (T*)db, npairs, (int)nblk, kc, accumulate,
-                       uocr_grad_unscale(dtype));
+                       (const double*)partial, (T*)c.dw, (T*)c.db, npairs, (int)nblk, kc, c.accumulate,
+                       uocr_grad_unscale(c.dtype));
     UOCR_LAUNCH_CHECK(ctx);
-    if (!use_bias && !accumulate && db)
-        UOCR_HIP(ctx, hipMemsetAsync(db, 0, (size_t)d.cout * sizeof(T), ctx->stream));
+    if (!c.use_bias && !c.accumulate && c.db)
+        UOCR_HIP(ctx, hipMemsetAsync(c.db, 0, (size_t)d.cout * sizeof(T), ctx->stream));
+    return UOCR_OK;
+}
+
+template <class Call>
+int by_dtype(uocr_ctx* ctx, const Call& c) {
+    UOCR_DISPATCH_ACT(ctx, c.dtype, { return run_generic<TS, T>(ctx, c); });
     return UOCR_OK;
 }
 
 }  // namespace
 
-int uocr_conv_fwd_generic(uocr_ctx* ctx, int dtype, const void* x, const void* w, const void* b, void* y,
-                          const ConvDims& d, double pad_value, int use_bias, int act, double act_alpha) {
-    UOCR_DISPATCH_ACT(ctx, dtype, { return fwd_generic<TS, T>(ctx, x, w, b, y, d, pad_value, use_bias, act, act_alpha); });
-    return UOCR_OK;
-}
-
-int uocr_conv_dgrad_generic(uocr_ctx* ctx, int dtype, const void* dy, const void* w, void* dx, const ConvDims& d,
-                            const ActMask& mask) {
-    UOCR_DISPATCH_ACT(ctx, dtype, { return dgrad_generic<TS, T>(ctx, dy, w, dx, d, mask); });
-    return UOCR_OK;
-}
-
-int uocr_conv_wgrad_generic(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw, void* db,
-                            const ConvDims& d, double pad_value, int use_bias, int accumulate) {
-    UOCR_DISPATCH_ACT(ctx, dtype, {
-        return wgrad_generic<TS, T>(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate);
-    });
-    return UOCR_OK;
-}
+int uocr_conv_generic_run(uocr_ctx* ctx, const ConvFwd& c) { return by_dtype(ctx, c); }
+int uocr_conv_generic_run(uocr_ctx* ctx, const ConvDgrad& c) { return by_dtype(ctx, c); }
+int uocr_conv_generic_run(uocr_ctx* ctx, const ConvWgrad& c) { return by_dtype(ctx, c); }

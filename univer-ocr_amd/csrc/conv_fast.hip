@@ -56,8 +56,8 @@ struct FastDims {
     int n, h, w, oh, ow, ph, pw;
 };
 
-// the shapes that the kernels in front of the table (uocr_conv_*_fast) ask for; the two 5x5 ones take any output size
-// (conv_is5x5_pad2 of conv_dims.h also wants the full one)
+// the shapes that the kernels in front of the table (uocr_conv_fast_run) ask for.  The two 5x5 ones are not
+// conv_is5x5_pad2(d, s): they lack its term oh == ceil(h / s), ow == ceil(w / s), and check_dims admits smaller outputs
 inline bool is_c16_same(const ConvDims& d, int cin, int cout) {          // 3x3, stride 1, output the size of the input
     return d.kh == 3 && d.kw == 3 && d.cin == cin && d.cout == cout && d.sh == 1 && d.sw == 1 && d.oh == d.h &&
            d.ow == d.w;
@@ -1169,8 +1169,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_taprows_finish(const float* __
 // accumulators of a tap row and ROW, the floats from one tap row of a block's partials to the next; rows x cols: the
 // extent that the tiles cover; producer(TA{}, grid, partial, tiles_per_block) launches the kernel for activations of type TA.
 template <class C, class Producer>
-int launch_wgrad_taprows(uocr_ctx* ctx, int dtype, int kernel_id, int n, int rows, int cols, void* dw, void* db, int use_bias,
-                         int accumulate, Producer&& producer) {
+int launch_wgrad_taprows(uocr_ctx* ctx, const ConvWgrad& c, int kernel_id, int rows, int cols, Producer&& producer) {
+    const int n = c.d.n;
     const int tiles_x = (cols + C::TW - 1) / C::TW, tiles_y = (rows + C::TH - 1) / C::TH;
     // ~1024 blocks: a few tiles of one column strip each (conv_wgrad_t542 measured at 32 x 256 x 512: 512 blocks 58 us,
     // 1024 57, 2048 65, 4096 74)
@@ -1181,14 +1181,14 @@ int launch_wgrad_taprows(uocr_ctx* ctx, int dtype, int kernel_id, int n, int row
     int rc = UOCR_OK;
     float* partial = uocr_partial_buffer(ctx, (size_t)nblocks * 5 * C::ROW * sizeof(float), &rc);
     if (rc) return rc;
-    UOCR_DISPATCH_TA(ctx, dtype, { producer(TA{}, grid, partial, per_block); });
+    UOCR_DISPATCH_TA(ctx, c.dtype, { producer(TA{}, grid, partial, per_block); });
     UOCR_LAUNCH_CHECK(ctx);
-    const float unscale = (float)uocr_grad_unscale(dtype);
-    const FinishDesc fd = finish_taprows(partial, nblocks, C::ROW, C::NW, C::NB, (float*)dw, (float*)db, use_bias,
-                                         accumulate, unscale);
+    const float unscale = (float)uocr_grad_unscale(c.dtype);
+    const FinishDesc fd = finish_taprows(partial, nblocks, C::ROW, C::NW, C::NB, (float*)c.dw, (float*)c.db, c.use_bias,
+                                         c.accumulate, unscale);
     return uocr_noted_conv(ctx, 2, kernel_id, uocr_finish(ctx, fd, [&] {
         hipLaunchKernelGGL((conv_wgrad_taprows_finish<C::ROW, C::NW>), dim3(5 * C::NW + C::NB), dim3(256), 0, ctx->stream,
-                           (const float*)partial, (float*)dw, (float*)db, nblocks, use_bias, accumulate, unscale);
+                           (const float*)partial, (float*)c.dw, (float*)c.db, nblocks, c.use_bias, c.accumulate, unscale);
     }));
 }
 
@@ -1246,24 +1246,24 @@ struct FastConv {
     }
     static FastDims dims(const ConvDims& d) { return FastDims{d.n, d.h, d.w, d.oh, d.ow, d.ph, d.pw}; }
 
-    static int fwd(uocr_ctx* ctx, int dtype, const void* x, const void* w, const void* b, void* y, const ConvDims& d,
-                   double pad, int use_bias, int act, double alpha) {
+    static int run(uocr_ctx* ctx, const ConvFwd& c) {
+        const ConvDims& d = c.d;
         // (the activation kind as a tag where that was measured to pay: the row-loop kernels with 4 output channels)
-        return uocr_act_tags<0>(ctx, act, UOCR_ACT_NONE, [&](auto kinds) -> int {
+        return uocr_act_tags<0>(ctx, c.act, UOCR_ACT_NONE, [&](auto kinds) -> int {
         using K = ActKindsIf<COUT == 4, decltype(kinds)>;
-        UOCR_DISPATCH_TA(ctx, dtype, {
+        UOCR_DISPATCH_TA(ctx, c.dtype, {
             if constexpr (R.fwd.px > 0) {
                 const int groups = (d.ow + R.fwd.px - 1) / R.fwd.px;
                 const dim3 grid((groups + 63) / 64, (d.oh + 3) / 4, d.n), block(64, 4);
                 hipLaunchKernelGGL((conv_fwd_px<KH, KW, CIN, COUT, SH, SW, R.fwd.px, TA, K>), grid, block, 0, ctx->stream,
-                                   (const TA*)x, (const float*)w, (const float*)b, (TA*)y, dims(d), (float)pad,
-                                   use_bias, act, (float)alpha);
+                                   (const TA*)c.x, (const float*)c.w, (const float*)c.b, (TA*)c.y, dims(d),
+                                   (float)c.pad_value, c.use_bias, c.act, (float)c.act_alpha);
             } else {
                 constexpr int PXW = 64 / (COUT / R.fwd.cob);
                 const dim3 grid((d.ow + PXW - 1) / PXW, (d.oh + 4 * R.fwd.py - 1) / (4 * R.fwd.py), d.n), block(64, 4);
                 hipLaunchKernelGGL((conv_fwd_fast<KH, KW, CIN, COUT, SH, SW, R.fwd.cob, R.fwd.py, TA>), grid, block, 0, ctx->stream,
-                                   (const TA*)x, (const float*)w, (const float*)b, (TA*)y, dims(d), (float)pad,
-                                   use_bias, act, (float)alpha);
+                                   (const TA*)c.x, (const float*)c.w, (const float*)c.b, (TA*)c.y, dims(d),
+                                   (float)c.pad_value, c.use_bias, c.act, (float)c.act_alpha);
             }
         });
         UOCR_LAUNCH_CHECK(ctx);
@@ -1271,28 +1271,28 @@ struct FastConv {
         });
     }
 
-    static int dgrad(uocr_ctx* ctx, int dtype, const void* dy, const void* w, void* dx, const ConvDims& d,
-                     const ActMask& mask) {
-        UOCR_DISPATCH_TA(ctx, dtype, {
+    static int run(uocr_ctx* ctx, const ConvDgrad& c) {
+        const ConvDims& d = c.d;
+        UOCR_DISPATCH_TA(ctx, c.dtype, {
             if constexpr (R.dx.px > 0) {
                 const int groups = (d.w + R.dx.px - 1) / R.dx.px;
                 const dim3 grid((groups + 63) / 64, (d.h + 3) / 4, d.n), block(64, 4);
                 hipLaunchKernelGGL((conv_dgrad_px<KH, KW, CIN, COUT, R.dx.px, TA>), grid, block, 0, ctx->stream,
-                                   (const TA*)dy, (const float*)w, (TA*)dx, dims(d), (const TA*)mask.y, mask.act,
-                                   (float)mask.alpha);
+                                   (const TA*)c.dy, (const float*)c.w, (TA*)c.dx, dims(d), (const TA*)c.mask.y,
+                                   c.mask.act, (float)c.mask.alpha);
             } else {
                 const dim3 grid((d.w + 63) / 64, (d.h + 4 * R.dx.py - 1) / (4 * R.dx.py), d.n), block(64, 4);
                 hipLaunchKernelGGL((conv_dgrad_fast<KH, KW, CIN, COUT, SH, SW, R.dx.py, TA>), grid, block, 0, ctx->stream,
-                                   (const TA*)dy, (const float*)w, (TA*)dx, dims(d), (const TA*)mask.y, mask.act,
-                                   (float)mask.alpha);
+                                   (const TA*)c.dy, (const float*)c.w, (TA*)c.dx, dims(d), (const TA*)c.mask.y,
+                                   c.mask.act, (float)c.mask.alpha);
             }
         });
         UOCR_LAUNCH_CHECK(ctx);
         return UOCR_OK;
     }
 
-    static int wgrad(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw, void* db, const ConvDims& d,
-                     double pad, int use_bias, int accumulate) {
+    static int run(uocr_ctx* ctx, const ConvWgrad& c) {
+        const ConvDims& d = c.d;
         using C = WgradCfg<KH, KW, CIN, COUT, SH, SW, R.dw.kyr, R.dw.cob>;
         // bands of output rows: ~512 (or 64) blocks per (tap group, channel group), at least 4 rows each
         constexpr int RQ = 4;             // rows consumed per block iteration (one per wave)
@@ -1310,19 +1310,19 @@ struct FastConv {
         int rc = UOCR_OK;
         float* partial = uocr_partial_buffer(ctx, bytes, &rc);
         if (rc) return rc;
-        UOCR_DISPATCH_TA(ctx, dtype, {
+        UOCR_DISPATCH_TA(ctx, c.dtype, {
             hipLaunchKernelGGL((conv_wgrad_fast<KH, KW, CIN, COUT, SH, SW, R.dw.kyr, R.dw.cob, R.dw.px, (CIN >= 4), TA>),
-                               dim3(nblocks, ngroups), dim3(64, 4), 0, ctx->stream, (const TA*)x, (const TA*)dy,
-                               partial, dims(d), (float)pad, rows, nbands);
+                               dim3(nblocks, ngroups), dim3(64, 4), 0, ctx->stream, (const TA*)c.x, (const TA*)c.dy,
+                               partial, dims(d), (float)c.pad_value, rows, nbands);
         });
         UOCR_LAUNCH_CHECK(ctx);
-        const float unscale = (float)uocr_grad_unscale(dtype);
-        const FinishDesc fd = finish_fast(partial, nblocks, ngroups, {C::NP, C::NW, KW, CIN, COUT, R.dw.kyr, R.dw.cob}, (float*)dw,
-                                          (float*)db, use_bias, accumulate, unscale);
+        const float unscale = (float)uocr_grad_unscale(c.dtype);
+        const FinishDesc fd = finish_fast(partial, nblocks, ngroups, {C::NP, C::NW, KW, CIN, COUT, R.dw.kyr, R.dw.cob},
+                                          (float*)c.dw, (float*)c.db, c.use_bias, c.accumulate, unscale);
         return uocr_finish(ctx, fd, [&] {
             hipLaunchKernelGGL((conv_wgrad_fast_finish<KH, KW, CIN, COUT, R.dw.kyr, R.dw.cob, C::NW, C::NP>),
-                               dim3(C::NACC, ngroups), dim3(256), 0, ctx->stream, (const float*)partial, (float*)dw,
-                               (float*)db, nblocks, use_bias, accumulate, unscale);
+                               dim3(C::NACC, ngroups), dim3(256), 0, ctx->stream, (const float*)partial, (float*)c.dw,
+                               (float*)c.db, nblocks, c.use_bias, c.accumulate, unscale);
         });
     }
 };
@@ -1349,39 +1349,39 @@ int launch_c16(uocr_ctx* ctx, Kernel kernel, int py, const C16Args& a, const Con
     return UOCR_OK;
 }
 
-}  // namespace
-
-bool uocr_conv_fast_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d, const void* p0, const void* p1,
-                             const void* p2) {
+// p0, p1: the two activation tensors of the call (4-element accesses); p2: a float32 parameter tensor
+bool fast_takes(uocr_ctx* ctx, int dtype, const ConvDims& d, const void* p0, const void* p1, const void* p2) {
     const int base = UOCR_DTYPE_BASE(dtype);
     if ((base != UOCR_F32 && base != UOCR_F16) || !ctx->opt_fast) return false;
-    // p0, p1: the two activation tensors of the call (4-element accesses); p2: a float32 parameter tensor
     if (!uocr_aligned_act(p0, dtype) || !uocr_aligned_act(p1, dtype) || !uocr_aligned_act(p2, UOCR_F32)) return false;
     return with_fast_conv(d, [](auto) {});
 }
 
+}  // namespace
+
+bool uocr_conv_fast_takes(uocr_ctx* ctx, const ConvFwd& c) { return fast_takes(ctx, c.dtype, c.d, c.x, c.y, c.w); }
+bool uocr_conv_fast_takes(uocr_ctx* ctx, const ConvDgrad& c) { return fast_takes(ctx, c.dtype, c.d, c.dy, c.dx, c.w); }
+bool uocr_conv_fast_takes(uocr_ctx* ctx, const ConvWgrad& c) { return fast_takes(ctx, c.dtype, c.d, c.x, c.dy, c.dw); }
+
 // (the 16-channel quad-lane kernels and the Char conv_1 dx kernel exist in float32 only: binary16 runs those
 // shapes -- none of them is on the page nets' fused path -- through the FastConv kernels of the table)
-int uocr_conv_fwd_fast(uocr_ctx* ctx, int dtype, const void* x, const void* w, const void* b, void* y,
-                       const ConvDims& d, double pad_value, int use_bias, int act, double act_alpha) {
-    const bool f32 = UOCR_DTYPE_BASE(dtype) == UOCR_F32;
-    const C16Args c16{x, w, b, y, (float)pad_value, use_bias, act, (float)act_alpha, ActMask{nullptr, UOCR_ACT_NONE, 0.0}};
+int uocr_conv_fast_run(uocr_ctx* ctx, const ConvFwd& c) {
+    const ConvDims& d = c.d;
+    const bool f32 = UOCR_DTYPE_BASE(c.dtype) == UOCR_F32;
+    const C16Args c16{c.x, c.w, c.b, c.y, (float)c.pad_value, c.use_bias, c.act, (float)c.act_alpha, ActMask{nullptr, UOCR_ACT_NONE, 0.0}};
     if (f32 && is_c16_same(d, 1, 16))
         return launch_c16(ctx, conv_c16_expand<3, 3, 2, false>, 2, c16, d, 0, UOCR_CONV_C16_EXPAND);
     if (f32 && is_c16_same(d, 16, 1))
         return launch_c16(ctx, conv_c16_reduce<3, 3, 4, false>, 4, c16, d, 0, UOCR_CONV_C16_REDUCE);
     int rc = UOCR_OK;
-    if (with_fast_conv(d, [&](auto fc) {
-            rc = uocr_noted_conv(ctx, 0, fc.FWD_KERNEL, fc.fwd(ctx, dtype, x, w, b, y, d, pad_value, use_bias, act, act_alpha));
-        }))
-        return rc;
+    if (with_fast_conv(d, [&](auto fc) { rc = uocr_noted_conv(ctx, 0, fc.FWD_KERNEL, fc.run(ctx, c)); })) return rc;
     UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "no fast conv kernel for this shape");
 }
 
-int uocr_conv_dgrad_fast(uocr_ctx* ctx, int dtype, const void* dy, const void* w, void* dx, const ConvDims& d,
-                         const ActMask& mask) {
-    const bool f32 = UOCR_DTYPE_BASE(dtype) == UOCR_F32;
-    const C16Args c16{dy, w, nullptr, dx, 0.f, 0, UOCR_ACT_NONE, 0.f, mask};
+int uocr_conv_fast_run(uocr_ctx* ctx, const ConvDgrad& c) {
+    const ConvDims& d = c.d;
+    const bool f32 = UOCR_DTYPE_BASE(c.dtype) == UOCR_F32;
+    const C16Args c16{c.dy, c.w, nullptr, c.dx, 0.f, 0, UOCR_ACT_NONE, 0.f, c.mask};
     if (f32 && is_c16_same(d, 16, 1))
         return launch_c16(ctx, conv_c16_expand<3, 3, 2, true>, 2, c16, d, 1, UOCR_CONV_C16_EXPAND);
     if (f32 && is_c16_same(d, 1, 16))
@@ -1389,8 +1389,8 @@ int uocr_conv_dgrad_fast(uocr_ctx* ctx, int dtype, const void* dy, const void* w
     if (f32 && d.kh == 5 && d.kw == 3 && d.sh == 2 && d.sw == 1 && d.ph == 0 && d.pw == 1 && d.cin == 1 && d.cout == 64 &&
         d.h <= 65535 && d.n <= 65535) {                   // (rows and images are grid dimensions y and z)
         hipLaunchKernelGGL(conv_dgrad_c64s2, dim3((unsigned)((d.w + 15) / 16), d.h, d.n), dim3(256), 0, ctx->stream,
-                           (const float*)dy, (const float*)w, (float*)dx, d.n, d.h, d.w, d.oh, d.ow,
-                           (const float*)mask.y, mask.act, (float)mask.alpha);
+                           (const float*)c.dy, (const float*)c.w, (float*)c.dx, d.n, d.h, d.w, d.oh, d.ow,
+                           (const float*)c.mask.y, c.mask.act, (float)c.mask.alpha);
         UOCR_LAUNCH_CHECK(ctx);
         uocr_note_conv(ctx, 1, UOCR_CONV_DGRAD_C64S2);
         return UOCR_OK;
@@ -1398,13 +1398,13 @@ int uocr_conv_dgrad_fast(uocr_ctx* ctx, int dtype, const void* dy, const void* w
     if (is_5x5_s2_pad2(d) && ((d.cin == 1 && (d.cout == 1 || d.cout == 4)) || (d.cin == 4 && d.cout == 4))) {
         const dim3 grid(((d.w + 1) / 2 + 63) / 64, ((d.h + 1) / 2 + 3) / 4, d.n), block(64, 4);
         const FastDims fd{d.n, d.h, d.w, d.oh, d.ow, d.ph, d.pw};
-        const int rc = uocr_act_tags<1>(ctx, UOCR_ACT_NONE, mask.act, [&](auto kinds) -> int {
+        const int rc = uocr_act_tags<1>(ctx, UOCR_ACT_NONE, c.mask.act, [&](auto kinds) -> int {
             using K = decltype(kinds);             // (4 -> 4 only: the 1-channel forms gain nothing)
             using D = ActKinds<UOCR_ACT_DYN, UOCR_ACT_DYN>;
-            UOCR_DISPATCH_TA(ctx, dtype, {
+            UOCR_DISPATCH_TA(ctx, c.dtype, {
                 auto launch = [&](auto kernel) {
-                    hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, (const TA*)dy, (const float*)w, (TA*)dx, fd,
-                                       (const TA*)mask.y, mask.act, (float)mask.alpha);
+                    hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, (const TA*)c.dy, (const float*)c.w, (TA*)c.dx, fd,
+                                       (const TA*)c.mask.y, c.mask.act, (float)c.mask.alpha);
                 };
                 if (d.cin == 4) launch(conv_dgrad_s2<4, 4, TA, K>);
                 else if (d.cout == 1) launch(conv_dgrad_s2<1, 1, TA, D>);
@@ -1418,15 +1418,14 @@ int uocr_conv_dgrad_fast(uocr_ctx* ctx, int dtype, const void* dy, const void* w
         return UOCR_OK;
     }
     int rc = UOCR_OK;
-    if (with_fast_conv(d, [&](auto fc) { rc = uocr_noted_conv(ctx, 1, fc.DX_KERNEL, fc.dgrad(ctx, dtype, dy, w, dx, d, mask)); }))
-        return rc;
+    if (with_fast_conv(d, [&](auto fc) { rc = uocr_noted_conv(ctx, 1, fc.DX_KERNEL, fc.run(ctx, c)); })) return rc;
     UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "no fast conv kernel for this shape");
 }
 
-int uocr_conv_wgrad_fast(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw, void* db,
-                         const ConvDims& d, double pad_value, int use_bias, int accumulate) {
-    const bool f32 = UOCR_DTYPE_BASE(dtype) == UOCR_F32;
-    if (f32 && is_c16_same(d, 16, 1) && pad_value == 0.0) {
+int uocr_conv_fast_run(uocr_ctx* ctx, const ConvWgrad& c) {
+    const ConvDims& d = c.d;
+    const bool f32 = UOCR_DTYPE_BASE(c.dtype) == UOCR_F32;
+    if (f32 && is_c16_same(d, 16, 1) && c.pad_value == 0.0) {
         constexpr int NA = 3 * 3 * 4 + 1;
         const long budget = uocr_budget(ctx, 2048);
         int rows = (int)((d.n * d.h + budget - 1) / budget);
@@ -1437,11 +1436,11 @@ int uocr_conv_wgrad_fast(uocr_ctx* ctx, int dtype, const void* x, const void* dy
         int rc = uocr_need_workspace(ctx, (size_t)nblocks * 4 * NA * sizeof(float));
         if (rc) return rc;
         float* partial = (float*)ctx->workspace;
-        hipLaunchKernelGGL((conv_c16_wgrad<3, 3>), dim3(nblocks), dim3(64, 4), 0, ctx->stream, (const float*)x,
-                           (const float*)dy, partial, d.h, d.w, d.ph, d.pw, rows, nbands);
+        hipLaunchKernelGGL((conv_c16_wgrad<3, 3>), dim3(nblocks), dim3(64, 4), 0, ctx->stream, (const float*)c.x,
+                           (const float*)c.dy, partial, d.h, d.w, d.ph, d.pw, rows, nbands);
         UOCR_LAUNCH_CHECK(ctx);
         hipLaunchKernelGGL((conv_c16_wgrad_finish<3, 3>), dim3(NA, 4), dim3(256), 0, ctx->stream,
-                           (const float*)partial, (float*)dw, (float*)db, nblocks, use_bias, accumulate);
+                           (const float*)partial, (float*)c.dw, (float*)c.db, nblocks, c.use_bias, c.accumulate);
         UOCR_LAUNCH_CHECK(ctx);
         uocr_note_conv(ctx, 2, UOCR_CONV_C16_WGRAD);
         return UOCR_OK;
@@ -1450,24 +1449,19 @@ int uocr_conv_wgrad_fast(uocr_ctx* ctx, int dtype, const void* x, const void* dy
     // 34 vs 29 us lose -- too little work per staged tile -- and stay on the register kernels)
     if (is_5x5_s2_pad2(d) && ctx->opt_tiled == 1 && d.cin == 1 && d.cout == 4)
         return launch_wgrad_taprows<S2Cfg<1, 4>>(
-            ctx, dtype, UOCR_CONV_WGRAD_S2_TILED, d.n, d.oh, d.ow, dw, db, use_bias, accumulate,
-            [&](auto ta, dim3 grid, float* partial, int per_block) {
+            ctx, c, UOCR_CONV_WGRAD_S2_TILED, d.oh, d.ow, [&](auto ta, dim3 grid, float* partial, int per_block) {
                 using TA = decltype(ta);
-                hipLaunchKernelGGL((conv_wgrad_s2_tiled<1, 4, TA>), grid, dim3(320), 0, ctx->stream, (const TA*)x,
-                                   (const TA*)dy, partial, d.h, d.w, d.oh, d.ow, (float)pad_value, per_block);
+                hipLaunchKernelGGL((conv_wgrad_s2_tiled<1, 4, TA>), grid, dim3(320), 0, ctx->stream, (const TA*)c.x,
+                                   (const TA*)c.dy, partial, d.h, d.w, d.oh, d.ow, (float)c.pad_value, per_block);
             });
     if (is_5x5_s1_pad2(d) && d.cin == 4 && d.cout == 2)
         return launch_wgrad_taprows<t542::Taprows>(
-            ctx, dtype, UOCR_CONV_WGRAD_T542, d.n, d.h, d.w, dw, db, use_bias, accumulate,
-            [&](auto ta, dim3 grid, float* partial, int per_block) {
+            ctx, c, UOCR_CONV_WGRAD_T542, d.h, d.w, [&](auto ta, dim3 grid, float* partial, int per_block) {
                 using TA = decltype(ta);
-                hipLaunchKernelGGL((conv_wgrad_t542<TA>), grid, dim3(320), 0, ctx->stream, (const TA*)x, (const TA*)dy,
-                                   partial, d.h, d.w, (float)pad_value, per_block);
+                hipLaunchKernelGGL((conv_wgrad_t542<TA>), grid, dim3(320), 0, ctx->stream, (const TA*)c.x, (const TA*)c.dy,
+                                   partial, d.h, d.w, (float)c.pad_value, per_block);
             });
     int rc = UOCR_OK;
-    if (with_fast_conv(d, [&](auto fc) {
-            rc = uocr_noted_conv(ctx, 2, UOCR_CONV_TABLE_FAST, fc.wgrad(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate));
-        }))
-        return rc;
+    if (with_fast_conv(d, [&](auto fc) { rc = uocr_noted_conv(ctx, 2, UOCR_CONV_TABLE_FAST, fc.run(ctx, c)); })) return rc;
     UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "no fast conv kernel for this shape");
 }

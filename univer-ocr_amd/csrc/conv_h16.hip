@@ -363,35 +363,45 @@ int launch_h16(uocr_ctx* ctx, const ToeplitzCall& c) {
     return UOCR_OK;
 }
 
-}  // namespace
-
-// which: 0 forward, 1 backward-data.  Measured against the vector kernels at 8 x 1024 x 2048 (tools/bench_h16.py):
+// Measured against the vector kernels at 8 x 1024 x 2048 (tools/bench_h16.py):
 // every 4-channel layer wins (1.2 - 2.8x); of the 1-channel layers only the stride-1 forward (49 -> 38 us) and the
 // stride-2 1 -> 4 backward-data (30 -> 23 us) do -- 2-byte result stores and 25 FMAs per pixel leave the matrix
 // cores nothing to win -- so the others stay on conv_fast.hip / conv_up.hip.
-bool uocr_conv_h16_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d, int which) {
-    if (UOCR_DTYPE_BASE(dtype) != UOCR_F16 || !ctx->opt_fast || !ctx->opt_h16 || d.n > 65535) return false;
-    if (conv_is5x5_pad2(d, 1)) return (d.cin == 4 && (d.cout == 2 || d.cout == 4)) || (d.cin == 1 && d.cout == 1 && which == 0);
-    if (conv_is5x5_pad2(d, 2)) return (d.cin == 4 && d.cout == 4) || (d.cin == 1 && d.cout == 4 && which == 1);   // (encoder)
+bool h16_shape(const ConvDims& d, bool dgrad) {
+    if (d.n > 65535) return false;
+    if (conv_is5x5_pad2(d, 1)) return (d.cin == 4 && (d.cout == 2 || d.cout == 4)) || (d.cin == 1 && d.cout == 1 && !dgrad);
+    if (conv_is5x5_pad2(d, 2)) return (d.cin == 4 && d.cout == 4) || (d.cin == 1 && d.cout == 4 && dgrad);   // (encoder)
     return false;
 }
+bool h16_aligned(const ConvFwd& c) { return uocr_aligned_act(c.x, c.dtype) && uocr_aligned_act(c.y, c.dtype); }
+bool h16_aligned(const ConvDgrad& c) {
+    return uocr_aligned_act(c.dy, c.dtype) && uocr_aligned_act(c.dx, c.dtype) &&
+           (!c.mask.y || uocr_aligned_act(c.mask.y, c.dtype));
+}
+template <class Call>                                    // dtype, options, this form's shape rule, pointers
+bool h16_takes(uocr_ctx* ctx, const Call& c, bool shape_ok) {
+    return UOCR_DTYPE_BASE(c.dtype) == UOCR_F16 && ctx->opt_fast && ctx->opt_h16 && shape_ok && h16_aligned(c);
+}
 
-int uocr_conv_fwd_h16(uocr_ctx* ctx, const void* x, const void* w, const void* b, void* y, const ConvDims& d,
-                      double pad_value, int use_bias, int act, double act_alpha) {
-    const ToeplitzCall c = toeplitz_fwd_call(x, w, b, y, d.n, d.h, d.w, d.oh, d.ow, d.ph, d.pw, pad_value, use_bias, act,
-                                             act_alpha);
+}  // namespace
+
+bool uocr_conv_h16_takes(uocr_ctx* ctx, const ConvFwd& c) { return h16_takes(ctx, c, h16_shape(c.d, false)); }
+bool uocr_conv_h16_takes(uocr_ctx* ctx, const ConvDgrad& c) { return h16_takes(ctx, c, h16_shape(c.d, true)); }
+
+int uocr_conv_h16_run(uocr_ctx* ctx, const ConvFwd& fc) {
+    const ConvDims& d = fc.d;
+    const ToeplitzCall c = toeplitz_fwd_call(fc, d.ph, d.pw);
     if (d.sh == 2) return launch_h16<Geo<4, 4, 5, 5, 2, M_FWD>>(ctx, c);
     if (d.cin == 1) return launch_h16<Geo<1, 1, 5, 5, 1, M_FWD>>(ctx, c);
     if (d.cout == 2) return launch_h16<Geo<4, 2, 5, 5, 1, M_FWD>>(ctx, c);
     return launch_h16<Geo<4, 4, 5, 5, 1, M_FWD>>(ctx, c);
 }
 
-int uocr_conv_dgrad_h16(uocr_ctx* ctx, const void* dy, const void* w, void* dx, const ConvDims& d,
-                        const ActMask& mask) {
+int uocr_conv_h16_run(uocr_ctx* ctx, const ConvDgrad& dc) {
+    const ConvDims& d = dc.d;
     // stride 2: a 3x3 window over dy per 2x2 block of dx;  stride 1: a forward conv over dy with flipped taps
     // (padding kh - 1 - ph)
-    const int ph = d.sh == 2 ? 1 : d.kh - 1 - d.ph, pw = d.sh == 2 ? 1 : d.kw - 1 - d.pw;
-    const ToeplitzCall c = toeplitz_dgrad_call(dy, w, dx, d.n, d.oh, d.ow, d.h, d.w, ph, pw, mask.y, mask.act, mask.alpha);
+    const ToeplitzCall c = d.sh == 2 ? toeplitz_dgrad_call(dc, 1, 1) : toeplitz_dgrad_call(dc, d.kh - 1 - d.ph, d.kw - 1 - d.pw);
     if (d.sh == 2) {
         if (d.cin == 4) return launch_h16<Geo<4, 4, 3, 3, 1, M_S2DGRAD>>(ctx, c);
         return launch_h16<Geo<4, 1, 3, 3, 1, M_S2DGRAD>>(ctx, c);
@@ -401,18 +411,12 @@ int uocr_conv_dgrad_h16(uocr_ctx* ctx, const void* dy, const void* w, void* dx, 
 }
 
 // Upsample2D(2) + conv 5x5 / padding 2, 4 -> 4 channels, on the low-res grid (conv_up.hip)
-bool uocr_upconv_h16_eligible(uocr_ctx* ctx, int dtype, int cin, int cout) {
-    return UOCR_DTYPE_BASE(dtype) == UOCR_F16 && ctx->opt_fast && ctx->opt_h16 && cin == 4 && cout == 4;
-}
+bool uocr_upconv_h16_takes(uocr_ctx* ctx, const ConvFwd& c) { return h16_takes(ctx, c, c.d.cin == 4 && c.d.cout == 4); }
+bool uocr_upconv_h16_takes(uocr_ctx* ctx, const ConvDgrad& c) { return h16_takes(ctx, c, c.d.cin == 4 && c.d.cout == 4); }
 
-int uocr_upconv_fwd_h16(uocr_ctx* ctx, const void* x_low, const void* w, const void* b, void* y, int n, int hl, int wl,
-                        int use_bias, int act, double act_alpha) {
-    return launch_h16<Geo<4, 4, 3, 3, 1, M_UPFWD>>(
-        ctx, toeplitz_fwd_call(x_low, w, b, y, n, hl, wl, 2 * hl, 2 * wl, 1, 1, 0.0, use_bias, act, act_alpha));
+int uocr_upconv_h16_run(uocr_ctx* ctx, const ConvFwd& c) {
+    return launch_h16<Geo<4, 4, 3, 3, 1, M_UPFWD>>(ctx, toeplitz_fwd_call(c, 1, 1));
 }
-
-int uocr_upconv_dgrad_h16(uocr_ctx* ctx, const void* dy, const void* w, void* dx_low, int n, int hl, int wl,
-                          const void* mask_y, int mask_act, double mask_alpha) {
-    return launch_h16<Geo<4, 4, 6, 6, 2, M_UPDGRAD>>(
-        ctx, toeplitz_dgrad_call(dy, w, dx_low, n, 2 * hl, 2 * wl, hl, wl, 2, 2, mask_y, mask_act, mask_alpha));
+int uocr_upconv_h16_run(uocr_ctx* ctx, const ConvDgrad& c) {
+    return launch_h16<Geo<4, 4, 6, 6, 2, M_UPDGRAD>>(ctx, toeplitz_dgrad_call(c, 2, 2));
 }

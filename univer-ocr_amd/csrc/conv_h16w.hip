@@ -763,15 +763,22 @@ __global__ __launch_bounds__(256) void wgrad_h16_s2_kernel(const _Float16* __res
     write_partials(red, partial);
 }
 
-}  // namespace
-
-bool uocr_conv_wgrad_h16_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d) {
-    return UOCR_DTYPE_BASE(dtype) == UOCR_F16 && ctx->opt_fast && ctx->opt_h16 && conv_is5x5_pad2(d, 1) &&
-           ((d.cin == 4 && d.cout == 2) || (d.cin == 1 && d.cout == 1)) && (long)d.h * d.w * 4 < (1l << 31);
+// what every binary16 weight-gradient rung asks besides its shape
+bool h16w_on(uocr_ctx* ctx, const ConvWgrad& c) {
+    return UOCR_DTYPE_BASE(c.dtype) == UOCR_F16 && ctx->opt_fast && ctx->opt_h16 && uocr_aligned_act(c.x, c.dtype) &&
+           uocr_aligned_act(c.dy, c.dtype);
 }
 
-int uocr_conv_wgrad_h16(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw, void* db, const ConvDims& d,
-                        double pad_value, int use_bias, int accumulate) {
+}  // namespace
+
+bool uocr_conv_h16_takes(uocr_ctx* ctx, const ConvWgrad& c) {
+    const ConvDims& d = c.d;
+    return h16w_on(ctx, c) && conv_is5x5_pad2(d, 1) && ((d.cin == 4 && d.cout == 2) || (d.cin == 1 && d.cout == 1)) &&
+           (long)d.h * d.w * 4 < (1l << 31);
+}
+
+int uocr_conv_h16_run(uocr_ctx* ctx, const ConvWgrad& c) {
+    const ConvDims& d = c.d;
     static int cache42 = 0, cache11 = 0;
     const bool one = d.cin == 1;
     const int nv = one ? e11::NV : e42::NV;
@@ -784,57 +791,49 @@ int uocr_conv_wgrad_h16(uocr_ctx* ctx, int dtype, const void* x, const void* dy,
     if (rc != UOCR_OK) return rc;
     float* partial = uocr_partial_buffer(ctx, (size_t)grid * nv * sizeof(float), &rc);
     if (rc != UOCR_OK) return rc;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)x, (const _Float16*)dy, partial,
-                       d.h, d.w, tiles_x, tiles_y, (int)ntiles, (float)pad_value);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)c.x, (const _Float16*)c.dy, partial,
+                       d.h, d.w, tiles_x, tiles_y, (int)ntiles, (float)c.pad_value);
     UOCR_LAUNCH_CHECK(ctx);
-    return h16_finish(ctx, partial, nv, one ? 25 : 200, (float*)dw, (float*)db, grid, use_bias, accumulate,
-                      (float)uocr_grad_unscale(dtype));
+    return h16_finish(ctx, partial, nv, one ? 25 : 200, (float*)c.dw, (float*)c.db, grid, c.use_bias, c.accumulate,
+                      (float)uocr_grad_unscale(c.dtype));
 }
 
+// Upsample2D(2) + conv (conv_up.hip: 4 -> 4 or 1 -> 1 channels, checked there)
+bool uocr_upconv_wgrad_h16_takes(uocr_ctx* ctx, const ConvWgrad& c) { return h16w_on(ctx, c); }
+
 // partial rows as conv_up.hip's producers write them: dw and db themselves (up_phase.h: UP4_NOUT / UP1_NOUT floats)
-int uocr_upconv_wgrad_h16(uocr_ctx* ctx, const void* x_low, const void* dy, float* partial, size_t partial_floats,
-                          int n, int hl, int wl, int ch, int* nblocks) {
-    if (ch == 1) {
-        static int cache1 = 0;
-        const int tiles_x = (wl + up1::BC - 1) / up1::BC, tiles_y = (hl + up1::BR - 1) / up1::BR;
-        const long ntiles = (long)n * tiles_y * tiles_x;
-        UOCR_REQUIRE(ctx, (long)hl * wl * 4 < (1l << 31));
-        int grid = 0;
-        const int rc = uocr_persistent_grid(ctx, wgrad_h16_up1_kernel, ntiles, 1, &cache1, &grid);
-        if (rc != UOCR_OK) return rc;
-        UOCR_REQUIRE(ctx, (size_t)grid * UP1_NOUT <= partial_floats);
-        hipLaunchKernelGGL(wgrad_h16_up1_kernel, dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)x_low,
-                           (const _Float16*)dy, partial, hl, wl, tiles_x, tiles_y, (int)ntiles);
-        UOCR_LAUNCH_CHECK(ctx);
-        *nblocks = grid;
-        return UOCR_OK;
-    }
-    static int cache = 0;
-    const int tiles_x = (wl + up::BC - 1) / up::BC, tiles_y = (hl + up::BR - 1) / up::BR;
+int uocr_upconv_wgrad_h16(uocr_ctx* ctx, const ConvWgrad& c, float* partial, size_t partial_floats, int* nblocks) {
+    static int cache4 = 0, cache1 = 0;
+    const int n = c.d.n, hl = c.d.h, wl = c.d.w;
+    const bool one = c.d.cin == 1;
+    const int tiles_x = (wl + up::BC - 1) / up::BC, tiles_y = (hl + up::BR - 1) / up::BR;     // (both: 16 x 64 positions)
     const long ntiles = (long)n * tiles_y * tiles_x;
-    UOCR_REQUIRE(ctx, (long)hl * wl * 16 < (1l << 31));
+    UOCR_REQUIRE(ctx, (long)hl * wl * (one ? 4 : 16) < (1l << 31));
+    const auto kernel = one ? wgrad_h16_up1_kernel : wgrad_h16_up_kernel;
     int grid = 0;
-    const int rc = uocr_persistent_grid(ctx, wgrad_h16_up_kernel, ntiles, 1, &cache, &grid);
+    const int rc = uocr_persistent_grid(ctx, kernel, ntiles, 1, one ? &cache1 : &cache4, &grid);
     if (rc != UOCR_OK) return rc;
-    UOCR_REQUIRE(ctx, (size_t)grid * UP4_NOUT <= partial_floats);
-    hipLaunchKernelGGL(wgrad_h16_up_kernel, dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)x_low,
-                       (const _Float16*)dy, partial, hl, wl, tiles_x, tiles_y, (int)ntiles);
+    UOCR_REQUIRE(ctx, (size_t)grid * (one ? UP1_NOUT : UP4_NOUT) <= partial_floats);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)c.x, (const _Float16*)c.dy, partial,
+                       hl, wl, tiles_x, tiles_y, (int)ntiles);
     UOCR_LAUNCH_CHECK(ctx);
     *nblocks = grid;
     return UOCR_OK;
 }
+static_assert(up::BR == up1::BR && up::BC == up1::BC, "uocr_upconv_wgrad_h16 tiles both kernels alike");
 
 // dw / db of the 5x5 / stride 2 / padding 2 encoder convs (4 -> 4, 1 -> 4, 1 -> 1)
-bool uocr_conv_wgrad_s2_h16_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d) {
-    return UOCR_DTYPE_BASE(dtype) == UOCR_F16 && ctx->opt_fast && ctx->opt_h16 && conv_is5x5_pad2(d, 2) &&
+bool uocr_conv_h16_s2_takes(uocr_ctx* ctx, const ConvWgrad& c) {
+    const ConvDims& d = c.d;
+    return h16w_on(ctx, c) && conv_is5x5_pad2(d, 2) &&
            ((d.cin == 4 && d.cout == 4) || (d.cin == 1 && (d.cout == 4 || d.cout == 1))) &&
            (long)d.h * d.w * d.cin < (1l << 31);
 }
 
 namespace {
 template <int CI, int CO>
-int launch_s2(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw, void* db, const ConvDims& d,
-              double pad_value, int use_bias, int accumulate) {
+int launch_s2(uocr_ctx* ctx, const ConvWgrad& c) {
+    const ConvDims& d = c.d;
     using G = S2<CI, CO>;
     static int cache = 0;
     int tiles_x, tiles_y;
@@ -844,17 +843,16 @@ int launch_s2(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw,
     if (rc != UOCR_OK) return rc;
     float* partial = uocr_partial_buffer(ctx, (size_t)grid * G::NV * sizeof(float), &rc);
     if (rc != UOCR_OK) return rc;
-    hipLaunchKernelGGL((wgrad_h16_s2_kernel<CI, CO>), dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)x,
-                       (const _Float16*)dy, partial, d.h, d.w, d.oh, d.ow, tiles_x, tiles_y, (int)ntiles, (float)pad_value);
+    hipLaunchKernelGGL((wgrad_h16_s2_kernel<CI, CO>), dim3(grid), dim3(256), 0, ctx->stream, (const _Float16*)c.x,
+                       (const _Float16*)c.dy, partial, d.h, d.w, d.oh, d.ow, tiles_x, tiles_y, (int)ntiles, (float)c.pad_value);
     UOCR_LAUNCH_CHECK(ctx);
-    return h16_finish(ctx, partial, G::NV, 25 * CI * CO, (float*)dw, (float*)db, grid, use_bias, accumulate,
-                      (float)uocr_grad_unscale(dtype));
+    return h16_finish(ctx, partial, G::NV, 25 * CI * CO, (float*)c.dw, (float*)c.db, grid, c.use_bias, c.accumulate,
+                      (float)uocr_grad_unscale(c.dtype));
 }
 }  // namespace
 
-int uocr_conv_wgrad_s2_h16(uocr_ctx* ctx, int dtype, const void* x, const void* dy, void* dw, void* db, const ConvDims& d,
-                           double pad_value, int use_bias, int accumulate) {
-    if (d.cin == 4) return launch_s2<4, 4>(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate);
-    if (d.cout == 4) return launch_s2<1, 4>(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate);
-    return launch_s2<1, 1>(ctx, dtype, x, dy, dw, db, d, pad_value, use_bias, accumulate);
+int uocr_conv_h16_s2_run(uocr_ctx* ctx, const ConvWgrad& c) {
+    if (c.d.cin == 4) return launch_s2<4, 4>(ctx, c);
+    if (c.d.cout == 4) return launch_s2<1, 4>(ctx, c);
+    return launch_s2<1, 1>(ctx, c);
 }

@@ -165,13 +165,14 @@ __global__ __launch_bounds__(256) void conv_h3_fwd_kernel(const float* __restric
 
 }  // namespace
 
-bool uocr_conv_h3_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d) {
-    return ctx->opt_h3 && UOCR_DTYPE_BASE(dtype) == UOCR_F32 && conv_is5x5_pad2(d, 1) && d.cin == 4 && d.cout == 2 &&
-           d.n <= 65535 && (size_t)d.w * 16 < 0x7FFFFFFFu;
+bool uocr_conv_h3_takes(uocr_ctx* ctx, const ConvFwd& c) {
+    const ConvDims& d = c.d;
+    return ctx->opt_h3 && UOCR_DTYPE_BASE(c.dtype) == UOCR_F32 && conv_is5x5_pad2(d, 1) && d.cin == 4 && d.cout == 2 &&
+           d.n <= 65535 && (size_t)d.w * 16 < 0x7FFFFFFFu && uocr_aligned16(c.x) && uocr_aligned16(c.y);
 }
 
-int uocr_conv_fwd_h3(uocr_ctx* ctx, const void* x, const void* w, const void* b, void* y, const ConvDims& d,
-                     double pad_value, int use_bias, int act, double act_alpha) {
+int uocr_conv_h3_run(uocr_ctx* ctx, const ConvFwd& c) {
+    const ConvDims& d = c.d;
     const int nstrips = (d.w + OWN - 1) / OWN;
     const int nw = std::min(4, nstrips);
     const int blocks_x = (nstrips + nw - 1) / nw;
@@ -187,27 +188,26 @@ int uocr_conv_fwd_h3(uocr_ctx* ctx, const void* x, const void* w, const void* b,
     const dim3 grid(blocks_x, bands, d.n), block(nw * 64);
     auto go = [&](auto padnz, auto atag) {
         hipLaunchKernelGGL((conv_h3_fwd_kernel<decltype(padnz)::value, decltype(atag)::value>), grid, block, lds, ctx->stream,
-                           (const float*)x, (const float*)w, (const float*)b, (float*)y, d.h, d.w, band_h, nstrips,
-                           (float)pad_value, use_bias, (float)act_alpha);
+                           (const float*)c.x, (const float*)c.w, (const float*)c.b, (float*)c.y, d.h, d.w, band_h, nstrips,
+                           (float)c.pad_value, c.use_bias, (float)c.act_alpha);
     };
     auto by_act = [&](auto padnz) {
-        switch (act) {
+        switch (c.act) {
             case UOCR_ACT_RELU: go(padnz, std::integral_constant<int, UOCR_ACT_RELU>{}); break;
             case UOCR_ACT_LEAKY: go(padnz, std::integral_constant<int, UOCR_ACT_LEAKY>{}); break;
             case UOCR_ACT_SIGMOID: go(padnz, std::integral_constant<int, UOCR_ACT_SIGMOID>{}); break;
             default: go(padnz, std::integral_constant<int, UOCR_ACT_NONE>{}); break;
         }
     };
-    if (pad_value != 0.0) by_act(std::true_type{});
+    if (c.pad_value != 0.0) by_act(std::true_type{});
     else by_act(std::false_type{});
     UOCR_LAUNCH_CHECK(ctx);
     return UOCR_OK;
 }
 
 #else
-bool uocr_conv_h3_eligible(uocr_ctx*, int, const ConvDims&) { return false; }
-int uocr_conv_fwd_h3(uocr_ctx* ctx, const void*, const void*, const void*, void*, const ConvDims&, double, int, int,
-                     double) {
+bool uocr_conv_h3_takes(uocr_ctx*, const ConvFwd&) { return false; }
+int uocr_conv_h3_run(uocr_ctx* ctx, const ConvFwd&) {
     UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "conv_h3: library built without UOCR_BUILD_EXPERIMENTS");
 }
 #endif

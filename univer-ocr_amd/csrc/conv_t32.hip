@@ -354,25 +354,33 @@ int launch_t32(uocr_ctx* ctx, const ToeplitzCall& c) {
     });
 }
 
-}  // namespace
-
-// which: 0 forward, 1 backward-data.  Bits of the "t32" option: 1 forward / 2 backward-data / 4 upsample+conv
-// backward-data of the 4-channel layers, 8 / 16 / 32 the same for the 1-channel layers.
+// Bits of the "t32" option: 1 forward / 2 backward-data / 4 upsample+conv backward-data of the 4-channel layers,
+// 8 / 16 / 32 the same for the 1-channel layers.
 // The default library holds only what is on by default (bit 2: backward-data of the 4-channel layers); the other forms --
 // measured slower in the page step, DESIGN.md section 5 -- are built with UOCR_BUILD_EXPERIMENTS=1 ./build.sh.
-bool uocr_conv_t32_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d, int which) {
+// bit4: the option bit of the 4-channel form (the 1-channel form's is 8 x that)
+bool t32_on(uocr_ctx* ctx, int dtype, const ConvDims& d, int bit4) {
     if (dtype != UOCR_F32 || !ctx->opt_fast || d.n > 65535 || !conv_is5x5_pad2(d, 1)) return false;
     const int built = ctx->opt_t32 & UOCR_T32_BUILT;
-    if (d.cin == 4 && (d.cout == 2 || d.cout == 4)) return built & (1 << which);
-    if (d.cin == 1 && d.cout == 1) return built & (8 << which);
+    if (d.cin == 4 && (d.cout == 2 || d.cout == 4)) return built & bit4;
+    if (d.cin == 1 && d.cout == 1) return built & (8 * bit4);
     return false;
 }
+bool t32_aligned(const ConvDgrad& c) {
+    return uocr_aligned16(c.dy) && uocr_aligned16(c.dx) && (!c.mask.y || uocr_aligned16(c.mask.y));
+}
 
-int uocr_conv_fwd_t32(uocr_ctx* ctx, const void* x, const void* w, const void* b, void* y, const ConvDims& d,
-                      double pad_value, int use_bias, int act, double act_alpha) {
+}  // namespace
+
+bool uocr_conv_t32_takes(uocr_ctx* ctx, const ConvFwd& c) {
+    return t32_on(ctx, c.dtype, c.d, 1) && uocr_aligned16(c.x) && uocr_aligned16(c.y);
+}
+bool uocr_conv_t32_takes(uocr_ctx* ctx, const ConvDgrad& c) { return t32_on(ctx, c.dtype, c.d, 2) && t32_aligned(c); }
+
+int uocr_conv_t32_run(uocr_ctx* ctx, const ConvFwd& fc) {
 #ifdef UOCR_EXPERIMENTS
-    const ToeplitzCall c = toeplitz_fwd_call(x, w, b, y, d.n, d.h, d.w, d.oh, d.ow, d.ph, d.pw, pad_value, use_bias, act,
-                                             act_alpha);
+    const ConvDims& d = fc.d;
+    const ToeplitzCall c = toeplitz_fwd_call(fc, d.ph, d.pw);
     if (d.cin == 1) return launch_t32<Geo<1, 1, 5, 5, 1, M_FWD>, 0>(ctx, c);
     if (d.cout == 2) return launch_t32<Geo<4, 2, 5, 5, 1, M_FWD>, 0>(ctx, c);
     return launch_t32<Geo<4, 4, 5, 5, 1, M_FWD>, 0>(ctx, c);
@@ -381,11 +389,10 @@ int uocr_conv_fwd_t32(uocr_ctx* ctx, const void* x, const void* w, const void* b
 #endif
 }
 
-int uocr_conv_dgrad_t32(uocr_ctx* ctx, const void* dy, const void* w, void* dx, const ConvDims& d,
-                        const ActMask& mask) {
+int uocr_conv_t32_run(uocr_ctx* ctx, const ConvDgrad& dc) {
+    const ConvDims& d = dc.d;
     // a forward conv over dy with flipped taps: padding kh - 1 - ph
-    const ToeplitzCall c = toeplitz_dgrad_call(dy, w, dx, d.n, d.oh, d.ow, d.h, d.w, d.kh - 1 - d.ph, d.kw - 1 - d.pw,
-                                               mask.y, mask.act, mask.alpha);
+    const ToeplitzCall c = toeplitz_dgrad_call(dc, d.kh - 1 - d.ph, d.kw - 1 - d.pw);
 #ifdef UOCR_EXPERIMENTS
     if (d.cin == 1) return launch_t32<Geo<1, 1, 5, 5, 1, M_DGRAD>, 1>(ctx, c);
 #endif
@@ -394,19 +401,19 @@ int uocr_conv_dgrad_t32(uocr_ctx* ctx, const void* dy, const void* w, void* dx, 
 }
 
 // backward-data of Upsample2D(2) + conv 5x5 / padding 2 (4 -> 4 or 1 -> 1 channels) on the low-res grid
-bool uocr_upconv_t32_eligible(uocr_ctx* ctx, int dtype, int cin, int cout) {
+bool uocr_upconv_t32_takes(uocr_ctx* ctx, const ConvDgrad& c) {
     const int built = ctx->opt_t32 & UOCR_T32_BUILT;
-    return dtype == UOCR_F32 && ctx->opt_fast &&
-           ((cin == 4 && cout == 4 && (built & 4)) || (cin == 1 && cout == 1 && (built & 32)));
+    return c.dtype == UOCR_F32 && ctx->opt_fast &&
+           ((c.d.cin == 4 && c.d.cout == 4 && (built & 4)) || (c.d.cin == 1 && c.d.cout == 1 && (built & 32))) &&
+           t32_aligned(c);
 }
 
-int uocr_upconv_dgrad_t32(uocr_ctx* ctx, const void* dy, const void* w, void* dx_low, int n, int hl, int wl, int ch,
-                          const void* mask_y, int mask_act, double mask_alpha) {
+int uocr_upconv_t32_run(uocr_ctx* ctx, const ConvDgrad& dc) {
 #ifndef UOCR_EXPERIMENTS
     UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "upconv_t32: library built without UOCR_BUILD_EXPERIMENTS");
 #else
-    const ToeplitzCall c = toeplitz_dgrad_call(dy, w, dx_low, n, 2 * hl, 2 * wl, hl, wl, 2, 2, mask_y, mask_act, mask_alpha);
-    if (ch == 1) return launch_t32<Geo<1, 1, 6, 6, 2, M_UPDGRAD, 4>, 1>(ctx, c);
+    const ToeplitzCall c = toeplitz_dgrad_call(dc, 2, 2);
+    if (dc.d.cin == 1) return launch_t32<Geo<1, 1, 6, 6, 2, M_UPDGRAD, 4>, 1>(ctx, c);
     return launch_t32<Geo<4, 4, 6, 6, 2, M_UPDGRAD>, 1>(ctx, c);
 #endif
 }

@@ -287,8 +287,8 @@ __global__ __launch_bounds__(256) void wgrad_t32_e_kernel(const float* __restric
 }
 
 template <int CI, int CO>
-int launch_s2(uocr_ctx* ctx, const void* x, const void* dy, void* dw, void* db, const ConvDims& d, double pad_value,
-              int use_bias, int accumulate) {
+int launch_s2(uocr_ctx* ctx, const ConvWgrad& c) {
+    const ConvDims& d = c.d;
     using G = S2<CI, CO>;
     static int cache = 0;
     int tiles_x, tiles_y;
@@ -299,18 +299,18 @@ int launch_s2(uocr_ctx* ctx, const void* x, const void* dy, void* dw, void* db, 
     rc = uocr_need_workspace(ctx, (size_t)grid * G::NV * sizeof(float));
     if (rc != UOCR_OK) return rc;
     float* partial = (float*)ctx->workspace;
-    hipLaunchKernelGGL((wgrad_t32_s2_kernel<CI, CO>), dim3(grid), dim3(256), 0, ctx->stream, (const float*)x,
-                       (const float*)dy, partial, d.h, d.w, d.oh, d.ow, tiles_x, tiles_y, (int)ntiles, (float)pad_value);
+    hipLaunchKernelGGL((wgrad_t32_s2_kernel<CI, CO>), dim3(grid), dim3(256), 0, ctx->stream, (const float*)c.x,
+                       (const float*)c.dy, partial, d.h, d.w, d.oh, d.ow, tiles_x, tiles_y, (int)ntiles, (float)c.pad_value);
     UOCR_LAUNCH_CHECK(ctx);
     hipLaunchKernelGGL(wgrad_t32_finish, dim3(G::NV), dim3(256), 0, ctx->stream, (const float*)partial, G::NV,
-                       25 * CI * CO, (float*)dw, (float*)db, grid, use_bias, accumulate);
+                       25 * CI * CO, (float*)c.dw, (float*)c.db, grid, c.use_bias, c.accumulate);
     UOCR_LAUNCH_CHECK(ctx);
     return UOCR_OK;
 }
 
 template <int CI, int CO>
-int launch_e(uocr_ctx* ctx, const void* x, const void* dy, void* dw, void* db, const ConvDims& d, double pad_value,
-             int use_bias, int accumulate) {
+int launch_e(uocr_ctx* ctx, const ConvWgrad& c) {
+    const ConvDims& d = c.d;
     using G = E1<CI, CO>;
     static int cache = 0;
     const int tiles_x = (d.w + 4 + G::BC - 1) / G::BC, tiles_y = (d.h + G::BR - 1) / G::BR;     // col runs over [-4, w)
@@ -321,11 +321,11 @@ int launch_e(uocr_ctx* ctx, const void* x, const void* dy, void* dw, void* db, c
     rc = uocr_need_workspace(ctx, (size_t)grid * G::NV * sizeof(float));
     if (rc != UOCR_OK) return rc;
     float* partial = (float*)ctx->workspace;
-    hipLaunchKernelGGL((wgrad_t32_e_kernel<CI, CO>), dim3(grid), dim3(256), 0, ctx->stream, (const float*)x,
-                       (const float*)dy, partial, d.h, d.w, tiles_x, tiles_y, (int)ntiles, (float)pad_value);
+    hipLaunchKernelGGL((wgrad_t32_e_kernel<CI, CO>), dim3(grid), dim3(256), 0, ctx->stream, (const float*)c.x,
+                       (const float*)c.dy, partial, d.h, d.w, tiles_x, tiles_y, (int)ntiles, (float)c.pad_value);
     UOCR_LAUNCH_CHECK(ctx);
     hipLaunchKernelGGL(wgrad_t32_finish, dim3(G::NV), dim3(256), 0, ctx->stream, (const float*)partial, G::NV,
-                       25 * CI * CO, (float*)dw, (float*)db, grid, use_bias, accumulate);
+                       25 * CI * CO, (float*)c.dw, (float*)c.db, grid, c.use_bias, c.accumulate);
     UOCR_LAUNCH_CHECK(ctx);
     return UOCR_OK;
 }
@@ -333,28 +333,27 @@ int launch_e(uocr_ctx* ctx, const void* x, const void* dy, void* dw, void* db, c
 }  // namespace
 
 // "t32" option bits: 64 = stride-1 weight gradients (4 -> 2, 1 -> 1), 128 = stride-2 (4 -> 4, 1 -> 4, 1 -> 1)
-bool uocr_conv_wgrad_t32_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d) {
-    if (dtype != UOCR_F32 || !ctx->opt_fast || (long)d.h * d.w * d.cin >= (1l << 31)) return false;
+bool uocr_conv_t32_takes(uocr_ctx* ctx, const ConvWgrad& c) {
+    const ConvDims& d = c.d;
+    if (c.dtype != UOCR_F32 || !ctx->opt_fast || (long)d.h * d.w * d.cin >= (1l << 31)) return false;
+    if (!uocr_aligned16(c.x) || !uocr_aligned16(c.dy)) return false;
     if ((ctx->opt_t32 & 64) && conv_is5x5_pad2(d, 1)) return (d.cin == 4 && d.cout == 2) || (d.cin == 1 && d.cout == 1);
     if ((ctx->opt_t32 & 128) && conv_is5x5_pad2(d, 2))
         return (d.cin == 4 && d.cout == 4) || (d.cin == 1 && (d.cout == 4 || d.cout == 1));
     return false;
 }
 
-int uocr_conv_wgrad_t32(uocr_ctx* ctx, const void* x, const void* dy, void* dw, void* db, const ConvDims& d,
-                        double pad_value, int use_bias, int accumulate) {
-    if (d.sh == 1) {
-        if (d.cin == 4) return launch_e<4, 2>(ctx, x, dy, dw, db, d, pad_value, use_bias, accumulate);
-        return launch_e<1, 1>(ctx, x, dy, dw, db, d, pad_value, use_bias, accumulate);
-    }
-    if (d.cin == 4) return launch_s2<4, 4>(ctx, x, dy, dw, db, d, pad_value, use_bias, accumulate);
-    if (d.cout == 4) return launch_s2<1, 4>(ctx, x, dy, dw, db, d, pad_value, use_bias, accumulate);
-    return launch_s2<1, 1>(ctx, x, dy, dw, db, d, pad_value, use_bias, accumulate);
+int uocr_conv_t32_run(uocr_ctx* ctx, const ConvWgrad& c) {
+    const ConvDims& d = c.d;
+    if (d.sh == 1) return d.cin == 4 ? launch_e<4, 2>(ctx, c) : launch_e<1, 1>(ctx, c);
+    if (d.cin == 4) return launch_s2<4, 4>(ctx, c);
+    if (d.cout == 4) return launch_s2<1, 4>(ctx, c);
+    return launch_s2<1, 1>(ctx, c);
 }
 
 #else
-bool uocr_conv_wgrad_t32_eligible(uocr_ctx*, int, const ConvDims&) { return false; }
-int uocr_conv_wgrad_t32(uocr_ctx* ctx, const void*, const void*, void*, void*, const ConvDims&, double, int, int) {
+bool uocr_conv_t32_takes(uocr_ctx*, const ConvWgrad&) { return false; }
+int uocr_conv_t32_run(uocr_ctx* ctx, const ConvWgrad&) {
     UOCR_FAIL(ctx, UOCR_ERR_UNSUPPORTED, "conv_t32w: library built without UOCR_BUILD_EXPERIMENTS");
 }
 #endif

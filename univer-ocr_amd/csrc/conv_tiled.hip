@@ -192,36 +192,33 @@ bool shape_ok(const ConvDims& d) {
 
 }  // namespace
 
-bool uocr_conv_tiled_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d) {
-    const int base = UOCR_DTYPE_BASE(dtype);
+bool uocr_conv_tiled_takes(uocr_ctx* ctx, const ConvFwd& c) {
+    const int base = UOCR_DTYPE_BASE(c.dtype);
     if ((base != UOCR_F32 && base != UOCR_F16) || !ctx->opt_fast || ctx->opt_tiled == 0) return false;
-    return shape_ok<4>(d) || shape_ok<2>(d);
+    return (shape_ok<4>(c.d) || shape_ok<2>(c.d)) && uocr_aligned_act(c.x, c.dtype) && uocr_aligned_act(c.y, c.dtype);
 }
 
-int uocr_conv_fwd_tiled(uocr_ctx* ctx, int dtype, const void* x, const void* w, const void* b, void* y,
-                        const ConvDims& d, double pad_value, int use_bias, int act, double act_alpha) {
+int uocr_conv_tiled_run(uocr_ctx* ctx, const ConvFwd& c) {
+    const ConvDims& d = c.d;
+    const float pad = (float)c.pad_value, alpha = (float)c.act_alpha;
     const TileDims td{d.n, d.h, d.w, d.ph, d.pw};
     const dim3 grid((d.w + TW - 1) / TW, (d.h + TH - 1) / TH, d.n), block(256);
-    UOCR_DISPATCH_TA(ctx, dtype, {
+    UOCR_DISPATCH_TA(ctx, c.dtype, {
         if (d.cout == 2 && d.ph == 2 && d.pw == 2 && ctx->opt_tiled != 2) {
             const dim3 wgrid((d.w + wide::WTW - 1) / wide::WTW, (d.h + wide::WTH - 1) / wide::WTH, d.n);
-            uocr_act_tags<0>(ctx, act, UOCR_ACT_NONE, [&](auto kinds) -> int {
-                hipLaunchKernelGGL((conv_fwd_t542<TA, decltype(kinds)>), wgrid, block, 0, ctx->stream, (const TA*)x,
-                                   (const float*)w, (const float*)b, (TA*)y, d.h, d.w, (float)pad_value, use_bias, act,
-                                   (float)act_alpha);
+            uocr_act_tags<0>(ctx, c.act, UOCR_ACT_NONE, [&](auto kinds) -> int {
+                hipLaunchKernelGGL((conv_fwd_t542<TA, decltype(kinds)>), wgrid, block, 0, ctx->stream, (const TA*)c.x,
+                                   (const float*)c.w, (const float*)c.b, (TA*)c.y, d.h, d.w, pad, c.use_bias, c.act, alpha);
                 return UOCR_OK;
             });
         } else if (d.cout == 4) {
-            hipLaunchKernelGGL((conv_tiled_kernel<5, 5, 4, 4, TA>), grid, block, 0, ctx->stream, (const TA*)x,
-                               (const float*)w, (const float*)b, (TA*)y, td, (float)pad_value, use_bias, act,
-                               (float)act_alpha);
+            hipLaunchKernelGGL((conv_tiled_kernel<5, 5, 4, 4, TA>), grid, block, 0, ctx->stream, (const TA*)c.x,
+                               (const float*)c.w, (const float*)c.b, (TA*)c.y, td, pad, c.use_bias, c.act, alpha);
         } else {
-            hipLaunchKernelGGL((conv_tiled_kernel<5, 5, 4, 2, TA>), grid, block, 0, ctx->stream, (const TA*)x,
-                               (const float*)w, (const float*)b, (TA*)y, td, (float)pad_value, use_bias, act,
-                               (float)act_alpha);
+            hipLaunchKernelGGL((conv_tiled_kernel<5, 5, 4, 2, TA>), grid, block, 0, ctx->stream, (const TA*)c.x,
+                               (const float*)c.w, (const float*)c.b, (TA*)c.y, td, pad, c.use_bias, c.act, alpha);
         }
     });
     UOCR_LAUNCH_CHECK(ctx);
     return UOCR_OK;
 }
-

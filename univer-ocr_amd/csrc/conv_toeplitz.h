@@ -67,18 +67,15 @@ struct ToeplitzCall {
     float mask_alpha;
 };
 
-// a forward conv: bias and activation, no mask
-inline ToeplitzCall toeplitz_fwd_call(const void* x, const void* w, const void* b, void* y, int n, int h_in, int w_in,
-                                      int h_out, int w_out, int ph, int pw, double pad, int use_bias, int act,
-                                      double alpha) {
-    return {x, w, b, y, nullptr, n, h_in, w_in, h_out, w_out, ph, pw, (float)pad, use_bias, act, (float)alpha,
-            UOCR_ACT_NONE, 0.f};
+// a forward conv: bias and activation, no mask; ph, pw: the padding of the kernel's window (upsample2x + conv: 1)
+inline ToeplitzCall toeplitz_fwd_call(const ConvFwd& c, int ph, int pw) {
+    return {c.x, c.w, c.b, c.y, nullptr, c.d.n, c.d.h, c.d.w, c.d.oh, c.d.ow, ph, pw, (float)c.pad_value, c.use_bias,
+            c.act, (float)c.act_alpha, UOCR_ACT_NONE, 0.f};
 }
-// backward-data: a conv over dy with zero padding, no bias, no activation; dx *= act'(mask_y) where there is a mask
-inline ToeplitzCall toeplitz_dgrad_call(const void* dy, const void* w, void* dx, int n, int h_in, int w_in, int h_out,
-                                        int w_out, int ph, int pw, const void* mask_y, int mask_act, double mask_alpha) {
-    return {dy, w, nullptr, dx, mask_y, n, h_in, w_in, h_out, w_out, ph, pw, 0.f, 0, UOCR_ACT_NONE, 0.f,
-            mask_y ? mask_act : UOCR_ACT_NONE, (float)mask_alpha};
+// backward-data: a conv over dy (window padding ph, pw; zero padding value), no bias; dx *= act'(mask.y) if there is a mask
+inline ToeplitzCall toeplitz_dgrad_call(const ConvDgrad& c, int ph, int pw) {
+    return {c.dy, c.w, nullptr, c.dx, c.mask.y, c.d.n, c.d.oh, c.d.ow, c.d.h, c.d.w, ph, pw, 0.f, 0, UOCR_ACT_NONE, 0.f,
+            c.mask.y ? c.mask.act : UOCR_ACT_NONE, (float)c.mask.alpha};
 }
 
 // the tile grid of a call over its position grid (U x U output pixels per position), and the size the kernels' 32-bit

@@ -581,6 +581,119 @@ int check_up(uocr_ctx* ctx, int dtype, int n, int hl, int wl, int cin, int cout,
     return UOCR_OK;
 }
 
+ConvDims up_dims(int n, int hl, int wl, int cin, int cout) { return {n, hl, wl, cin, cout, 5, 5, 1, 1, 2, 2, 2 * hl, 2 * wl}; }   // (conv_dims.h)
+int up_ncols(const ConvWgrad& c) { return c.d.cin == 1 ? UP1_NOUT : UP4_NOUT; }         // floats of a partial row
+
+// A forward / backward-data call as the rows of this file see it: the record, and the entry's weff argument, which only
+// the vector kernels use; the MFMA families get the record alone
+struct UpFwd { ConvFwd call; void* weff; };
+struct UpDgrad { ConvDgrad call; const void* weff; };
+template <class Up> bool up_h16_takes(uocr_ctx* ctx, const Up& u) { return uocr_upconv_h16_takes(ctx, u.call); }
+template <class Up> int up_h16_run(uocr_ctx* ctx, const Up& u) { return uocr_upconv_h16_run(ctx, u.call); }
+bool up_t32_takes(uocr_ctx* ctx, const UpDgrad& u) { return uocr_upconv_t32_takes(ctx, u.call); }
+int up_t32_run(uocr_ctx* ctx, const UpDgrad& u) { return uocr_upconv_t32_run(ctx, u.call); }
+
+int up_fwd_vector(uocr_ctx* ctx, const UpFwd& u) {
+    const ConvFwd& c = u.call;
+    const int n = c.d.n, hl = c.d.h, wl = c.d.w, cin = c.d.cin;
+    const int strips = (wl + RW - 1) / RW, rows = up_rows_per_block(strips, hl, n, (unsigned)uocr_budget(ctx, 2048));
+    if (cin != 1) uocr_note_split(ctx, (long long)strips * ((hl + rows - 1) / rows) * n, (long long)strips * ((hl + RH - 1) / RH) * n);
+    return uocr_act_tags<0>(ctx, c.act, UOCR_ACT_NONE, [&](auto kinds) -> int {
+    using K = decltype(kinds);
+    UOCR_DISPATCH_TA(ctx, c.dtype, {
+        if (cin == 1)
+            hipLaunchKernelGGL((up1_fwd_kernel<TA>), dim3((wl + RW - 1) / RW, (hl + RH - 1) / RH, n), dim3(256), 0,
+                               ctx->stream, (const TA*)c.x, (const float*)c.w, (const float*)c.b, (TA*)c.y, hl, wl,
+                               c.use_bias, c.act, (float)c.act_alpha);
+        else
+            hipLaunchKernelGGL((upconv_fwd_kernel<TA, K>), dim3(strips, (hl + rows - 1) / rows, n), dim3(256), 0,
+                               ctx->stream, (const TA*)c.x, (const float*)c.w, (const float*)c.b, (TA*)c.y, hl, wl, rows,
+                               c.use_bias, c.act, (float)c.act_alpha, (float*)u.weff);
+    });
+    UOCR_LAUNCH_CHECK(ctx);
+    return UOCR_OK;
+    });
+}
+
+int up_dgrad_vector(uocr_ctx* ctx, const UpDgrad& u) {
+    const ConvDgrad& c = u.call;
+    const int n = c.d.n, hl = c.d.h, wl = c.d.w, cin = c.d.cin;
+    const float* weff = (const float*)u.weff;              // from this layer's forward call with the same w, or null
+    if (cin != 1 && !weff) {
+        const int rc = uocr_need_workspace(ctx, NWEFF * sizeof(float));
+        if (rc != UOCR_OK) return rc;
+        hipLaunchKernelGGL(upconv_weff_kernel, dim3(1), dim3(256), 0, ctx->stream, (const float*)c.w, (float*)ctx->workspace);
+        weff = (const float*)ctx->workspace;
+    }
+    const dim3 grid((wl + RW - 1) / RW, (hl + RH - 1) / RH, n);
+    return uocr_act_tags<1>(ctx, UOCR_ACT_NONE, c.mask.act, [&](auto kinds) -> int {
+    using K = decltype(kinds);
+    UOCR_DISPATCH_TA(ctx, c.dtype, {
+        if (cin == 1)
+            hipLaunchKernelGGL((up1_dgrad_kernel<TA>), grid, dim3(256), 0, ctx->stream, (const TA*)c.dy, (const float*)c.w,
+                               (TA*)c.dx, hl, wl, (const TA*)c.mask.y, c.mask.act, (float)c.mask.alpha);
+        else
+            hipLaunchKernelGGL((upconv_dgrad_kernel<TA, K>), grid, dim3(256), 0, ctx->stream, (const TA*)c.dy,
+                               weff, (TA*)c.dx, hl, wl, (const TA*)c.mask.y, c.mask.act, (float)c.mask.alpha);
+    });
+    UOCR_LAUNCH_CHECK(ctx);
+    return UOCR_OK;
+    });
+}
+
+// the block partials are rows of dw and db themselves (up_phase.h); their float64 column sums: recorded when a deferred
+// group is open (finish_group.h), else one coalesced launch
+int up_wgrad_finish(uocr_ctx* ctx, const ConvWgrad& c, const float* partial, int nblocks) {
+    const float unscale = (float)uocr_grad_unscale(c.dtype);
+    const int ncols = up_ncols(c), ndw = ncols - c.d.cin;
+    const FinishDesc fd = finish_cols(partial, nblocks, ncols, ndw, (float*)c.dw, (float*)c.db, c.use_bias, c.accumulate, unscale);
+    return uocr_finish(ctx, fd, [&] {
+        hipLaunchKernelGGL(colsum_finish_kernel, dim3((ncols + 7) / 8), dim3(256), 0, ctx->stream, partial, nblocks,
+                           ncols, ndw, (float*)c.dw, (float*)c.db, c.use_bias, c.accumulate, unscale);
+    });
+}
+
+// binary16 MFMAs over channel / phase planes (conv_h16w.hip), same partial rows
+int up_wgrad_h16(uocr_ctx* ctx, const ConvWgrad& c) {
+    const size_t floats = (size_t)ctx->cu_count * 8 * up_ncols(c);
+    int rc = UOCR_OK, nblocks = 0;
+    float* partial = uocr_partial_buffer(ctx, floats * sizeof(float), &rc);
+    if (rc != UOCR_OK) return rc;
+    rc = uocr_upconv_wgrad_h16(ctx, c, partial, floats, &nblocks);
+    return rc != UOCR_OK ? rc : up_wgrad_finish(ctx, c, partial, nblocks);
+}
+
+int up_wgrad_vector(uocr_ctx* ctx, const ConvWgrad& c) {
+    const int n = c.d.n, hl = c.d.h, wl = c.d.w, cin = c.d.cin;
+    // fewer, longer blocks than the forward: every block ends with a reduction and a partial row for the finish kernel
+    const int strips = (wl + RW - 1) / RW, rows = up_rows_per_block(strips, hl, n, (unsigned)uocr_budget(ctx, 1024));
+    const int bands = (hl + rows - 1) / rows, nblocks = strips * bands * n;
+    uocr_note_split(ctx, nblocks, (long long)strips * ((hl + RH - 1) / RH) * n);       // (work items: bands of RH rows)
+    int rc = UOCR_OK;
+    float* partial = uocr_partial_buffer(ctx, (size_t)nblocks * up_ncols(c) * sizeof(float), &rc);
+    if (rc != UOCR_OK) return rc;
+    UOCR_DISPATCH_TA(ctx, c.dtype, {
+        if (cin == 1)
+            hipLaunchKernelGGL((up1_wgrad_kernel<TA>), dim3(strips, bands, n), dim3(256), 0, ctx->stream,
+                               (const TA*)c.x, (const TA*)c.dy, partial, hl, wl, rows);
+        else
+            hipLaunchKernelGGL((upconv_wgrad_kernel<TA>), dim3(strips, bands, n), dim3(256), 0, ctx->stream,
+                               (const TA*)c.x, (const TA*)c.dy, partial, hl, wl, rows);
+    });
+    UOCR_LAUNCH_CHECK(ctx);
+    return up_wgrad_finish(ctx, c, partial, nblocks);
+}
+
+// The ladders of the three entries: the MFMA families first, this file's vector kernels take what is left.  These
+// entries report no kernel (uocr_ctx_last_conv speaks of uocr_conv2d_* calls).
+constexpr ConvRow<UpFwd> UP_FWD_ROWS[] = {{CONV_NOT_NOTED, up_h16_takes, up_h16_run},
+                                          {CONV_NOT_NOTED, uocr_conv_any_takes, up_fwd_vector}};
+constexpr ConvRow<UpDgrad> UP_DGRAD_ROWS[] = {{CONV_NOT_NOTED, up_h16_takes, up_h16_run},
+                                              {CONV_NOT_NOTED, up_t32_takes, up_t32_run},
+                                              {CONV_NOT_NOTED, uocr_conv_any_takes, up_dgrad_vector}};
+constexpr ConvRow<ConvWgrad> UP_WGRAD_ROWS[] = {{CONV_NOT_NOTED, uocr_upconv_wgrad_h16_takes, up_wgrad_h16},
+                                                {CONV_NOT_NOTED, uocr_conv_any_takes, up_wgrad_vector}};
+
 }  // namespace
 
 extern "C" int uocr_upconv2x_fwd(uocr_ctx* ctx, int dtype, const void* x_low, const void* w, const void* b, void* y,
@@ -590,25 +703,8 @@ extern "C" int uocr_upconv2x_fwd(uocr_ctx* ctx, int dtype, const void* x_low, co
     UOCR_REQUIRE(ctx, x_low && w && b && y);
     int rc = check_up(ctx, dtype, n, hl, wl, cin, cout, kh, kw, ph, pw);
     if (rc != UOCR_OK) return rc;
-    if (uocr_upconv_h16_eligible(ctx, dtype, cin, cout) && uocr_aligned_act(x_low, dtype) && uocr_aligned_act(y, dtype))
-        return uocr_upconv_fwd_h16(ctx, x_low, w, b, y, n, hl, wl, use_bias, act, act_alpha);
-    const int strips = (wl + RW - 1) / RW, rows = up_rows_per_block(strips, hl, n, (unsigned)uocr_budget(ctx, 2048));
-    if (cin != 1) uocr_note_split(ctx, (long long)strips * ((hl + rows - 1) / rows) * n, (long long)strips * ((hl + RH - 1) / RH) * n);
-    return uocr_act_tags<0>(ctx, act, UOCR_ACT_NONE, [&](auto kinds) -> int {
-    using K = decltype(kinds);
-    UOCR_DISPATCH_TA(ctx, dtype, {
-        if (cin == 1)
-            hipLaunchKernelGGL((up1_fwd_kernel<TA>), dim3((wl + RW - 1) / RW, (hl + RH - 1) / RH, n), dim3(256), 0,
-                               ctx->stream, (const TA*)x_low, (const float*)w, (const float*)b, (TA*)y, hl, wl, use_bias,
-                               act, (float)act_alpha);
-        else
-            hipLaunchKernelGGL((upconv_fwd_kernel<TA, K>), dim3(strips, (hl + rows - 1) / rows, n), dim3(256), 0,
-                               ctx->stream, (const TA*)x_low, (const float*)w, (const float*)b, (TA*)y, hl, wl, rows,
-                               use_bias, act, (float)act_alpha, (float*)weff);
-    });
-    UOCR_LAUNCH_CHECK(ctx);
-    return UOCR_OK;
-    });
+    const ConvFwd call{dtype, up_dims(n, hl, wl, cin, cout), x_low, w, b, y, 0.0, use_bias, act, act_alpha};
+    return uocr_conv_dispatch(ctx, 0, UP_FWD_ROWS, UpFwd{call, weff});
 }
 
 extern "C" int uocr_upconv2x_bwd_data(uocr_ctx* ctx, int dtype, const void* dy, const void* w, void* dx_low, int n,
@@ -619,33 +715,9 @@ extern "C" int uocr_upconv2x_bwd_data(uocr_ctx* ctx, int dtype, const void* dy, 
     UOCR_REQUIRE(ctx, act == UOCR_ACT_NONE || x_act != nullptr);
     int rc = check_up(ctx, dtype, n, hl, wl, cin, cout, kh, kw, ph, pw);
     if (rc != UOCR_OK) return rc;
-    if (uocr_upconv_h16_eligible(ctx, dtype, cin, cout) && uocr_aligned_act(dy, dtype) &&
-        uocr_aligned_act(dx_low, dtype) && (act == UOCR_ACT_NONE || uocr_aligned_act(x_act, dtype)))
-        return uocr_upconv_dgrad_h16(ctx, dy, w, dx_low, n, hl, wl, act == UOCR_ACT_NONE ? nullptr : x_act, act, act_alpha);
-    if (uocr_upconv_t32_eligible(ctx, dtype, cin, cout) && uocr_aligned16(dy) && uocr_aligned16(dx_low) &&
-        (act == UOCR_ACT_NONE || uocr_aligned16(x_act)))
-        return uocr_upconv_dgrad_t32(ctx, dy, w, dx_low, n, hl, wl, cin, act == UOCR_ACT_NONE ? nullptr : x_act, act, act_alpha);
-    const float* weff = (const float*)weff_in;             // from this layer's forward call with the same w, or null
-    if (cin != 1 && !weff) {
-        rc = uocr_need_workspace(ctx, NWEFF * sizeof(float));
-        if (rc != UOCR_OK) return rc;
-        hipLaunchKernelGGL(upconv_weff_kernel, dim3(1), dim3(256), 0, ctx->stream, (const float*)w, (float*)ctx->workspace);
-        weff = (const float*)ctx->workspace;
-    }
-    const dim3 grid((wl + RW - 1) / RW, (hl + RH - 1) / RH, n);
-    return uocr_act_tags<1>(ctx, UOCR_ACT_NONE, act, [&](auto kinds) -> int {
-    using K = decltype(kinds);
-    UOCR_DISPATCH_TA(ctx, dtype, {
-        if (cin == 1)
-            hipLaunchKernelGGL((up1_dgrad_kernel<TA>), grid, dim3(256), 0, ctx->stream, (const TA*)dy, (const float*)w,
-                               (TA*)dx_low, hl, wl, (const TA*)x_act, act, (float)act_alpha);
-        else
-            hipLaunchKernelGGL((upconv_dgrad_kernel<TA, K>), grid, dim3(256), 0, ctx->stream, (const TA*)dy,
-                               weff, (TA*)dx_low, hl, wl, (const TA*)x_act, act, (float)act_alpha);
-    });
-    UOCR_LAUNCH_CHECK(ctx);
-    return UOCR_OK;
-    });
+    const ActMask mask{act == UOCR_ACT_NONE ? nullptr : x_act, act, act_alpha};
+    const ConvDgrad call{dtype, up_dims(n, hl, wl, cin, cout), dy, w, dx_low, mask};
+    return uocr_conv_dispatch(ctx, 1, UP_DGRAD_ROWS, UpDgrad{call, weff_in});
 }
 
 extern "C" int uocr_upconv2x_bwd_weight(uocr_ctx* ctx, int dtype, const void* x_low, const void* dy, void* dw, void* db,
@@ -655,42 +727,6 @@ extern "C" int uocr_upconv2x_bwd_weight(uocr_ctx* ctx, int dtype, const void* x_
     UOCR_REQUIRE(ctx, x_low && dy && dw && db);
     int rc = check_up(ctx, dtype, n, hl, wl, cin, cout, kh, kw, ph, pw);
     if (rc != UOCR_OK) return rc;
-    const float unscale = (float)uocr_grad_unscale(dtype);
-    const int ncols = cin == 1 ? UP1_NOUT : UP4_NOUT, ndw = ncols - cin;
-    // the block partials are rows of dw and db themselves (up_phase.h); their float64 column sums: recorded when a deferred
-    // group is open (finish_group.h), else one coalesced launch
-    auto finish = [&](const float* partial, int nblocks) -> int {
-        const FinishDesc fd = finish_cols(partial, nblocks, ncols, ndw, (float*)dw, (float*)db, use_bias, accumulate, unscale);
-        return uocr_finish(ctx, fd, [&] {
-            hipLaunchKernelGGL(colsum_finish_kernel, dim3((ncols + 7) / 8), dim3(256), 0, ctx->stream, partial, nblocks,
-                               ncols, ndw, (float*)dw, (float*)db, use_bias, accumulate, unscale);
-        });
-    };
-    if (UOCR_DTYPE_BASE(dtype) == UOCR_F16 && ctx->opt_fast && ctx->opt_h16 && uocr_aligned_act(x_low, dtype) &&
-        uocr_aligned_act(dy, dtype)) {
-        // binary16 MFMAs over channel / phase planes (conv_h16w.hip), same partial rows
-        const size_t floats = (size_t)ctx->cu_count * 8 * ncols;
-        float* partial = uocr_partial_buffer(ctx, floats * sizeof(float), &rc);
-        if (rc != UOCR_OK) return rc;
-        int nblocks = 0;
-        rc = uocr_upconv_wgrad_h16(ctx, x_low, dy, partial, floats, n, hl, wl, cin, &nblocks);
-        if (rc != UOCR_OK) return rc;
-        return finish(partial, nblocks);
-    }
-    // fewer, longer blocks than the forward: every block ends with a reduction and a partial row for the finish kernel
-    const int strips = (wl + RW - 1) / RW, rows = up_rows_per_block(strips, hl, n, (unsigned)uocr_budget(ctx, 1024));
-    const int bands = (hl + rows - 1) / rows, nblocks = strips * bands * n;
-    uocr_note_split(ctx, nblocks, (long long)strips * ((hl + RH - 1) / RH) * n);       // (work items: bands of RH rows)
-    float* partial = uocr_partial_buffer(ctx, (size_t)nblocks * ncols * sizeof(float), &rc);
-    if (rc != UOCR_OK) return rc;
-    UOCR_DISPATCH_TA(ctx, dtype, {
-        if (cin == 1)
-            hipLaunchKernelGGL((up1_wgrad_kernel<TA>), dim3(strips, bands, n), dim3(256), 0, ctx->stream,
-                               (const TA*)x_low, (const TA*)dy, partial, hl, wl, rows);
-        else
-            hipLaunchKernelGGL((upconv_wgrad_kernel<TA>), dim3(strips, bands, n), dim3(256), 0, ctx->stream,
-                               (const TA*)x_low, (const TA*)dy, partial, hl, wl, rows);
-    });
-    UOCR_LAUNCH_CHECK(ctx);
-    return finish(partial, nblocks);
+    return uocr_conv_dispatch(ctx, 2, UP_WGRAD_ROWS,
+                              ConvWgrad{dtype, up_dims(n, hl, wl, cin, cout), x_low, dy, dw, db, 0.0, use_bias, accumulate});
 }

@@ -1150,36 +1150,40 @@ int uocr_gemm_mfma(uocr_ctx* ctx, const GemmArgs& g) {
     return launch_mfma(ctx, A, B, ep, g.m, g.n, g.depth, true);
 }
 
-bool uocr_conv_mfma_eligible(uocr_ctx* ctx, int dtype, const ConvDims& d, int which /*0 fwd, 1 dgrad, 2 wgrad*/) {
+// depth_ch: the channel count along the GEMM's depth, which must fill its tiles (forward cin, backward-data cout, else 0)
+static bool conv_mfma_shape(uocr_ctx* ctx, int dtype, const ConvDims& d, int depth_ch) {
     if (dtype != UOCR_F32 || ctx->opt_mfma == 0) return false;
-    if (d.cout % 4 || d.cin % 4) return false;
-    if (which == 0 && d.cin % BD) return false;
-    if (which == 1 && d.cout % BD) return false;
-    if (which == 1 && (size_t)d.kh * d.kw * d.cin * d.cout * sizeof(float) > ws_half(ctx)) return false;
-    if (ctx->opt_mfma == 2) return true;
-    return d.cin >= 16 && d.cout >= 16;
+    if (d.cout % 4 || d.cin % 4 || depth_ch % BD) return false;
+    return ctx->opt_mfma == 2 || (d.cin >= 16 && d.cout >= 16);
 }
 
-int uocr_conv_fwd_mfma(uocr_ctx* ctx, const void* x, const void* w, const void* b, void* y, const ConvDims& d,
-                       double pad_value, int use_bias, int act, double act_alpha) {
+bool uocr_conv_mfma_takes(uocr_ctx* ctx, const ConvFwd& c) { return conv_mfma_shape(ctx, c.dtype, c.d, c.d.cin); }
+bool uocr_conv_mfma_takes(uocr_ctx* ctx, const ConvDgrad& c) {
+    return conv_mfma_shape(ctx, c.dtype, c.d, c.d.cout) &&
+           (size_t)c.d.kh * c.d.kw * c.d.cin * c.d.cout * sizeof(float) <= ws_half(ctx);       // (the weights, transposed)
+}
+bool uocr_conv_mfma_takes(uocr_ctx* ctx, const ConvWgrad& c) { return conv_mfma_shape(ctx, c.dtype, c.d, 0); }
+
+int uocr_conv_mfma_run(uocr_ctx* ctx, const ConvFwd& c) {
+    const ConvDims& d = c.d;
     const int M = d.n * d.oh * d.ow, K = d.kh * d.kw * d.cin;
-    AConvFwd A((const float*)x, d, (float)pad_value, M);
-    BRowMajor B{(const float*)w, d.cout, K, d.cout, aligned16(w) ? 1 : 0};
-    Epilogue ep{(float*)y, d.cout, use_bias ? (const float*)b : nullptr, act, (float)act_alpha, 0, -1, nullptr,
-                nullptr,    UOCR_ACT_NONE, 0.f};
+    AConvFwd A((const float*)c.x, d, (float)c.pad_value, M);
+    BRowMajor B{(const float*)c.w, d.cout, K, d.cout, aligned16(c.w) ? 1 : 0};
+    Epilogue ep{(float*)c.y, d.cout, c.use_bias ? (const float*)c.b : nullptr, c.act, (float)c.act_alpha, 0, -1, nullptr,
+                nullptr,      UOCR_ACT_NONE, 0.f};
     return launch_mfma(ctx, A, B, ep, M, d.cout, K, (size_t)M * d.cout * 4 * 8 <= ws_half(ctx));
 }
 
-int uocr_conv_dgrad_mfma(uocr_ctx* ctx, const void* dy, const void* w, void* dx, const ConvDims& d,
-                         const ActMask& mask) {
+int uocr_conv_mfma_run(uocr_ctx* ctx, const ConvDgrad& c) {
+    const ConvDims& d = c.d;
     const int M = d.n * d.h * d.w, D = d.kh * d.kw * d.cout;
     // B((kk, oc), ic) = w[(kk * cin + ic) * cout + oc]: the weights as they lie in memory, read along oc
-    AConvDgrad A((const float*)dy, d, M);
-    BDepthContig B{(const float*)w, d.cout, d.cin, D, d.cin, FastDiv(d.cout), aligned16(w) ? 1 : 0};
-    Epilogue ep = plain_epilogue((float*)dx, d.cin, 0);
-    ep.mask_y = (const float*)mask.y;
-    ep.mask_act = mask.act;
-    ep.mask_alpha = (float)mask.alpha;
+    AConvDgrad A((const float*)c.dy, d, M);
+    BDepthContig B{(const float*)c.w, d.cout, d.cin, D, d.cin, FastDiv(d.cout), aligned16(c.w) ? 1 : 0};
+    Epilogue ep = plain_epilogue((float*)c.dx, d.cin, 0);
+    ep.mask_y = (const float*)c.mask.y;
+    ep.mask_act = c.mask.act;
+    ep.mask_alpha = (float)c.mask.alpha;
     // A strided transposed conv only meets the tap rows ky with (iy + ph - ky) % sh == 0 and an output row inside the
     // image; the kernel skips the depth tiles of the others.  When few tiles per block are live, a depth split only
     // adds slabs of zeros and a reduce launch (Char conv_3, 5 x 3 stride (2, 1) on 5 rows: 1 of 5 tap rows live,
@@ -1195,20 +1199,21 @@ int uocr_conv_dgrad_mfma(uocr_ctx* ctx, const void* dy, const void* w, void* dx,
     return launch_mfma(ctx, A, B, ep, M, d.cin, D, split_ok);
 }
 
-int uocr_conv_wgrad_mfma(uocr_ctx* ctx, const void* x, const void* dy, void* dw, void* db, const ConvDims& d,
-                         double pad_value, int use_bias, int accumulate) {
+int uocr_conv_mfma_run(uocr_ctx* ctx, const ConvWgrad& c) {
+    const ConvDims& d = c.d;
+    const int use_bias = c.use_bias;
     const int K = d.kh * d.kw * d.cin, P = d.n * d.oh * d.ow;
     const int M = K + (use_bias ? 1 : 0);
     const int cursor_ok = d.ow >= BD && (long)(d.n + 1) * d.h * d.w * d.cin < (1l << 31) - (long)d.kh * d.w * d.cin;
-    AConvWgrad A{(const float*)x, d, (float)pad_value, K, use_bias, P, FastDiv(d.ow), FastDiv(d.oh), cursor_ok};
-    BRowMajor B{(const float*)dy, d.cout, P, d.cout, aligned16(dy) ? 1 : 0};
-    Epilogue ep{(float*)dw, d.cout, nullptr, UOCR_ACT_NONE, 0.f, accumulate, use_bias ? K : -1, (float*)db,
-                nullptr,    UOCR_ACT_NONE, 0.f};
+    AConvWgrad A{(const float*)c.x, d, (float)c.pad_value, K, use_bias, P, FastDiv(d.ow), FastDiv(d.oh), cursor_ok};
+    BRowMajor B{(const float*)c.dy, d.cout, P, d.cout, aligned16(c.dy) ? 1 : 0};
+    Epilogue ep{(float*)c.dw, d.cout, nullptr, UOCR_ACT_NONE, 0.f, c.accumulate, use_bias ? K : -1, (float*)c.db,
+                nullptr,      UOCR_ACT_NONE, 0.f};
     if (!defer_record(ctx, A, B, ep, M, d.cout, P)) {
         int rc = launch_mfma(ctx, A, B, ep, M, d.cout, P, true);
         if (rc) return rc;
     }
-    if (!use_bias && !accumulate) UOCR_HIP(ctx, hipMemsetAsync(db, 0, (size_t)d.cout * sizeof(float), ctx->stream));
+    if (!use_bias && !c.accumulate) UOCR_HIP(ctx, hipMemsetAsync(c.db, 0, (size_t)d.cout * sizeof(float), ctx->stream));
     return UOCR_OK;
 }
 

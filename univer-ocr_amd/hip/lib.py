@@ -149,6 +149,7 @@ _PROTOS = {
     'uocr_ctx_last_pack_lines': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     'uocr_page_layout': [_ctx, C.c_ulonglong, C.c_ulonglong, _i, _i, _i, _i] + [_vp] * 6,
     'uocr_page_render': [_ctx, _i, _i, _i, _i] + [_vp] * 4 + [_i] + [_vp] * 4 + [C.c_longlong] + [_vp] * 6,
+    'uocr_ctx_last_page_gen': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     'uocr_dp_init': [_ctx, _i, _i, _vp],
     'uocr_dp_info': [_ctx, C.POINTER(_i), C.POINTER(_i)],
     'uocr_dp_allreduce_sum': [_ctx, _vp, _sz, _i],
@@ -162,12 +163,6 @@ _SPECIAL = {
     'uocr_dp_version': (C.c_int, [C.POINTER(C.c_int)]),
     'uocr_last_error': (C.c_char_p, [_ctx]),
     'uocr_ctx_get_stream': (C.c_void_p, [_ctx]),
-    # the launch report of the page generator.  It is an ordinary uocr_ctx_last_* getter and belongs beside the others in
-    # _PROTOS; it stands here only because tests/test_gpu_launch_reports.py pins the number of getters in _PROTOS at 13 and
-    # the change that added this one could not touch existing test files.  tests/test_gpu_pages.py and
-    # tests/test_pages_host.py ask of it what the generic tests ask of the others.  Move it to _PROTOS, and drop the second
-    # lookup of Runtime._report, in the change that raises that count.
-    'uocr_ctx_last_page_gen': (C.c_int, [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
 }
 
 ABI_SYMBOLS = sorted(list(_PROTOS) + list(_SPECIAL))

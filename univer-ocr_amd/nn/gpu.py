@@ -184,8 +184,7 @@ class Runtime:
     def _report(self, symbol):
         """The values of the launch report `symbol` (a uocr_ctx_last_* getter) on the current lane: one out parameter per
         POINTER(T) that its prototype in hip.lib declares after the context."""
-        protos = hiplib._PROTOS[symbol] if symbol in hiplib._PROTOS else hiplib._SPECIAL[symbol][1]
-        outs = [pointer._type_() for pointer in protos[1:]]
+        outs = [pointer._type_() for pointer in hiplib._PROTOS[symbol][1:]]
         self.call(symbol, *[C.byref(out) for out in outs])
         return tuple(out.value for out in outs)
 
