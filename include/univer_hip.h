@@ -585,6 +585,38 @@ int uocr_pred_to_text(uocr_ctx* ctx, int dtype, int n_lines, const void* const* 
  * (all 0 before the first call) -- tests size their inputs from it */
 int uocr_ctx_last_pred_to_text(uocr_ctx* ctx, int* rows_per_block, int* lines_per_launch, int* launches);
 
+/* ---- text score: how well the lines of a page were read (no counterpart in the reference, whose nn/metrics.py is a
+ * stub) ----
+ * Line i is pred[i]: (w[i], n_chars) in `dtype`, the Char net's raw output, and label[i]: (w[i], n_chars) in `dtype`,
+ * the one-hot labels of the same columns (uocr_char_label).  Both are read by ONE rule.  The id of a row is -1 where the
+ * row holds a NaN or its maximum == 0.0 (-0.0 included), otherwise the SMALLEST column that equals the row's maximum (a
+ * negative maximum is a maximum like any other): uocr_pred_to_text's conventions with the first candidate taken.  The
+ * reading of a matrix is one id per run of equal row ids; id 0 (the tab, the background class) and -1 emit nothing and
+ * end a run: row r contributes iff id[r] > 0 and (r == 0 or id[r] != id[r-1]).  The score of the line is the unit-cost
+ * Levenshtein distance between reading(label[i]), the EXPECTED string, and reading(pred[i]), the READ string, where ids
+ * x and y match when canon[x] == canon[y] -- the library knows no alphabet; the identity table compares ids.
+ * scores: DEVICE int32 (n_lines, 4): distance, length of the expected string, length of the read string, 0.
+ * read_ids / expected_ids: optional (either may be NULL) HOST arrays of n_lines device pointers to uint8 buffers of
+ * w[i] bytes -- a reading is never longer than w[i], so there is no capacity and never a second call; the ids of the
+ * reading are written from byte 0 on and nothing behind them.  pred, label, w and canon (n_chars entries) are HOST
+ * arrays; pred[i], label[i] are device pointers.
+ * Limits: 1 <= n_chars <= 255, 1 <= w[i] <= max_width of uocr_text_score_limits, 0 <= canon[k] < n_chars (UOCR_ERR_ARG
+ * otherwise, as for null pointers, pred[i] / label[i] / scores off their element's alignment and n_lines < 0);
+ * UOCR_ERR_DTYPE for an unknown dtype; UOCR_ERR_UNSUPPORTED for more rows than one grid takes.  Nothing is written on any
+ * error; n_lines = 0 is UOCR_OK and launches nothing (the other arguments are not looked at).  Two launches per
+ * lines_per_launch lines; of the ctx workspace 2 bytes per row rounded up to rows_per_block rows per matrix plus
+ * 12 * w[i] + 8 bytes per line of the largest launch (UOCR_ERR_WORKSPACE).  Comparisons and integer arithmetic only: no
+ * tolerance in any dtype.  No atomics: results are bit-identical run to run.  Asynchronous and capturable.  The call
+ * leaves no launch report. */
+int uocr_text_score(uocr_ctx* ctx, int dtype, int n_lines, const void* const* pred, const void* const* label, const int* w,
+                    int n_chars, const int* canon, unsigned char* const* read_ids, unsigned char* const* expected_ids,
+                    int* scores);
+/* the sizes uocr_text_score works with, whatever the context: rows of a matrix per block of the reading kernel, lines per
+ * launch pair, columns of the expected string per panel of the distance kernel (64 lanes x the most columns per lane; a
+ * string of up to 64 K columns runs with K = 1, 2, 4 columns per lane), the widest line it takes.  UOCR_ERR_ARG for a
+ * null pointer, before anything is written -- tests size their inputs from it */
+int uocr_text_score_limits(int* rows_per_block, int* lines_per_launch, int* columns_per_panel, int* max_width);
+
 /* ---- the lines of a page in one strip (the Char net over all lines in one pass; the reference runs a pass per line,
  * nn/model_system.py:150-154) ----
  * A strip is (1, h, strip_w, c) in `dtype`; its columns are cut into SEGMENTS [x0[i], x0[i] + w[i]), i < n_lines, with GAPS

@@ -54,6 +54,13 @@ candidates (the remembered character always lies in the pair class of the last c
 lines of all paragraphs of a page in ONE kernel call (nn/ops.py: pred_to_text), a second one only for lines with tied
 rows; the host reads back the ids and nothing else.  The reference copies every prediction to the host and hands it to
 a worker pool.
+
+ScoreText has no counterpart in the reference (its nn/metrics.py is a stub): per line, the Char net's raw output and the
+one-hot labels of the same columns are read by ONE rule -- the first maximum of every row, one id per run of equal ids,
+the tab and rows without a maximum end a run -- and compared by the unit-cost edit distance, two ids matching when the
+table `canonical_ids` maps them to one id (by default the halves of a look-alike pair, whose glyphs the generator draws
+from the same pixels).  All lines of a page are ONE kernel call (nn/ops.py: text_score) and one readback of the scores
+and ids; DESIGN.md section 8 says why the score is not taken between context['text'] and the typed text.
 """
 import string
 
@@ -369,3 +376,33 @@ class PredToText:
         flat = [ops.as_device(line) for paragraph in predictions for line in paragraph]
         texts = iter(''.join(self.chars[i] for i in ids) for ids in ops.pred_to_text(flat, self.cls))
         return [[next(texts) for _ in paragraph] for paragraph in predictions]
+
+
+def canonical_ids(pairs=SIMILAR_PAIRS, n_chars=len(CHARS), similar=True):
+    """canon[id] for ScoreText: the id itself, and with similar=True the Cyrillic member of its look-alike pair for both
+    members: two ids match when their entries are equal"""
+    canon = np.arange(n_chars, dtype=np.int32)
+    if similar:
+        for cyrillic, latin in pairs:
+            canon[latin] = cyrillic
+    return canon
+
+
+class ScoreText:
+    def __init__(self, chars=CHARS, pairs=SIMILAR_PAIRS, similar=True):
+        self.chars, self.canon = chars, canonical_ids(pairs, len(chars), similar)
+
+    def __call__(self, predictions, labels):
+        """predictions[paragraph][line], labels[paragraph][line]: (W, n_chars) DeviceArrays, the Char net's raw output and
+        the labels of the same columns.  Returns (scores, read_text, expected_text) in the same nesting: per line the
+        ints (distance, expected length, read length) and the two readings as str (a paragraph without lines stays [],
+        a page without paragraphs []); one kernel call and one readback for the page."""
+        if [len(paragraph) for paragraph in predictions] != [len(paragraph) for paragraph in labels]:
+            raise ValueError(f'ScoreText: predictions for {[len(p) for p in predictions]} lines per paragraph, labels for '
+                             f'{[len(p) for p in labels]}')
+        flat = lambda nested: [ops.as_device(line) for paragraph in nested for line in paragraph]
+        scores, read, expected = ops.text_score(flat(predictions), flat(labels), self.canon, want_ids=True)
+        text = lambda ids: ''.join(self.chars[i] for i in ids)
+        rows = iter(zip((tuple(int(v) for v in row) for row in scores), map(text, read), map(text, expected)))
+        nested = [[next(rows) for _ in paragraph] for paragraph in predictions]
+        return tuple([[line[k] for line in paragraph] for paragraph in nested] for k in range(3))

@@ -1,0 +1,91 @@
+"""How well a page was read: the systems of my_model/model.py: make_evaluate_system over the pages of a generator, the
+scores of all lines added up (the reference has nothing of the kind: its nn/metrics.py is a stub).  The character error
+rate is the edit distance between what the labels of the crops say and what the Char net read, over the length of the
+former; `coverage` says how much of the typed text the crop stages found at all, which the error rate alone would hide.
+
+    python -m univer_ocr_amd.my_model.evaluate [--weights model_weights.json] [--pages 8] [--seed 1234]
+        [--height 256 --width 512] [--predicted-crops] [--distinct-look-alikes] [--device-search] [--page-line-labels]
+        [--page-char-pass]
+"""
+import json
+from collections import namedtuple
+
+from .model import CHAR_INPUT_HEIGHT, make_evaluate_context_maker, make_evaluate_system
+
+TextReport = namedtuple('TextReport', 'pages lines exact_lines typed_chars expected_chars read_chars distance cer coverage')
+
+
+def load_evaluate_system(input_shape, weights_path=None, crops='true', **options):
+    """make_evaluate_system with the weights of `weights_path` (a model_weights.json); a missing file, or none, leaves the
+    fresh weights in place (as my_model/predict.py: load_model_system)"""
+    weights = {}
+    if weights_path is not None:
+        try:
+            with open(weights_path) as fp:
+                weights = json.load(fp)
+        except OSError:
+            print(f'No {weights_path} file found')
+    return make_evaluate_system(input_shape, weights=weights, crops=crops, **options)[0]
+
+
+def evaluate_text(pages, n_pages, model_system=None, weights_path=None, crops='true', contexts=None, **options):
+    """Pages 0 .. n_pages - 1 of `pages`, a PagesWithText, through `model_system` (default: load_evaluate_system for the
+    pages' size, `options` to make_evaluate_system), one `predict` per page.  Returns the TextReport of all their lines:
+    typed_chars from pages.texts(i), expected_chars / read_chars / distance the sums of the lines' scores, exact_lines
+    the lines at distance 0, cer = distance / expected_chars (None where that is 0), coverage = expected_chars /
+    typed_chars (None where that is 0).  contexts: a list that receives every page's context."""
+    height, width = pages.source.height, pages.source.width
+    if crops == 'predicted' and (height % 16 or width % 16):
+        raise ValueError(f'evaluate_text: the nets take pages whose sides are multiples of 16, got {height} x {width}')
+    if model_system is None:
+        shape = (1, CHAR_INPUT_HEIGHT, 64, 1) if crops == 'true' else (1, height, width, 1)
+        model_system = load_evaluate_system(shape, weights_path, crops, **options)
+    make_context = make_evaluate_context_maker(crops)
+    lines = exact = typed = expected = read = distance = 0
+    for index in range(int(n_pages)):
+        context = make_context(pages.get, (index,))
+        model_system.predict(context)
+        if contexts is not None:
+            contexts.append(context)
+        typed += sum(len(line) for paragraph in pages.texts(index) for line in paragraph)
+        for d, n_expected, n_read in (score for paragraph in context['text_scores'] for score in paragraph):
+            lines, exact = lines + 1, exact + (d == 0)
+            expected, read, distance = expected + n_expected, read + n_read, distance + d
+    return TextReport(int(n_pages), lines, exact, typed, expected, read, distance,
+                      distance / expected if expected else None, expected / typed if typed else None)
+
+
+def main(argv=None):
+    import argparse
+
+    from ..nn.gpu import CP
+    from .pages import GeneratedPages, PagesWithText
+    parser = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    parser.add_argument('--weights', default=None, help='model_weights.json (default: fresh weights)')
+    parser.add_argument('--pages', type=int, default=8, help='pages with text to read')
+    parser.add_argument('--seed', type=int, default=1234, help='the stream of the page generator')
+    parser.add_argument('--height', type=int, default=256)
+    parser.add_argument('--width', type=int, default=512)
+    parser.add_argument('--predicted-crops', action='store_true',
+                        help='end to end: paragraphs and lines as the nets find them, not the true layers')
+    parser.add_argument('--distinct-look-alikes', action='store_true',
+                        help='the halves of a Cyrillic / Latin look-alike pair count as different characters')
+    parser.add_argument('--device-search', action='store_true',
+                        help='the angle search of the paragraphs in one call on the device, not round by round on the host')
+    parser.add_argument('--page-line-labels', action='store_true',
+                        help='the line masks of all paragraphs of the page labelled in one call, not paragraph by paragraph')
+    parser.add_argument('--page-char-pass', action='store_true',
+                        help='the Char net once per page on all lines laid side by side, not once per line')
+    args = parser.parse_args(argv)
+    CP.use_gpu()
+    pages = PagesWithText(GeneratedPages(1, args.height, args.width, seed=args.seed, length=args.pages), args.pages)
+    report = evaluate_text(pages, args.pages, weights_path=args.weights, crops='predicted' if args.predicted_crops else 'true',
+                           rotation_search='device' if args.device_search else 'host',
+                           line_labelling='page' if args.page_line_labels else 'paragraph',
+                           char_batching='page' if args.page_char_pass else 'line', similar=not args.distinct_look_alikes)
+    print(json.dumps(report._asdict()))
+    return report
+
+
+if __name__ == '__main__':
+    main()

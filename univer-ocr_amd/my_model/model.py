@@ -17,6 +17,8 @@ the upright crop; `rotation_search='device'` lets the device walk that search, o
 `make_predict_system` chains the four nets through the device stages -- a page goes in, text comes out
 (my_model/predict.py) -- with the rotation search on, as the reference has it in that mode.  The PREDICT,
 TRAIN_CHAR and TRAIN_ALL members of `Modes` are not routed through `make_model_system` and say where their systems are.
+`make_evaluate_system` puts CharLabel in front of Char and TextScore behind PredToText in either chain: what the Char
+net read, scored against the labels that travel with the crops (my_model/evaluate.py adds the lines up).
 """
 from enum import Enum
 
@@ -236,6 +238,29 @@ def make_pred_to_text_component(progress_tracker=None, source='char_pred', targe
         context[target] = pred_to_text(predictions)
 
     return RawFunctionComponent(to_text)
+
+
+def make_text_score_component(progress_tracker=None, pred='char_pred', labels='char_labels', target='text_scores',
+                              read='read_text', expected='expected_text', lines=None, similar=True):
+    """No counterpart in the reference: context[pred][paragraph][line], the Char net's raw outputs, are scored against
+    context[labels][paragraph][line], the labels of the same columns: context[target][p][l] = (distance, expected
+    length, read length), context[read][p][l] and context[expected][p][l] the two readings as str, in one kernel call and
+    one readback for the page (my_model/crop.py: ScoreText).  A page without a line never reaches the Char net, so
+    context[pred] is missing there: everything is [].  lines: as in make_pred_to_text_component, the label of the nested
+    list of line crops -- one entry per paragraph of context[lines], [] for the paragraphs without lines at the end of
+    the page.  similar: the halves of a look-alike pair count as one character (my_model/crop.py: canonical_ids)."""
+    from .crop import ScoreText
+    score_text = ScoreText(similar=similar)
+
+    @track_function('TextScore', 'forward', progress_tracker)
+    def text_score(context):
+        predictions = list(context.get(pred, []))
+        if lines is not None:
+            predictions += [[] for _ in range(len(context[lines]) - len(predictions))]
+        truth = list(context.get(labels, []))[:len(predictions)] if predictions else []
+        context[target], context[read], context[expected] = score_text(predictions, truth)
+
+    return RawFunctionComponent(text_score, score_text)
 
 
 def make_paragraph_crop_component(find_rotation=False, progress_tracker=None, sources=('monochrome_pred', 'line'),
@@ -559,3 +584,68 @@ def make_predict_system(input_shape, progress_tracker=None, weights=None, find_r
                   net['Char'], make_pred_to_text_component(progress_tracker, lines='cropped_2_monochrome')]
     return (ModelSystem(components), models,
             ['Monochrome', 'Paragraph', 'ParagraphCrop', 'Line', 'LineCrop', 'Char', 'PredToText'])
+
+
+EVALUATE_NAMES = {'true': ['ParagraphCrop', 'LineCrop', 'CharLabel', 'Char', 'PredToText', 'TextScore'],
+                  'predicted': ['Monochrome', 'Paragraph', 'ParagraphCrop', 'Line', 'LineCrop', 'CharLabel', 'Char',
+                                'PredToText', 'TextScore']}
+
+
+def make_evaluate_context_maker(crops):
+    """the context of make_evaluate_system(crops=...) from one page of a dataset: with 'true' the label layers the crop
+    stages read (the TRAIN_CHAR context), with 'predicted' the image, as in PREDICT, and the `char` layer that rides
+    through the crop stages beside it"""
+    if crops not in EVALUATE_NAMES:
+        raise ValueError(f"make_evaluate_context_maker: crops must be 'true' or 'predicted', got {crops!r}")
+    if crops == 'true':
+        return make_train_char_context_maker()
+    return _context_maker({'monochrome_X': 'image', 'char': 'char'})
+
+
+def make_evaluate_system(input_shape, progress_tracker=None, weights=None, crops='true', find_rotation=None,
+                         rotation_search='host', line_labelling='paragraph', char_batching='line', similar=True):
+    """What the Char net reads, scored against the labels that travel with the crops.  Returns (model_system, models,
+    names); run it with `predict`: context['text_scores'][p][l] = (distance, expected length, read length),
+    context['read_text'][p][l], context['expected_text'][p][l] and, as in PREDICT, context['text'][p][l].
+      crops='true'       the Char net alone: the TRAIN_CHAR chain on the page's true layers (make_train_char_system),
+                         [ParagraphCrop, LineCrop, CharLabel, Char, PredToText, TextScore]; input_shape is the Char
+                         net's; find_rotation defaults to False, as there
+      crops='predicted'  end to end: the PREDICT chain (make_predict_system) with `char` among the sources of
+                         ParagraphCrop and LineCrop and CharLabel in front of Char, [Monochrome, Paragraph,
+                         ParagraphCrop, Line, LineCrop, CharLabel, Char, PredToText, TextScore]; input_shape is the
+                         page's; find_rotation defaults to True, as there
+    The labels are cut, turned and zoomed by the same boxes as the pixels the net sees, so label and prediction cover the
+    same columns whatever the crop stages found.  rotation_search, line_labelling, char_batching: as in
+    make_predict_system; similar: as in make_text_score_component."""
+    if crops not in EVALUATE_NAMES:
+        raise ValueError(f"make_evaluate_system: crops must be 'true' or 'predicted', got {crops!r}")
+    if char_batching not in ('line', 'page'):
+        raise ValueError(f"make_evaluate_system: char_batching must be 'line' or 'page', got {char_batching!r}")
+    find_rotation = (crops == 'predicted') if find_rotation is None else find_rotation
+    char_shape = input_shape if crops == 'true' else (input_shape[0], CHAR_INPUT_HEIGHT, 64, 1)
+    shapes = {'Char': char_shape} if crops == 'true' else {'Monochrome': input_shape, 'Paragraph': input_shape,
+                                                           'Line': input_shape, 'Char': char_shape}
+    models = {name: _make_net(name, shape, None, progress_tracker, weights) for name, shape in shapes.items()}
+    selector = CharSelector('cropped_2_monochrome', None, 'char_pred')
+    char = (PackedLinesComponent if char_batching == 'page' else ModelComponent)('Char', models['Char'], selector,
+                                                                                delist_result=True)
+    tail = [make_char_label_component(progress_tracker), char,
+            make_pred_to_text_component(progress_tracker, lines='cropped_2_monochrome'),
+            make_text_score_component(progress_tracker, lines='cropped_2_monochrome', similar=similar)]
+    if crops == 'true':
+        head = [make_paragraph_crop_component(find_rotation, progress_tracker, ('monochrome_pred', 'line', 'char'),
+                                              ('cropped_monochrome', 'cropped_line', 'cropped_char'), rotation_search),
+                make_line_crop_component(progress_tracker, line_labelling=line_labelling)]
+    else:
+        net = {name: ModelComponent(name, models[name], sel, delist_result=True) for name, sel in (
+            ('Monochrome', StringSelector('monochrome_X', None, 'monochrome_pred')),
+            ('Paragraph', StringSelector('monochrome_pred', None, 'paragraph_pred')),
+            ('Line', LineSelector('cropped_monochrome', None, 'line_pred')))}
+        head = [net['Monochrome'], net['Paragraph'],
+                make_paragraph_crop_component(find_rotation, progress_tracker, ('monochrome_pred', 'char'),
+                                              ('cropped_monochrome', 'cropped_char'), rotation_search),
+                net['Line'],
+                make_line_crop_component(progress_tracker, 'line_pred', ('cropped_monochrome', 'cropped_char'),
+                                         ('cropped_2_monochrome', 'cropped_2_char'), empty_page_ok=True,
+                                         line_labelling=line_labelling)]
+    return ModelSystem(head + tail), models, list(EVALUATE_NAMES[crops])

@@ -959,6 +959,45 @@ def pred_to_text(lines, cls):
     return [v.tolist() for v in ids]
 
 
+# ---- score of the lines: what the Char net read against the labels (no counterpart in the reference) --------------------
+def text_score(preds, labels, canon, want_ids=False):
+    """The edit distance between what the labels say and what the Char net read, for every line: preds and labels are flat
+    lists of (W, n_chars) DeviceArrays of one dtype, preds[i] the net's raw output and labels[i] the one-hot labels of the
+    same W columns.  Both are read by one rule (the first maximum of every row, none where it is 0 or the row holds a
+    NaN; one id per run of equal ids, the tab ends a run) and compared at unit cost, ids x and y matching when
+    canon[x] == canon[y].  Returns int32 (n, 3): distance, length of the expected reading, length of the read one; with
+    want_ids=True also the two readings, (scores, read ids per line, expected ids per line) as lists of ints.  ONE
+    uocr_text_score call and ONE device-to-host copy -- scores and ids share a buffer -- and no call for an empty list."""
+    preds, labels = list(preds), list(labels)
+    if len(preds) != len(labels):
+        raise ValueError(f'text_score: {len(preds)} predictions for {len(labels)} labels')
+    for a in preds + labels:
+        if not isinstance(a, DeviceArray) or a.ndim != 2 or a.shape[0] < 1:
+            raise ValueError(f'text_score: expected (W, n_chars) device arrays, got {getattr(a, "shape", type(a))}')
+    if not preds:
+        return (np.zeros((0, 3), np.int32), [], []) if want_ids else np.zeros((0, 3), np.int32)
+    canon = [int(v) for v in canon]
+    for pred, label in zip(preds, labels):
+        if pred.shape != label.shape or pred.shape[1] != len(canon):
+            raise ValueError(f'text_score: prediction {pred.shape} and labels {label.shape} of a line have one shape, '
+                             f'(W, {len(canon)}) for a table of {len(canon)} entries')
+    code = _shared_code(preds + labels, 'text_score', 'a dtype')
+    n, widths = len(preds), [a.shape[0] for a in preds]
+    starts = 16 * n + np.concatenate([[0], np.cumsum(widths + widths)]).astype(np.int64)
+    out = CP.empty((int(starts[-1]) if want_ids else 16 * n,), np.uint8)
+    address = lambda offsets: (C.c_void_p * n)(*[out.ptr + int(o) for o in offsets]) if want_ids else None
+    _rt().call('uocr_text_score', code, n, _pointers(preds), _pointers(labels), _ints(widths), len(canon), _ints(canon),
+               address(starts[:n]), address(starts[n:2 * n]), out.ptr)
+    host = out.numpy()
+    table = host[:16 * n].view(np.int32).reshape(n, 4)
+    scores = table[:, :3].copy()
+    if not want_ids:
+        return scores
+    read = [host[s:s + count].tolist() for s, count in zip(starts[:n], table[:, 2])]
+    expected = [host[s:s + count].tolist() for s, count in zip(starts[n:2 * n], table[:, 1])]
+    return scores, read, expected
+
+
 # ---- line crops (interpreter/interpreter.py:504-523: the gather half of LineCrop) -------------------------------------
 def line_crop_shape(box_h, box_w, quarter_turns, zoomed_height=32, minimal_width=8):
     """(zoom_h, zoom_w, out_w) of a box_h x box_w box after `quarter_turns` turns of 90 degrees, ndimage.zoom by
