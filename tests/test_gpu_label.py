@@ -243,6 +243,36 @@ def test_threshold_rules_at_the_tile_size(tile_size, rt):
                 assert np.array_equal(table[i, :count[i]], exp_table), f'{dtype}/{rule}'
 
 
+def test_statistics_hand_off_three_calls_in_a_row(tile_size, rt):
+    """The statistics launch hands its block sums to the last block to arrive through a counter that must be back at zero
+    for the next call.  Three `mean_max` calls on one runtime, the outputs filled with a sentinel before each (label_raw):
+    every call equals the flood fill at the float64 threshold and all three have the same bits.  A counter left non-zero
+    would leave the threshold unwritten -- a failed comparison, nothing waits.  So that an unwritten threshold cannot be
+    the previous call's (equal) value, a larger all-foreground image is labelled with the `value` rule in between: no
+    statistics launch, and its root plane (all zero) lies over the smaller call's workspace."""
+    h, w = tile_size
+    x = np.random.default_rng(11).random((2, h, w))
+    t = threshold_of(x, 'mean_max')
+    x[np.abs(x - t) < 5e-3] += 0.02
+    x = x.astype(np.float32)
+    t = threshold_of(x, 'mean_max')
+    assert np.min(np.abs(x.astype(np.float64) - t)) > 1e-3
+    expected = [flood_fill(x[i].astype(np.float64) > t) for i in range(2)]
+    assert all(len(exp_table) > 1 for _, exp_table in expected)
+    results = []
+    for call in range(3):
+        labels, table, count = label_raw(rt, x, 'mean_max')
+        for i, (exp_labels, exp_table) in enumerate(expected):
+            assert count[i] == len(exp_table) and np.array_equal(labels[i], exp_labels), f'call {call}, image {i}'
+            assert np.array_equal(table[i, :count[i]], exp_table), f'call {call}, image {i}'
+        results.append((labels, table, count))
+        _, _, big_count = label_raw(rt, np.ones((1, 3 * h, 3 * w), np.float32))
+        assert big_count[0] == 1
+    for again in results[1:]:
+        for a, b in zip(results[0], again):
+            assert a.tobytes() == b.tobytes()
+
+
 def test_capture_and_replay(tile_size, rt):
     """both calls are asynchronous and capturable: a replayed graph labels and crops what the buffers hold then"""
     import torch

@@ -16,7 +16,7 @@ kernel's own arithmetic is judged.  What each case is for:
 | Adam / Momentum / RMSProp | 1, 3, 4, 5, 1027, 300 001, cap + 5 | Adam's vector body (4 float32 / 2 float64) with a tail behind the 2048-block cap, the scalar kernels past theirs, unaligned views with guards |
 | fused Momentum / Adam tails | 5003, 262 144 * 4 + 7 with four ranges, 1024 * 1024 + 4099 without | ranges that begin and end inside a vector, adjacent and empty ranges, L1 at weights of exactly 0, zero_grad on and off, hyper-parameters from device memory, the 256-block (ranges) and 1024-block caps with further trips, the last block's sum over 256 blocks of partials, VEC = 1 for views |
 | regularize | 60, 1025, 600 001 | `reg_kernel` past its 512-block cap, `finish_sum_kernel` over 512 partials, accumulation into gradient and loss slot |
-| softmax CE | (4100, 162), (8200, 100), (16400, 37); c in 1 .. 700 at m = 37 | more than 1024 blocks (the strided branch of `last_block_sum`), every lane-group width and more than 4 trips of 64 lanes, rows with a large common offset |
+| softmax CE | (4100, 162), (8200, 100), (16400, 37); c in 1 .. 700 at m = 37 | more than 1024 blocks (the strided walk of `last_block_fold` past its first 4 rows per thread), every lane-group width and more than 4 trips of 64 lanes, rows with a large common offset |
 | sigmoid CE | 525 313 elements | the 512-block cap |
 | Dice / Jaccard | (1, 768, 768, 1), (1, 1024, 1100, 2), (2, 130, 130, 4), (2, 97, 101, 3), (2, 95, 97, 1), binary16 (1, 1024, 2100, 2) | the 64-chunk cap of the sums kernels, the 512-chunk cap of the vector gradient kernel, C = 4 vectors, the generic kernels over several chunks, the fallback for unaligned views |
 | max-pool / upsample / fixed width | (2, 2050, 2064, 4), (3, 1800, 1804, 1), (2, 301, 403, 3); upsampling of more than 2 097 152 quads / outputs; (2, 16, 16400, 4) strips | the 8192-block cap of the vector and of the generic kernels, ties in most windows |
@@ -619,8 +619,8 @@ SOFTMAX_SHAPES = [(4100, 162), (8200, 100), (16400, 37)] + [(37, c) for c in (1,
 @pytest.mark.parametrize('dtype', DTYPES)
 @pytest.mark.parametrize('shape', SOFTMAX_SHAPES, ids=lambda s: f'{s[0]}x{s[1]}')
 def test_softmax_ce_past_1024_blocks_and_across_lane_groups(shape, dtype, gpu):
-    """m > 37: more than 1024 blocks, so the last block adds the block losses in the strided branch of
-    last_block_sum.  Three calls in a row: the arrival counter must be back at zero each time."""
+    """m > 37: more than 1024 blocks, so the last block adds the block losses past its first four rows per
+    thread in the strided walk of last_block_fold.  Three calls in a row: the arrival counter must be back at zero each time."""
     from univer_ocr_amd.nn import ops
     CP = gpu(dtype)
     m, c = shape

@@ -224,6 +224,42 @@ __global__ __launch_bounds__(256) void u8_to_float_vec_kernel(const uint8_t* __r
     }
 }
 
+// ---- the update rules opt_fused_one shares with the stand-alone kernels (reg_kernel, momentum_kernel; see adam_kernel) ----
+// How hipcc contracts a * b + c * d into one of its two FMAs depends on how the operands reach the expression, and the
+// results are pinned bit for bit: reg_term hands back its two terms instead of adding them, and the gradient of the Adam
+// rule comes by reference (its one caller holds it in a register) -- the forms that keep every kernel's bits.
+template <typename T>
+__device__ __forceinline__ T dev_sqrt(T x);
+template <>
+__device__ __forceinline__ float dev_sqrt<float>(float x) { return sqrtf(x); }
+template <>
+__device__ __forceinline__ double dev_sqrt<double>(double x) { return sqrt(x); }
+
+// regulariser of one weight (KIND 1 = L1, 2 = L2): dg = dR/dw, what the gradient gets, and term = R / strength, what the
+// float64 sum gets.  The callers add them: the fused kernel chooses the kind per range at run time and adds once.
+template <typename T, int KIND>
+__device__ __forceinline__ void reg_term(T w, T strength, T& dg, double& term) {
+    if (KIND == 2) {
+        dg = strength * T(2) * w;
+        term = (double)w * (double)w;
+    } else {
+        const T s = w > T(0) ? T(1) : (w < T(0) ? T(-1) : (w == T(0) ? T(0) : w));
+        dg = strength * s;
+        term = (double)(w < T(0) ? -w : w);
+    }
+}
+template <typename T>
+__device__ __forceinline__ void momentum_update(T& w, T g, T& v, T lr, T mu) {
+    v = mu * v - lr * g;
+    w += v;
+}
+template <typename T>
+__device__ __forceinline__ void adam_update(T& w, const T& g, T& v, T& a, T lr, T b1, T b2, T eps) {
+    v = b1 * v + (T(1) - b1) * g;
+    a = b2 * a + (T(1) - b2) * (g * g);
+    w -= lr / (dev_sqrt<T>(a) + eps) * v;
+}
+
 // ---- regularizers: grad += dR/dw, partial sums of R in float64 ------------------------------
 template <typename T, int KIND /*1 = L1, 2 = L2*/>
 __global__ __launch_bounds__(256) void reg_kernel(const T* w, T* grad, size_t n, T strength, double* partial) {
@@ -232,15 +268,11 @@ __global__ __launch_bounds__(256) void reg_kernel(const T* w, T* grad, size_t n,
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     double acc = 0.0;
     for (size_t i = tid; i < n; i += stride) {
-        const T v = w[i];
-        if (KIND == 2) {
-            grad[i] += strength * T(2) * v;
-            acc += (double)v * (double)v;
-        } else {
-            const T s = v > T(0) ? T(1) : (v < T(0) ? T(-1) : (v == T(0) ? T(0) : v));
-            grad[i] += strength * s;
-            acc += (double)(v < T(0) ? -v : v);
-        }
+        T dg;
+        double term;
+        reg_term<T, KIND>(w[i], strength, dg, term);
+        grad[i] += dg;
+        acc += term;
     }
     acc = block_reduce_sum(acc, smem);
     if (threadIdx.x == 0) partial[blockIdx.x] = acc;
@@ -257,13 +289,9 @@ __global__ __launch_bounds__(256) void finish_sum_kernel(const double* partial, 
 }
 
 // ---- optimizers ---------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ T dev_sqrt(T x);
-template <>
-__device__ __forceinline__ float dev_sqrt<float>(float x) { return sqrtf(x); }
-template <>
-__device__ __forceinline__ double dev_sqrt<double>(double x) { return sqrt(x); }
-
+// (adam_kernel keeps its own copy of the Adam expressions, and rmsprop_kernel, which no fused kernel shares a rule with,
+// stays as it was: through a shared function hipcc contracts b1 * v + c1 * g into the other of its two possible FMAs in
+// the float64 instantiations, and the last bits of v and w change)
 template <typename T, int V>
 __global__ __launch_bounds__(256) void adam_kernel(T* w, const T* g, T* v, T* a, size_t n, T lr, T b1, T b2,
                                                    T eps) {
@@ -300,16 +328,13 @@ template <typename T>
 __global__ __launch_bounds__(256) void momentum_kernel(T* w, const T* g, T* v, size_t n, T lr, T mu) {
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = tid; i < n; i += stride) {
-        const T vi = mu * v[i] - lr * g[i];
-        v[i] = vi;
-        w[i] += vi;
-    }
+    for (size_t i = tid; i < n; i += stride) momentum_update(w[i], g[i], v[i], lr, mu);
 }
 
 // Momentum step with the regulariser gradients and the gradient reset folded in (the tail of a train step:
 // layers.py:147-155 regularize, optimizers.py:75-78 update, layers.py:20-21 clear_grad = 4 launches -> 2).
-// Same float operations in the same order as reg_kernel followed by momentum_kernel.
+// The same float operations in the same order as reg_kernel followed by momentum_kernel / adam_kernel: reg_term, then the
+// kernel's update rule.
 struct RegRanges {
     long long lo[4], hi[4];
     int kind[4];          // 1 = L1, 2 = L2
@@ -318,7 +343,7 @@ struct RegRanges {
 };
 
 // OPT 0: Momentum (s1 = velocity; p0 = lr, p1 = momentum); OPT 1: Adam (s1 = velocity, s2 = accumulated;
-// p0 = lr, p1 = beta1, p2 = beta2, p3 = eps) -- the update expressions of momentum_kernel / adam_kernel
+// p0 = lr, p1 = beta1, p2 = beta2, p3 = eps)
 template <typename T, int OPT>
 __device__ __forceinline__ void opt_fused_one(T& wi, T& gi, T& vi, T& ai, long long i, const RegRanges& rr,
                                               bool near_range, double (&acc)[4], T p0, T p1, T p2, T p3) {
@@ -326,26 +351,17 @@ __device__ __forceinline__ void opt_fused_one(T& wi, T& gi, T& vi, T& ai, long l
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             if (r < rr.n && i >= rr.lo[r] && i < rr.hi[r]) {
-                const T strength = (T)rr.strength[r];
-                if (rr.kind[r] == 2) {
-                    gi += strength * T(2) * wi;
-                    acc[r] += (double)wi * (double)wi;
-                } else {
-                    const T s = wi > T(0) ? T(1) : (wi < T(0) ? T(-1) : (wi == T(0) ? T(0) : wi));
-                    gi += strength * s;
-                    acc[r] += (double)(wi < T(0) ? -wi : wi);
-                }
+                T dg;
+                double term;
+                if (rr.kind[r] == 2) reg_term<T, 2>(wi, (T)rr.strength[r], dg, term);
+                else reg_term<T, 1>(wi, (T)rr.strength[r], dg, term);
+                gi += dg;
+                acc[r] += term;
             }
         }
     }
-    if constexpr (OPT == 0) {
-        vi = p1 * vi - p0 * gi;
-        wi = wi + vi;
-    } else {
-        vi = p1 * vi + (T(1) - p1) * gi;
-        ai = p2 * ai + (T(1) - p2) * (gi * gi);
-        wi = wi - p0 / (dev_sqrt<T>(ai) + p3) * vi;
-    }
+    if constexpr (OPT == 0) momentum_update(wi, gi, vi, p0, p1);
+    else adam_update(wi, gi, vi, ai, p0, p1, p2, p3);
 }
 
 // VEC = 4: every thread moves 4 consecutive parameters per trip as one vector per array (the arrays are
@@ -369,11 +385,10 @@ __device__ __forceinline__ void loss_snapshot(const LossSnapshot& s) {
     for (int i = 0; i < s.count; ++i) s.ring[(size_t)k * s.count + i] = s.src[i];
 }
 
-// With regulariser ranges the last block to arrive adds the partial rows of all blocks, OPT_FUSED_SUM_TRIPS rows per
-// thread: the launcher's block cap for that case must stay within what 256 threads cover.
+// With regulariser ranges the last block to arrive adds the partial rows of all blocks (last_block_fold), the rows a
+// thread gets under the launcher's block cap for that case all in flight together.
 constexpr unsigned OPT_FUSED_REG_GRID = 256;
-constexpr int OPT_FUSED_SUM_TRIPS = 4;
-static_assert(OPT_FUSED_REG_GRID <= 256u * OPT_FUSED_SUM_TRIPS, "the last block of opt_fused_kernel would skip partial rows");
+constexpr int OPT_FUSED_SUM_TRIPS = (OPT_FUSED_REG_GRID + 255) / 256;
 
 template <typename T, int OPT, int VEC>
 __global__ __launch_bounds__(256) void opt_fused_kernel(T* __restrict__ w, T* __restrict__ g, T* __restrict__ s1,
@@ -439,51 +454,23 @@ __global__ __launch_bounds__(256) void opt_fused_kernel(T* __restrict__ w, T* __
         if (lane == 0) smem[wv_id][r] = t;
     }
     __syncthreads();
-    if (gridDim.x == 1) {                                  // small nets: the one block IS the whole sum, no finish launch
-        if (threadIdx.x == 0) {
-            double total = 0.0;
-            for (int r = 0; r < rr.n; ++r) total += rr.strength[r] * (smem[0][r] + smem[1][r] + smem[2][r] + smem[3][r]);
-            *loss_out = total;
-            loss_snapshot(snap);
-        }
-        return;
-    }
-    // several blocks: publish the block's four sums; the last block to arrive adds all of them up (block order) --
-    // no finish launch
-    __shared__ int last;
-    if (threadIdx.x < 4)
-        pub_store(partial + (size_t)blockIdx.x * 4 + threadIdx.x,
-                  smem[0][threadIdx.x] + smem[1][threadIdx.x] + smem[2][threadIdx.x] + smem[3][threadIdx.x]);
-    if (threadIdx.x == 0) last = sync_arrive(counter) == gridDim.x - 1;       // (threads 0-3 are one wave: drained together)
-    __syncthreads();
-    if (!last) return;
-    // every partial this thread adds is requested before the first one is waited for (agent-scope loads take a trip to the
-    // memory side each; one range after the other, one block at a time was 3 x 3 of them in a row), block order kept
-    __shared__ double red[16];
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    {
-        double t[OPT_FUSED_SUM_TRIPS][4];
-#pragma unroll
-        for (int k = 0; k < OPT_FUSED_SUM_TRIPS; ++k)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int i = threadIdx.x + 256 * k;
-                t[k][r] = (i < (int)gridDim.x && r < rr.n) ? pub_load(partial + (size_t)i * 4 + r) : 0.0;
-            }
-#pragma unroll
-        for (int k = 0; k < OPT_FUSED_SUM_TRIPS; ++k)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) a[r] += t[k][r];
-    }
-    double total = 0.0;
-    for (int r = 0; r < rr.n; ++r) {
-        const double sum = block_reduce_sum(a[r], red);
-        __syncthreads();
-        total += rr.strength[r] * sum;
-    }
+    // the block's four sums; with several blocks the last one to arrive gets the sums of all of them (block order) -- no
+    // finish launch, and small nets whose one block IS the whole sum skip the hand-off
+    __shared__ double red[17];
+    double sums[4] = {0.0, 0.0, 0.0, 0.0};
     if (threadIdx.x == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sums[r] = smem[0][r] + smem[1][r] + smem[2][r] + smem[3][r];
+    }
+    if (gridDim.x > 1 &&
+        !last_block_fold<256, OPT_FUSED_SUM_TRIPS, FoldSum, FoldSum, FoldSum, FoldSum>(counter, partial, sums, red))
+        return;
+    if (threadIdx.x == 0) {
+        double total = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (r < rr.n) total += rr.strength[r] * sums[r];
         *loss_out = total;
-        sync_clear(counter);
         loss_snapshot(snap);
     }
 }
@@ -764,7 +751,8 @@ static int launch_opt_fused(uocr_ctx* ctx, int dtype, int opt, void* w, void* g,
     UOCR_DISPATCH(ctx, dtype, {
         auto launch = [&](auto kernel) {
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, ctx->stream, (T*)w, (T*)g, (T*)s1, (T*)s2, count, (T)p0,
-                               (T)p1, (T)p2, (T)p3, rr, partial, reg_loss_out, ctx->sync + 3, zero_grad, hyper_dev, snap);
+                               (T)p1, (T)p2, (T)p3, rr, partial, reg_loss_out, ctx->sync + UOCR_SYNC_OPT_TAIL, zero_grad,
+                               hyper_dev, snap);
         };
         if (opt == 0 && vec) launch(opt_fused_kernel<T, 0, 4>);
         else if (opt == 0) launch(opt_fused_kernel<T, 0, 1>);

@@ -34,49 +34,25 @@ namespace {
 
 // (tile, chunk and strip sizes, the union-find and the body of steps 2-7 for one image: label_common.h, shared with
 // label_batch.hip)
-constexpr unsigned LSYNC = 4;              // word of ctx->sync the statistics launch counts its blocks in
 
 // ---- 1. threshold statistics ------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(LNT) void label_stats(const T* __restrict__ x, size_t count, int mode, unsigned* counter,
-                                                   double* partial /* [2 * grid] */, double* thr) {
+                                                   double* partial /* [grid][2] */, double* thr) {
     __shared__ double smem[17];
-    __shared__ double smax[5];
-    double sum = 0.0, mx = -INFINITY;
+    double v[2] = {0.0, -INFINITY};                            // sum, max
     for (size_t i = (size_t)blockIdx.x * LNT + threadIdx.x; i < count; i += (size_t)gridDim.x * LNT) {
-        const double v = (double)x[i];
-        sum += v;
-        mx = v > mx ? v : mx;
+        const double xi = (double)x[i];
+        v[0] += xi;
+        v[1] = xi > v[1] ? xi : v[1];
     }
-    sum = block_reduce_sum(sum, smem);
-    mx = wave_reduce_max(mx);
-    if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = mx;
-    __syncthreads();
+    v[0] = block_reduce_sum(v[0], smem);
+    v[1] = block_reduce_max(v[1], smem);
+    // (the last block to arrive folds the blocks' sums and maxima in a fixed order: the same bits run to run)
+    if (!last_block_fold<LNT, 4, FoldSum, FoldMax>(counter, partial, v, smem)) return;
     if (threadIdx.x == 0) {
-        for (int k = 1; k < LNT / 64; ++k) mx = smax[k] > mx ? smax[k] : mx;
-        pub_store(partial + 2 * blockIdx.x, sum);
-        pub_store(partial + 2 * blockIdx.x + 1, mx);
-        const unsigned t = sync_arrive(counter);
-        smax[4] = t == gridDim.x - 1 ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    if (smax[4] == 0.0) return;                                // block-uniform: only the last block to arrive goes on
-    sum = 0.0, mx = -INFINITY;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += LNT) {  // fixed order: the same bits run to run
-        sum += pub_load(partial + 2 * i);
-        const double m = pub_load(partial + 2 * i + 1);
-        mx = m > mx ? m : mx;
-    }
-    sum = block_reduce_sum(sum, smem);
-    mx = wave_reduce_max(mx);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < LNT / 64; ++k) mx = smax[k] > mx ? smax[k] : mx;
-        const double mean = sum / (double)count;
-        *thr = mode == UOCR_THRESH_MEAN ? mean : 0.5 * (mean + mx);
-        sync_clear(counter);
+        const double mean = v[0] / (double)count;
+        *thr = mode == UOCR_THRESH_MEAN ? mean : 0.5 * (mean + v[1]);
     }
 }
 
@@ -223,7 +199,7 @@ int uocr_label_components(uocr_ctx* ctx, int dtype, const void* x, int n, int h,
     UOCR_DISPATCH_STORAGE(ctx, dtype, {
         if (thresh_mode != UOCR_THRESH_VALUE) {
             hipLaunchKernelGGL(label_stats<T>, dim3(stat_blocks), dim3(LNT), 0, ctx->stream, (const T*)x, pixels, thresh_mode,
-                               ctx->sync + LSYNC, partial, thr);
+                               ctx->sync + UOCR_SYNC_LABEL_STATS, partial, thr);
             UOCR_LAUNCH_CHECK(ctx);
             ++launches;
         }

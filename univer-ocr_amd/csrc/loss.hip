@@ -99,6 +99,31 @@ __device__ __forceinline__ void seg_num_den(double s_pg, double s_p, double s_g,
     den = KIND == UOCR_LOSS_DICE ? s_p + s_g + 2 * SEG_EPS             // losses.py:19-20
                                  : s_p + s_g - num + 2 * SEG_EPS;      // losses.py:38
 }
+// the three sums of the pair whose chunk partials start at `o`: this thread adds chunks first, first + step, ... in that order
+__device__ __forceinline__ void seg_chunk_sums(const double* o, int first, int step, int nchunks, double& s_pg, double& s_p,
+                                               double& s_g) {
+    s_pg = s_p = s_g = 0.0;
+    for (int k = first; k < nchunks; k += step) {
+        s_pg += o[(size_t)k * 3];
+        s_p += o[(size_t)k * 3 + 1];
+        s_g += o[(size_t)k * 3 + 2];
+    }
+}
+// the gradient r = ca * label + cb
+template <int KIND>
+__device__ __forceinline__ void seg_coef(double num, double den, double& ca, double& cb) {
+    if (KIND == UOCR_LOSS_DICE) {
+        ca = -2.0 / den;
+        cb = 2.0 * num / (den * den);
+    } else {
+        ca = -(den + num) / (den * den);
+        cb = num / (den * den);
+    }
+}
+template <int KIND>
+__device__ __forceinline__ double seg_loss_term(double num, double den) {                // losses.py:22,40
+    return KIND == UOCR_LOSS_DICE ? 1.0 - 2.0 * num / den : 1.0 - num / den;
+}
 
 template <typename T, int KIND>
 __global__ __launch_bounds__(256) void seg_grad_kernel(const T* __restrict__ pred, const T* __restrict__ gt,
@@ -111,16 +136,10 @@ __global__ __launch_bounds__(256) void seg_grad_kernel(const T* __restrict__ pre
     if (chunk == 0 && pair == 0) {                       // the loss: sum over all pairs
         double loss = 0.0;
         for (int q = threadIdx.x; q < npairs; q += blockDim.x) {
-            double s_pg = 0.0, s_p = 0.0, s_g = 0.0;
-            for (int k = 0; k < nchunks; ++k) {
-                const double* o = partial + ((size_t)q * nchunks + k) * 3;
-                s_pg += o[0];
-                s_p += o[1];
-                s_g += o[2];
-            }
-            double num, den;
+            double s_pg, s_p, s_g, num, den;
+            seg_chunk_sums(partial + (size_t)q * nchunks * 3, 0, 1, nchunks, s_pg, s_p, s_g);
             seg_num_den<KIND>(s_pg, s_p, s_g, num, den);
-            loss += KIND == UOCR_LOSS_DICE ? 1.0 - 2.0 * num / den : 1.0 - num / den;   // losses.py:22,40
+            loss += seg_loss_term<KIND>(num, den);
         }
         loss = block_reduce_sum(loss, smem);
         if (threadIdx.x == 0) *loss_out = loss;
@@ -128,22 +147,10 @@ __global__ __launch_bounds__(256) void seg_grad_kernel(const T* __restrict__ pre
     }
     if (!grad) return;
     if (threadIdx.x == 0) {                              // nchunks <= 64: a serial sum in chunk order
-        double s_pg = 0.0, s_p = 0.0, s_g = 0.0;
-        for (int k = 0; k < nchunks; ++k) {
-            const double* o = partial + ((size_t)pair * nchunks + k) * 3;
-            s_pg += o[0];
-            s_p += o[1];
-            s_g += o[2];
-        }
-        double num, den;
+        double s_pg, s_p, s_g, num, den;
+        seg_chunk_sums(partial + (size_t)pair * nchunks * 3, 0, 1, nchunks, s_pg, s_p, s_g);
         seg_num_den<KIND>(s_pg, s_p, s_g, num, den);
-        if (KIND == UOCR_LOSS_DICE) {
-            coef[0] = -2.0 / den;
-            coef[1] = 2.0 * num / (den * den);
-        } else {
-            coef[0] = -(den + num) / (den * den);
-            coef[1] = num / (den * den);
-        }
+        seg_coef<KIND>(num, den, coef[0], coef[1]);
         coef[0] *= gscale;                               // UOCR_F16_SCALED(k): grad * 2^k (exact), else 1
         coef[1] *= gscale;
     }
@@ -283,13 +290,7 @@ __global__ __launch_bounds__(256) void seg_grad_vec_kernel(const T* __restrict__
         for (int q0 = 0; q0 < npairs; q0 += ngrp) {
             const int q = q0 + grp;
             double s_pg = 0.0, s_p = 0.0, s_g = 0.0;
-            if (q < npairs)
-                for (int k = sub; k < pchunks; k += gs) {
-                    const double* o = partial + ((size_t)q * pchunks + k) * 3;
-                    s_pg += o[0];
-                    s_p += o[1];
-                    s_g += o[2];
-                }
+            if (q < npairs) seg_chunk_sums(partial + (size_t)q * pchunks * 3, sub, gs, pchunks, s_pg, s_p, s_g);
             for (int off = gs >> 1; off > 0; off >>= 1) {
                 s_pg += __shfl_xor(s_pg, off, 64);
                 s_p += __shfl_xor(s_p, off, 64);
@@ -297,7 +298,7 @@ __global__ __launch_bounds__(256) void seg_grad_vec_kernel(const T* __restrict__
             }
             double num, den;
             seg_num_den<KIND>(s_pg, s_p, s_g, num, den);
-            if (sub == 0 && q < npairs) loss += KIND == UOCR_LOSS_DICE ? 1.0 - 2.0 * num / den : 1.0 - num / den;   // losses.py:22,40
+            if (sub == 0 && q < npairs) loss += seg_loss_term<KIND>(num, den);
         }
         // the group leaders' terms: lanes 0, gs, 2 gs, ... of the wave
         loss = wave_reduce_sum(loss);
@@ -311,26 +312,15 @@ __global__ __launch_bounds__(256) void seg_grad_vec_kernel(const T* __restrict__
     if (threadIdx.x < 64) {
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) {
-            double s_pg = 0.0, s_p = 0.0, s_g = 0.0;
-            for (int k = threadIdx.x; k < pchunks; k += 64) {
-                const double* o = partial + ((size_t)(b * C + ch) * pchunks + k) * 3;
-                s_pg += o[0];
-                s_p += o[1];
-                s_g += o[2];
-            }
+            double s_pg, s_p, s_g;
+            seg_chunk_sums(partial + (size_t)(b * C + ch) * pchunks * 3, threadIdx.x, 64, pchunks, s_pg, s_p, s_g);
             s_pg = wave_reduce_sum(s_pg);
             s_p = wave_reduce_sum(s_p);
             s_g = wave_reduce_sum(s_g);
             if (threadIdx.x == 0) {
                 double num, den, ca, cb;
                 seg_num_den<KIND>(s_pg, s_p, s_g, num, den);
-                if (KIND == UOCR_LOSS_DICE) {
-                    ca = -2.0 / den;
-                    cb = 2.0 * num / (den * den);
-                } else {
-                    ca = -(den + num) / (den * den);
-                    cb = num / (den * den);
-                }
+                seg_coef<KIND>(num, den, ca, cb);
                 // the gradient is linear in the label with these two coefficients (computed in float64, applied in
                 // float32: the label is 0 / 1 and the result is stored in float32 or binary16 anyway)
                 coef[ch][0] = (float)(ca * gscale);
@@ -447,7 +437,8 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const T* __restrict__ p
 #pragma unroll
             for (int r = 0; r < RPW; ++r) mine += rows[w][r];
     }
-    last_block_sum(counter, block_loss, mine, (int)gridDim.x, 1.0 / (double)m, loss_out, smem);
+    double v[1] = {mine};
+    if (last_block_fold<256, 4, FoldSum>(counter, block_loss, v, smem) && threadIdx.x == 0) *loss_out = (1.0 / (double)m) * v[0];
 }
 
 template <typename T>
@@ -466,7 +457,8 @@ __global__ __launch_bounds__(256) void sigmoid_ce_kernel(const T* __restrict__ p
     }
     acc = block_reduce_sum(acc, smem);
     __syncthreads();
-    last_block_sum(counter, partial, acc, (int)gridDim.x, inv_m, loss_out, smem);
+    double v[1] = {acc};
+    if (last_block_fold<256, 4, FoldSum>(counter, partial, v, smem) && threadIdx.x == 0) *loss_out = inv_m * v[0];
 }
 
 }  // namespace
@@ -489,6 +481,11 @@ int uocr_seg_loss(uocr_ctx* ctx, int dtype, int kind, const void* pred, const vo
     UOCR_REQUIRE(ctx, (size_t)hw * c < (size_t)INT32_MAX && npairs <= 65535);
     const double gscale = uocr_grad_scale(dtype);
     const auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+    // the gradient launch of the loss kind (the kernels come in through parameter types: their names do not carry a lambda)
+    const auto by_kind = [&](auto dice, auto jaccard, dim3 grid, auto... args) {
+        if (kind == UOCR_LOSS_DICE) hipLaunchKernelGGL(dice, grid, dim3(256), 0, ctx->stream, args...);
+        else hipLaunchKernelGGL(jaccard, grid, dim3(256), 0, ctx->stream, args...);
+    };
     const int elem = UOCR_DTYPE_BASE(dtype) == UOCR_F16 ? 2 : UOCR_DTYPE_BASE(dtype) == UOCR_F32 ? 4 : 8;
     const bool vec = elem <= 4 && (c == 1 || c == 2 || c == 4) && ((size_t)hw * c * elem) % 16 == 0 && al16(pred) &&
                      al16(gt) && (!grad || al16(grad)) && n < 65535;
@@ -505,14 +502,9 @@ int uocr_seg_loss(uocr_ctx* ctx, int dtype, int kind, const void* pred, const vo
             hipLaunchKernelGGL((seg_partial_vec_kernel<T, C>), dim3(nchunks, n), dim3(256), 0, ctx->stream, (const T*)pred,
                                (const T*)gt, partial, hw, nchunks);
             const dim3 ggrid = grad ? dim3(gchunks, n + 1) : dim3(1, 1);       // row 0: the loss
-            if (kind == UOCR_LOSS_DICE)
-                hipLaunchKernelGGL((seg_grad_vec_kernel<T, C, UOCR_LOSS_DICE>), ggrid, dim3(256), 0, ctx->stream,
-                                   (const T*)pred, (const T*)gt, (const double*)partial, (T*)grad, loss_out, hw, nchunks,
-                                   gchunks, npairs, out_act, gscale);
-            else
-                hipLaunchKernelGGL((seg_grad_vec_kernel<T, C, UOCR_LOSS_JACCARD>), ggrid, dim3(256), 0, ctx->stream,
-                                   (const T*)pred, (const T*)gt, (const double*)partial, (T*)grad, loss_out, hw, nchunks,
-                                   gchunks, npairs, out_act, gscale);
+            by_kind(seg_grad_vec_kernel<T, C, UOCR_LOSS_DICE>, seg_grad_vec_kernel<T, C, UOCR_LOSS_JACCARD>, ggrid,
+                    (const T*)pred, (const T*)gt, (const double*)partial, (T*)grad, loss_out, hw, nchunks, gchunks, npairs,
+                    out_act, gscale);
         };
         auto by_c = [&](auto tag) {
             if (c == 1) run(tag, std::integral_constant<int, 1>{});
@@ -530,14 +522,8 @@ int uocr_seg_loss(uocr_ctx* ctx, int dtype, int kind, const void* pred, const vo
         UOCR_LAUNCH_CHECK(ctx);
         // without a gradient only block (0,0) has work
         const dim3 grid = grad ? dim3(nchunks, npairs) : dim3(1, 1);
-        if (kind == UOCR_LOSS_DICE)
-            hipLaunchKernelGGL((seg_grad_kernel<T, UOCR_LOSS_DICE>), grid, dim3(256), 0, ctx->stream, (const T*)pred,
-                               (const T*)gt, (const double*)partial, (T*)grad, loss_out, hw, c, nchunks, npairs,
-                               out_act, gscale);
-        else
-            hipLaunchKernelGGL((seg_grad_kernel<T, UOCR_LOSS_JACCARD>), grid, dim3(256), 0, ctx->stream,
-                               (const T*)pred, (const T*)gt, (const double*)partial, (T*)grad, loss_out, hw, c,
-                               nchunks, npairs, out_act, gscale);
+        by_kind(seg_grad_kernel<T, UOCR_LOSS_DICE>, seg_grad_kernel<T, UOCR_LOSS_JACCARD>, grid, (const T*)pred,
+                (const T*)gt, (const double*)partial, (T*)grad, loss_out, hw, c, nchunks, npairs, out_act, gscale);
         UOCR_LAUNCH_CHECK(ctx);
     });
     return UOCR_OK;
@@ -556,8 +542,8 @@ int uocr_softmax_ce(uocr_ctx* ctx, int dtype, const void* pred, const void* gt, 
             constexpr int RL = decltype(rl_tag)::value;
             const int rows_per_block = 4 * (64 / RL);
             hipLaunchKernelGGL((softmax_ce_kernel<TS, T, RL>), dim3((m + rows_per_block - 1) / rows_per_block), dim3(256),
-                               0, ctx->stream, (const TS*)pred, (const TS*)gt, (TS*)grad, block_loss, ctx->sync + 1, loss_out,
-                               m, c, gscale);
+                               0, ctx->stream, (const TS*)pred, (const TS*)gt, (TS*)grad, block_loss,
+                               ctx->sync + UOCR_SYNC_SOFTMAX_CE, loss_out, m, c, gscale);
         };
         if (c <= 64) launch(std::integral_constant<int, 16>{});
         else if (c <= 128) launch(std::integral_constant<int, 32>{});
@@ -577,8 +563,8 @@ int uocr_sigmoid_ce(uocr_ctx* ctx, int dtype, const void* pred, const void* gt, 
     double* partial = (double*)ctx->workspace;
     UOCR_DISPATCH_STORAGE(ctx, dtype, {
         hipLaunchKernelGGL((sigmoid_ce_kernel<T>), dim3(grid), dim3(256), 0, ctx->stream, (const T*)pred,
-                           (const T*)gt, (T*)grad, partial, ctx->sync + 2, loss_out, count, 1.0 / (double)m,
-                           uocr_grad_scale(dtype));
+                           (const T*)gt, (T*)grad, partial, ctx->sync + UOCR_SYNC_SIGMOID_CE, loss_out, count,
+                           1.0 / (double)m, uocr_grad_scale(dtype));
         UOCR_LAUNCH_CHECK(ctx);
     });
     return UOCR_OK;

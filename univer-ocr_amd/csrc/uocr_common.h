@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "univer_hip.h"
 
@@ -50,7 +51,7 @@ struct uocr_ctx {
     unsigned* snap_counter = nullptr;
     void* gemm_defer = nullptr;    // recorded weight-gradient GEMMs of an open deferred group (gemm_mfma.hip), or null
     void* finish_defer = nullptr;  // recorded finish kernels + their partial region (finish_group.hip), or null
-    unsigned* sync = nullptr;      // UOCR_SYNC_WORDS arrival counters of the single-launch reductions (loss.hip): zero between launches
+    unsigned* sync = nullptr;      // arrival counters of the in-launch reductions, a word per user (uocr_sync_word): zero between launches
     int cu_count = 256;            // (the device's, once uocr_ctx_create could ask it)
     int opt_mfma = 1;        // 0 = never, 1 = auto (default), 2 = whenever eligible (tests)
     int opt_fast = 1;        // 0 = generic kernels only, 1 = shape-specialised fast paths (default)
@@ -77,7 +78,6 @@ struct uocr_ctx {
     char err[512] = {};
 };
 
-constexpr int UOCR_SYNC_WORDS = 1 << 18;   // 1 MB
 // bits of the "t32" option whose kernels this library contains (conv_t32.hip, conv_t32w.hip)
 #ifdef UOCR_EXPERIMENTS
 constexpr int UOCR_T32_BUILT = 255;
@@ -265,70 +265,126 @@ __device__ __forceinline__ T wave_reduce_max(T v) {
     return v;
 }
 
-// block-wide sum of doubles for blocks of up to 1024 threads; result valid in thread 0
+// block-wide sum of doubles for blocks of up to 1024 threads; result valid in thread 0 (NT: the block size where the caller
+// knows it at compile time, 0 = ask blockDim)
+template <int NT = 0>
 __device__ __forceinline__ double block_reduce_sum(double v, double* smem /* >= 16 doubles */) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     v = wave_reduce_sum(v);
     __syncthreads();
     if (lane == 0) smem[wid] = v;
     __syncthreads();
-    const int nw = (blockDim.x + 63) >> 6;
+    const int nw = NT ? (NT + 63) >> 6 : (blockDim.x + 63) >> 6;
     v = (threadIdx.x < (unsigned)nw) ? smem[threadIdx.x] : 0.0;
     if (wid == 0) v = wave_reduce_sum(v);
     return v;
 }
 
-// ---- single-launch sums (loss.hip: the cross-entropies; elementwise.hip: the regulariser sums of the fused optimizer tail)
-// Blocks hand small float64 partials to each other INSIDE a launch.  gfx950 has one L2 per XCD and they are not
-// coherent with each other, so every handed-off word is written by an agent-scope atomic store (write-through, sc1),
-// drained (s_waitcnt vmcnt(0)) before the writer's arrival is counted, and read by agent-scope atomic loads (sc1:
-// past this CU's L1 and this XCD's L2 copy); no fences.  Counters live in ctx->sync, are zero between launches and
-// are put back to zero by the last block that touches them.
+// block-wide maximum of doubles (NaN never wins), same shape as block_reduce_sum; result valid in thread 0
+template <int NT = 0>
+__device__ __forceinline__ double block_reduce_max(double v, double* smem /* >= 16 doubles */) {
+    v = wave_reduce_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) smem[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int nw = NT ? (NT + 63) >> 6 : (blockDim.x + 63) >> 6;
+        for (int k = 1; k < nw; ++k) v = smem[k] > v ? smem[k] : v;
+    }
+    return v;
+}
+
+// ---- in-launch reductions: the last block to arrive folds what every block of the launch published
+// Users: softmax_ce_kernel and sigmoid_ce_kernel (loss.hip: the loss, one sum), opt_fused_kernel (elementwise.hip: the four
+// regulariser sums of the fused optimizer tail), label_stats (label.hip: sum and max of the image for the threshold).
+// The protocol, stated once.  Blocks hand small float64 partials to each other INSIDE a launch.  gfx950 has one L2 per XCD
+// and they are not coherent with each other, so every handed-off word is written by a relaxed agent-scope atomic store
+// (write-through, sc1), drained (s_waitcnt vmcnt(0)) before the writer's arrival is counted by a relaxed agent-scope
+// fetch-add, and read by relaxed agent-scope atomic loads (sc1: past this CU's L1 and this XCD's L2 copy); no fences.
+// Nobody waits for another block.  Each user has its own counter word in ctx->sync (uocr_sync_word); a counter is zero
+// between launches and is put back to zero by the block that drew the last ticket.
+enum uocr_sync_word {
+    UOCR_SYNC_SOFTMAX_CE = 1,   // (word 0 is not in use; the indices are the ones the launches have always counted in)
+    UOCR_SYNC_SIGMOID_CE,
+    UOCR_SYNC_OPT_TAIL,
+    UOCR_SYNC_LABEL_STATS,
+    UOCR_SYNC_WORDS             // words of ctx->sync
+};
 __device__ __forceinline__ void pub_store(double* p, double v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ double pub_load(const double* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ unsigned sync_arrive(unsigned* c) {            // the payload stores of this thread are drained first
+__device__ __forceinline__ unsigned sync_arrive(unsigned* c) {            // the payload stores of this thread's wave are drained first
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     return __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned sync_peek(unsigned* c) {
-    return __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ void sync_clear(unsigned* c) {
     __hip_atomic_store(c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// The last block of a launch to arrive at `counter` adds up `count` published partials (block-strided, fixed order)
-// and stores scale * sum; every thread of every block calls this (it contains barriers).
-__device__ __forceinline__ void last_block_sum(unsigned* counter, double* partial, double mine, int count, double scale,
-                                               double* out, double* smem /* >= 17 doubles */) {
+// what one reduced quantity (a slot) is folded with: the order of the folds is fixed, so the bits are the same run to run
+struct FoldSum {
+    static __device__ __forceinline__ double identity() { return 0.0; }
+    static __device__ __forceinline__ double fold(double acc, double v) { return acc + v; }
+    template <int B>
+    static __device__ __forceinline__ double block(double v, double* smem) { return block_reduce_sum<B>(v, smem); }
+};
+struct FoldMax {
+    static __device__ __forceinline__ double identity() { return -INFINITY; }
+    static __device__ __forceinline__ double fold(double acc, double v) { return v > acc ? v : acc; }
+    template <int B>
+    static __device__ __forceinline__ double block(double v, double* smem) { return block_reduce_max<B>(v, smem); }
+};
+// Every thread of every block of the launch calls this once (it contains barriers), with the block's own value of each slot
+// in v[] of thread 0.  Returns false in all blocks but the one that drew the last ticket; there it returns true and leaves
+// the launch-wide value of each slot in v[] of thread 0, for the caller to scale and store.  Thread t folds rows t, t + B,
+// t + 2 B, ... of `partial` in that order (B = the block size of the launch), then the block tree of the slot's op.
+// Two things are structure here, not a convention of the callers:
+//  - thread 0 alone publishes all K words, drains them (sync_arrive) and takes the ticket: publisher and ticket-taker
+//    are one lane of one wave, whatever K is;
+//  - the K words of a thread's first TRIPS rows are all requested before the first one is waited for (an agent-scope load is
+//    a trip to the memory side, and with a branch around each load hipcc waits for each: K x TRIPS trips in a row).  So a
+//    row past the last block is read at a clamped address and replaced by the identity afterwards, no branch; rows past
+//    TRIPS * B are walked K loads at a time.
+template <int B, int TRIPS, class... Op, size_t... S /* 0 .. K-1: slot S is folded with the S-th Op */>
+__device__ __forceinline__ bool last_block_fold_slots(std::index_sequence<S...>, unsigned* counter, double* partial,
+                                                      double (&v)[sizeof...(Op)], double* smem) {
+    constexpr int K = sizeof...(Op);
+    static_assert(TRIPS >= 1 && K >= 1 && K * TRIPS <= 32, "a thread keeps K * TRIPS loads of two registers each in flight");
     if (threadIdx.x == 0) {
-        pub_store(partial + blockIdx.x, mine);
-        const unsigned t = sync_arrive(counter);
-        smem[16] = t == gridDim.x - 1 ? 1.0 : 0.0;
+#pragma unroll
+        for (int s = 0; s < K; ++s) pub_store(partial + (size_t)blockIdx.x * K + s, v[s]);
+        smem[16] = sync_arrive(counter) == gridDim.x - 1 ? 1.0 : 0.0;
     }
     __syncthreads();
-    if (smem[16] == 0.0) return;                       // block-uniform
-    double acc = 0.0;
-    if (count <= 4 * (int)blockDim.x) {                // (the usual case: all of a thread's partials requested at once)
-        double t[4];
+    if (smem[16] == 0.0) return false;                 // block-uniform
+    const int count = (int)gridDim.x;
+    double t[TRIPS][K];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int i = threadIdx.x + k * blockDim.x;
-            t[k] = i < count ? pub_load(partial + i) : 0.0;
-        }
+    for (int k = 0; k < TRIPS; ++k)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) acc += t[k];
-    } else {
-        for (int i = threadIdx.x; i < count; i += blockDim.x) acc += pub_load(partial + i);
+        for (int s = 0; s < K; ++s) t[k][s] = pub_load(partial + (size_t)min((int)threadIdx.x + k * B, count - 1) * K + s);
+    double acc[K] = {Op::identity()...};
+#pragma unroll
+    for (int k = 0; k < TRIPS; ++k) {
+        const bool live = (int)threadIdx.x + k * B < count;
+        ((acc[S] = Op::fold(acc[S], live ? t[k][S] : Op::identity())), ...);
     }
-    acc = block_reduce_sum(acc, smem);
-    if (threadIdx.x == 0) {
-        *out = scale * acc;
-        sync_clear(counter);
+    for (int i = (int)threadIdx.x + TRIPS * B; i < count; i += B) {
+        double row[K];
+#pragma unroll
+        for (int s = 0; s < K; ++s) row[s] = pub_load(partial + (size_t)i * K + s);
+        ((acc[S] = Op::fold(acc[S], row[S])), ...);
     }
+    ((v[S] = Op::template block<B>(acc[S], smem)), ...);
+    if (threadIdx.x == 0) sync_clear(counter);
+    return true;
+}
+template <int B, int TRIPS, class... Op>
+__device__ __forceinline__ bool last_block_fold(unsigned* counter, double* partial /* [gridDim.x][K] */,
+                                                double (&v)[sizeof...(Op)], double* smem /* >= 17 doubles */) {
+    return last_block_fold_slots<B, TRIPS, Op...>(std::index_sequence_for<Op...>{}, counter, partial, v, smem);
 }
 
 // ---- activation-tensor element access ---------------------------------------------------------------------
