@@ -128,6 +128,13 @@ def label_page(who, mask, arrays, max_components):
     return arrays, components, int(components.count[0])
 
 
+def nest_like(flat, nested):
+    """the next items of `flat` (a list, or an iterator that several calls draw from), one per item of every list of
+    `nested`, in `nested`'s nesting"""
+    items = iter(flat)
+    return [[next(items) for _ in inner] for inner in nested]
+
+
 class CropParagraphs:
     def __init__(self, find_rotation=False, max_components=4096):
         if find_rotation:
@@ -137,12 +144,31 @@ class CropParagraphs:
                 'find_rotation=False')
         self.max_components = max_components
 
+    def angles_of(self, components, paragraphs):
+        """the angle (degrees, or None) every paragraph is turned by: here none is"""
+        return [None] * paragraphs
+
     def __call__(self, mask, arrays, divisible_by=None):
         """mask: (1, H, W, 1) DeviceArray, arrays: list of (1, H, W, C) DeviceArrays.  Returns
         result[array_id][paragraph_id], paragraphs in scipy's label order.  divisible_by=(y, x) adds the zero frame of
-        make_divisible_by (my_model/model.py:26-34), which the reference applies to every crop right after this stage."""
-        arrays, components, paragraphs = label_page('CropParagraphs', mask, arrays, self.max_components)
-        return [[ops.masked_crop(a, components, 0, k, divisible_by) for k in range(1, paragraphs + 1)] for a in arrays]
+        make_divisible_by (my_model/model.py:26-34), which the reference applies to every crop right after this stage.
+        Every paragraph is turned by its angle (self.angles[p] afterwards: degrees, or None for a paragraph cut upright);
+        a paragraph whose rotated mask has no set pixel -- the reference raises there -- is cut upright too."""
+        arrays, components, paragraphs = label_page(type(self).__name__, mask, arrays, self.max_components)
+        angles = self.angles_of(components, paragraphs)
+        rotated = [p for p in range(paragraphs) if angles[p] is not None]
+        regions = {}
+        if rotated:
+            extents = ops.rotated_extent(components, 0, [(p + 1, angles[p]) for p in rotated])
+            regions = {p: tuple(int(v) for v in extent) for p, extent in zip(rotated, extents) if extent[1] > extent[0]}
+        for p in rotated:
+            if p not in regions:
+                angles[p] = None
+        self.angles = angles
+        turned = iter(ops.rotate_crop([(a, components, 0, p + 1, angles[p], regions[p]) for a in arrays for p in sorted(regions)],
+                                      divisible_by) if regions else [])
+        return [[next(turned) if p in regions else ops.masked_crop(a, components, 0, p + 1, divisible_by)
+                 for p in range(paragraphs)] for a in arrays]
 
 
 def search_steps(eps=1.0):
@@ -175,7 +201,7 @@ def search_angle(height_of, eps=1.0):
         return done.value
 
 
-class CropAndRotateParagraphs:
+class CropAndRotateParagraphs(CropParagraphs):
     def __init__(self, find_rotation=True, eps=1.0, max_components=4096, search='host'):
         """search: 'host' walks the rounds on the host (find_angles), 'device' leaves them to ONE rotation_search call;
         an eps whose tree the device cannot walk (nn/ops.py: search_table) keeps to the host search."""
@@ -206,31 +232,13 @@ class CropAndRotateParagraphs:
             extents = ops.rotated_extent(components, 0, [(p + 1, angle) for p in order for angle in probes[p]])
             heights = [int(y1 - y0) for y0, y1, _, _ in extents]
 
-    def __call__(self, mask, arrays, divisible_by=None):
-        """mask: (1, H, W, 1) DeviceArray, arrays: list of (1, H, W, C) DeviceArrays.  Returns
-        result[array_id][paragraph_id] as CropParagraphs does, every paragraph turned by its angle (self.angles[p]
-        afterwards: degrees, or None for a paragraph cut upright).  A paragraph whose rotated mask has no set pixel --
-        the reference raises there -- is cut upright too."""
-        arrays, components, paragraphs = label_page('CropAndRotateParagraphs', mask, arrays, self.max_components)
+    def angles_of(self, components, paragraphs):
+        """the angles of the search, walked on the host or by the device"""
         if not self.find_rotation or not paragraphs:
-            angles = [None] * paragraphs
-        elif self.search == 'device':
-            angles = list(ops.rotation_search(components, 0, range(1, paragraphs + 1), self.eps)[0])
-        else:
-            angles = self.find_angles(components, paragraphs)
-        rotated = [p for p in range(paragraphs) if angles[p] is not None]
-        regions = {}
-        if rotated:
-            extents = ops.rotated_extent(components, 0, [(p + 1, angles[p]) for p in rotated])
-            regions = {p: tuple(int(v) for v in extent) for p, extent in zip(rotated, extents) if extent[1] > extent[0]}
-        for p in rotated:
-            if p not in regions:
-                angles[p] = None
-        self.angles = angles
-        turned = iter(ops.rotate_crop([(a, components, 0, p + 1, angles[p], regions[p]) for a in arrays for p in sorted(regions)],
-                                      divisible_by) if regions else [])
-        return [[next(turned) if p in regions else ops.masked_crop(a, components, 0, p + 1, divisible_by)
-                 for p in range(paragraphs)] for a in arrays]
+            return [None] * paragraphs
+        if self.search == 'device':
+            return list(ops.rotation_search(components, 0, range(1, paragraphs + 1), self.eps)[0])
+        return self.find_angles(components, paragraphs)
 
 
 class CropLines:
@@ -291,7 +299,7 @@ class CropLines:
         entries = [(per_array[p], y0, x0, bh, bw, QUARTER_TURNS[rotation])
                    for per_array in arrays for p, (rotation, boxes) in enumerate(found) for y0, x0, bh, bw in boxes]
         crops = iter(ops.line_crop(entries, self.zoomed_height, self.minimal_width))
-        return [[[next(crops) for _ in boxes] for _, boxes in found] for _ in arrays]
+        return [nest_like(crops, [boxes for _, boxes in found]) for _ in arrays]
 
 
 class LabelChars:
@@ -304,8 +312,7 @@ class LabelChars:
         """arrays[paragraph][line]: (1, H, W, C) DeviceArrays.  Returns the labels, (W, n_chars) each, in the same nesting
         (a paragraph without lines stays [], a page without paragraphs []); one kernel call for the page."""
         flat = [ops.as_device(line) for paragraph in arrays for line in paragraph]
-        labels = iter(ops.char_label(flat, self.bits, self.n_chars))
-        return [[next(labels) for _ in paragraph] for paragraph in arrays]
+        return nest_like(ops.char_label(flat, self.bits, self.n_chars), arrays)
 
 
 def _alphabet(first, yo):
@@ -374,8 +381,7 @@ class PredToText:
         line as a str in the same nesting (a paragraph without lines stays [], a page without paragraphs []); one kernel
         call for the page, two when a row holds a tie."""
         flat = [ops.as_device(line) for paragraph in predictions for line in paragraph]
-        texts = iter(''.join(self.chars[i] for i in ids) for ids in ops.pred_to_text(flat, self.cls))
-        return [[next(texts) for _ in paragraph] for paragraph in predictions]
+        return nest_like((''.join(self.chars[i] for i in ids) for ids in ops.pred_to_text(flat, self.cls)), predictions)
 
 
 def canonical_ids(pairs=SIMILAR_PAIRS, n_chars=len(CHARS), similar=True):
@@ -403,6 +409,5 @@ class ScoreText:
         flat = lambda nested: [ops.as_device(line) for paragraph in nested for line in paragraph]
         scores, read, expected = ops.text_score(flat(predictions), flat(labels), self.canon, want_ids=True)
         text = lambda ids: ''.join(self.chars[i] for i in ids)
-        rows = iter(zip((tuple(int(v) for v in row) for row in scores), map(text, read), map(text, expected)))
-        nested = [[next(rows) for _ in paragraph] for paragraph in predictions]
-        return tuple([[line[k] for line in paragraph] for paragraph in nested] for k in range(3))
+        return (nest_like((tuple(int(v) for v in row) for row in scores), predictions),
+                nest_like(map(text, read), predictions), nest_like(map(text, expected), predictions))

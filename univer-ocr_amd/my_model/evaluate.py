@@ -11,6 +11,7 @@ import json
 from collections import namedtuple
 
 from .model import CHAR_INPUT_HEIGHT, make_evaluate_context_maker, make_evaluate_system
+from .predict import add_option_flags, flag_options, read_weights
 
 TextReport = namedtuple('TextReport', 'pages lines exact_lines typed_chars expected_chars read_chars distance cer coverage')
 
@@ -18,14 +19,7 @@ TextReport = namedtuple('TextReport', 'pages lines exact_lines typed_chars expec
 def load_evaluate_system(input_shape, weights_path=None, crops='true', **options):
     """make_evaluate_system with the weights of `weights_path` (a model_weights.json); a missing file, or none, leaves the
     fresh weights in place (as my_model/predict.py: load_model_system)"""
-    weights = {}
-    if weights_path is not None:
-        try:
-            with open(weights_path) as fp:
-                weights = json.load(fp)
-        except OSError:
-            print(f'No {weights_path} file found')
-    return make_evaluate_system(input_shape, weights=weights, crops=crops, **options)[0]
+    return make_evaluate_system(input_shape, weights=read_weights(weights_path), crops=crops, **options)[0]
 
 
 def evaluate_text(pages, n_pages, model_system=None, weights_path=None, crops='true', contexts=None, **options):
@@ -70,19 +64,12 @@ def main(argv=None):
                         help='end to end: paragraphs and lines as the nets find them, not the true layers')
     parser.add_argument('--distinct-look-alikes', action='store_true',
                         help='the halves of a Cyrillic / Latin look-alike pair count as different characters')
-    parser.add_argument('--device-search', action='store_true',
-                        help='the angle search of the paragraphs in one call on the device, not round by round on the host')
-    parser.add_argument('--page-line-labels', action='store_true',
-                        help='the line masks of all paragraphs of the page labelled in one call, not paragraph by paragraph')
-    parser.add_argument('--page-char-pass', action='store_true',
-                        help='the Char net once per page on all lines laid side by side, not once per line')
+    add_option_flags(parser)
     args = parser.parse_args(argv)
     CP.use_gpu()
     pages = PagesWithText(GeneratedPages(1, args.height, args.width, seed=args.seed, length=args.pages), args.pages)
     report = evaluate_text(pages, args.pages, weights_path=args.weights, crops='predicted' if args.predicted_crops else 'true',
-                           rotation_search='device' if args.device_search else 'host',
-                           line_labelling='page' if args.page_line_labels else 'paragraph',
-                           char_batching='page' if args.page_char_pass else 'line', similar=not args.distinct_look_alikes)
+                           similar=not args.distinct_look_alikes, **flag_options(args))
     print(json.dumps(report._asdict()))
     return report
 

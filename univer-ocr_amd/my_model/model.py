@@ -462,6 +462,63 @@ def make_context_maker(mode=Modes.PREDICT):
     return _context_maker(wanted[mode])
 
 
+# What differs between the page systems, as (predicted, labelled, last).  predicted: Monochrome, Paragraph and Line stand in
+# front of the crops they feed and LineCrop reads Line's prediction (a missing one is an empty page) -- else the true `line`
+# layer rides through ParagraphCrop and is LineCrop's mask; labelled: the `char` layer rides through both crop stages and
+# CharLabel reads it; last: the stage the system ends after, the supervised one where it is a net.
+_CUTS = {'TRAIN_LINE': (False, False, 'Line'), 'TRAIN_CHAR': (False, True, 'Char'), 'PREDICT': (True, False, 'PredToText'),
+         'true': (False, True, 'TextScore'), 'predicted': (True, True, 'TextScore')}
+
+
+def _page_chain(cut, net=None, tracker=None, find_rotation=False, rotation_search='host', line_labelling='paragraph',
+                similar=True):
+    """The chain every page system is a cut of, in the reference's component order (model.py:489-500): [(name, make)] of
+    the stages that _CUTS[cut] holds.  make() builds the component: net(name, selector class, X label, y label, prediction
+    label) that of a net, a make_*_component that of a device stage of my_model/crop.py, with the labels it reads and
+    files.  Nothing is built before that, so the names of a cut need no further argument."""
+    predicted, labelled, last = _CUTS[cut]
+    riders = ('monochrome_pred',) + ('line',) * (not predicted) + ('char',) * labelled      # through ParagraphCrop
+    companions = tuple(layer for layer in riders if layer != 'line')                         # through LineCrop too
+    cropped = lambda prefix, layers: tuple(prefix + layer.removesuffix('_pred') for layer in layers)
+    chain = (
+        ('Monochrome', predicted, lambda: net('Monochrome', StringSelector, 'monochrome_X', None, 'monochrome_pred')),
+        ('Paragraph', predicted, lambda: net('Paragraph', StringSelector, 'monochrome_pred', None, 'paragraph_pred')),
+        ('ParagraphCrop', True, lambda: make_paragraph_crop_component(
+            find_rotation, tracker, riders, cropped('cropped_', riders), rotation_search)),
+        ('Line', predicted or last == 'Line', lambda: net(
+            'Line', LineSelector, 'cropped_monochrome', 'cropped_line', 'line_pred')),
+        ('LineCrop', True, lambda: make_line_crop_component(
+            tracker, 'line_pred' if predicted else 'cropped_line', cropped('cropped_', companions),
+            cropped('cropped_2_', companions), empty_page_ok=predicted, line_labelling=line_labelling)),
+        ('CharLabel', labelled, lambda: make_char_label_component(tracker, 'cropped_2_char', 'char_labels')),
+        ('Char', True, lambda: net('Char', CharSelector, 'cropped_2_monochrome', 'char_labels', 'char_pred')),
+        ('PredToText', True, lambda: make_pred_to_text_component(tracker, 'char_pred', 'text', lines='cropped_2_monochrome')),
+        ('TextScore', True, lambda: make_text_score_component(tracker, 'char_pred', 'char_labels', 'text_scores',
+                                                              lines='cropped_2_monochrome', similar=similar)),
+    )
+    end = [name for name, _, _ in chain].index(last) + 1
+    return [(name, make) for name, present, make in chain[:end] if present]
+
+
+def _make_page_system(who, cut, input_shape, optimizer, progress_tracker, weights, char_batching='line', **options):
+    """(model_system, models, names) of the cut `cut` of _page_chain, which takes the `options`.  char_batching is checked
+    here (`who`: the builder in the message), the other options by the stages they reach.  input_shape is the page's where
+    the nets stand in front -- the Char net then takes lines of 64 columns -- and else the one net's own; a net gets its
+    `y` where the system ends after it."""
+    if char_batching not in ('line', 'page'):
+        raise ValueError(f"{who}: char_batching must be 'line' or 'page', got {char_batching!r}")
+    predicted, _, last = _CUTS[cut]
+    models = {}
+
+    def net(name, selector, X, y, pred):
+        shape = (input_shape[0], CHAR_INPUT_HEIGHT, 64, 1) if name == 'Char' and predicted else input_shape
+        models[name] = _make_net(name, shape, optimizer, progress_tracker, weights)
+        kind = PackedLinesComponent if name == 'Char' and char_batching == 'page' else ModelComponent
+        return kind(name, models[name], selector(X, y if name == last else None, pred), delist_result=True)
+    chain = _page_chain(cut, net, progress_tracker, **options)
+    return ModelSystem([make() for _, make in chain]), models, [name for name, _ in chain]
+
+
 def make_model_system(input_shape, optimizer=None, progress_tracker=None, weights=None, mode=Modes.PREDICT,
                       char_input_shape=None, find_rotation=False, rotation_search='host'):
     """model.py:486-717 for the device-resident modes.  Returns (model_system, models, names).
@@ -475,7 +532,8 @@ def make_model_system(input_shape, optimizer=None, progress_tracker=None, weight
     only) puts CropAndRotateParagraphs in the ParagraphCrop slot: the reference's default, every paragraph turned by the
     angle of its rotation search; rotation_search='device' lets the device walk that search (one call per page)."""
     if mode is Modes.TRAIN_LINE:
-        return _make_train_line_system(input_shape, optimizer, progress_tracker, weights, find_rotation, rotation_search)
+        return _make_page_system('make_model_system', 'TRAIN_LINE', input_shape, optimizer, progress_tracker, weights,
+                                 find_rotation=find_rotation, rotation_search=rotation_search)
     if find_rotation:
         raise ValueError(f'find_rotation=True: {mode.name} has no ParagraphCrop stage')
     plan = {
@@ -500,15 +558,6 @@ def make_model_system(input_shape, optimizer=None, progress_tracker=None, weight
     return ModelSystem(components), models, list(plan[mode])
 
 
-def _make_train_line_system(input_shape, optimizer, progress_tracker, weights, find_rotation=False, rotation_search='host'):
-    model = _make_net('Line', input_shape, optimizer, progress_tracker, weights)
-    line = ModelComponent('Line', model, LineSelector('cropped_monochrome', 'cropped_line', 'line_pred'),
-                          delist_result=True)
-    paragraph_crop = make_paragraph_crop_component(find_rotation, progress_tracker, rotation_search=rotation_search)
-    return (ModelSystem([paragraph_crop, line]), {'Line': model},
-            ['ParagraphCrop', 'Line'])
-
-
 def make_train_char_context_maker():
     """model.py:449-459 (the TRAIN_CHAR context) for `make_train_char_system`: the layers monochrome, paragraph, line and
     char of one page, moved to the device (the reference keeps them on the host for its host stages)."""
@@ -530,14 +579,8 @@ def make_train_char_system(input_shape, optimizer=None, progress_tracker=None, w
       Char           one step per line through a CharSelector; predictions at context['char_pred'][p][l]
     input_shape is the Char net's, (batch, *, width, channels): its height is CHAR_INPUT_HEIGHT.  line_labelling:
     'paragraph' or 'page', how LineCrop labels its masks (make_line_crop_component)."""
-    paragraph_crop = make_paragraph_crop_component(find_rotation, progress_tracker, ('monochrome_pred', 'line', 'char'),
-                                                   ('cropped_monochrome', 'cropped_line', 'cropped_char'), rotation_search)
-    model = _make_net('Char', input_shape, optimizer, progress_tracker, weights)
-    char = ModelComponent('Char', model, CharSelector('cropped_2_monochrome', 'char_labels', 'char_pred'),
-                          delist_result=True)
-    components = [paragraph_crop, make_line_crop_component(progress_tracker, line_labelling=line_labelling),
-                  make_char_label_component(progress_tracker), char]
-    return ModelSystem(components), {'Char': model}, ['ParagraphCrop', 'LineCrop', 'CharLabel', 'Char']
+    return _make_page_system('make_train_char_system', 'TRAIN_CHAR', input_shape, optimizer, progress_tracker, weights,
+                             find_rotation=find_rotation, rotation_search=rotation_search, line_labelling=line_labelling)
 
 
 def make_predict_system(input_shape, progress_tracker=None, weights=None, find_rotation=True, rotation_search='host',
@@ -563,32 +606,11 @@ def make_predict_system(input_shape, progress_tracker=None, weights=None, find_r
     line_labelling: 'paragraph' or 'page', how LineCrop labels its masks (make_line_crop_component).
     char_batching: 'line' runs the Char net once per line, 'page' once per page on all lines laid side by side
     (PackedLinesComponent): the same predictions from one pass."""
-    if char_batching not in ('line', 'page'):
-        raise ValueError(f"make_predict_system: char_batching must be 'line' or 'page', got {char_batching!r}")
-    models = {name: _make_net(name, shape, None, progress_tracker, weights)
-              for name, shape in (('Monochrome', input_shape), ('Paragraph', input_shape), ('Line', input_shape),
-                                  ('Char', (input_shape[0], CHAR_INPUT_HEIGHT, 64, 1)))}
-    selectors = {'Monochrome': StringSelector('monochrome_X', None, 'monochrome_pred'),
-                 'Paragraph': StringSelector('monochrome_pred', None, 'paragraph_pred'),
-                 'Line': LineSelector('cropped_monochrome', None, 'line_pred'),
-                 'Char': CharSelector('cropped_2_monochrome', None, 'char_pred')}
-    net = {name: ModelComponent(name, models[name], selectors[name], delist_result=True) for name in models}
-    if char_batching == 'page':
-        net['Char'] = PackedLinesComponent('Char', models['Char'], selectors['Char'], delist_result=True)
-    components = [net['Monochrome'], net['Paragraph'],
-                  make_paragraph_crop_component(find_rotation, progress_tracker, ('monochrome_pred',), ('cropped_monochrome',),
-                                                rotation_search),
-                  net['Line'],
-                  make_line_crop_component(progress_tracker, 'line_pred', ('cropped_monochrome',), ('cropped_2_monochrome',),
-                                           empty_page_ok=True, line_labelling=line_labelling),
-                  net['Char'], make_pred_to_text_component(progress_tracker, lines='cropped_2_monochrome')]
-    return (ModelSystem(components), models,
-            ['Monochrome', 'Paragraph', 'ParagraphCrop', 'Line', 'LineCrop', 'Char', 'PredToText'])
+    return _make_page_system('make_predict_system', 'PREDICT', input_shape, None, progress_tracker, weights, char_batching,
+                             find_rotation=find_rotation, rotation_search=rotation_search, line_labelling=line_labelling)
 
 
-EVALUATE_NAMES = {'true': ['ParagraphCrop', 'LineCrop', 'CharLabel', 'Char', 'PredToText', 'TextScore'],
-                  'predicted': ['Monochrome', 'Paragraph', 'ParagraphCrop', 'Line', 'LineCrop', 'CharLabel', 'Char',
-                                'PredToText', 'TextScore']}
+EVALUATE_NAMES = {crops: [name for name, _ in _page_chain(crops)] for crops in ('true', 'predicted')}
 
 
 def make_evaluate_context_maker(crops):
@@ -619,33 +641,7 @@ def make_evaluate_system(input_shape, progress_tracker=None, weights=None, crops
     make_predict_system; similar: as in make_text_score_component."""
     if crops not in EVALUATE_NAMES:
         raise ValueError(f"make_evaluate_system: crops must be 'true' or 'predicted', got {crops!r}")
-    if char_batching not in ('line', 'page'):
-        raise ValueError(f"make_evaluate_system: char_batching must be 'line' or 'page', got {char_batching!r}")
     find_rotation = (crops == 'predicted') if find_rotation is None else find_rotation
-    char_shape = input_shape if crops == 'true' else (input_shape[0], CHAR_INPUT_HEIGHT, 64, 1)
-    shapes = {'Char': char_shape} if crops == 'true' else {'Monochrome': input_shape, 'Paragraph': input_shape,
-                                                           'Line': input_shape, 'Char': char_shape}
-    models = {name: _make_net(name, shape, None, progress_tracker, weights) for name, shape in shapes.items()}
-    selector = CharSelector('cropped_2_monochrome', None, 'char_pred')
-    char = (PackedLinesComponent if char_batching == 'page' else ModelComponent)('Char', models['Char'], selector,
-                                                                                delist_result=True)
-    tail = [make_char_label_component(progress_tracker), char,
-            make_pred_to_text_component(progress_tracker, lines='cropped_2_monochrome'),
-            make_text_score_component(progress_tracker, lines='cropped_2_monochrome', similar=similar)]
-    if crops == 'true':
-        head = [make_paragraph_crop_component(find_rotation, progress_tracker, ('monochrome_pred', 'line', 'char'),
-                                              ('cropped_monochrome', 'cropped_line', 'cropped_char'), rotation_search),
-                make_line_crop_component(progress_tracker, line_labelling=line_labelling)]
-    else:
-        net = {name: ModelComponent(name, models[name], sel, delist_result=True) for name, sel in (
-            ('Monochrome', StringSelector('monochrome_X', None, 'monochrome_pred')),
-            ('Paragraph', StringSelector('monochrome_pred', None, 'paragraph_pred')),
-            ('Line', LineSelector('cropped_monochrome', None, 'line_pred')))}
-        head = [net['Monochrome'], net['Paragraph'],
-                make_paragraph_crop_component(find_rotation, progress_tracker, ('monochrome_pred', 'char'),
-                                              ('cropped_monochrome', 'cropped_char'), rotation_search),
-                net['Line'],
-                make_line_crop_component(progress_tracker, 'line_pred', ('cropped_monochrome', 'cropped_char'),
-                                         ('cropped_2_monochrome', 'cropped_2_char'), empty_page_ok=True,
-                                         line_labelling=line_labelling)]
-    return ModelSystem(head + tail), models, list(EVALUATE_NAMES[crops])
+    return _make_page_system('make_evaluate_system', crops, input_shape, None, progress_tracker, weights, char_batching,
+                             find_rotation=find_rotation, rotation_search=rotation_search, line_labelling=line_labelling,
+                             similar=similar)

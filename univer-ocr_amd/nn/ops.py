@@ -531,7 +531,48 @@ def has_nan(x):
 
 
 # ---- connected components / masked crops (interpreter/interpreter.py: ParagraphCrop) ---------------------------------
-class Components:
+# what the flat lists of the page-stage calls hold, as written in the messages: rank, least and most of shape[0]
+_ENTRY_FORMS = {'(1, H, W, C)': (4, 1, 1), '(N, H, W, C)': (4, 0, math.inf), '(W, n_chars)': (2, 1, math.inf)}
+
+
+def _check_entries(who, arrays, form='(1, H, W, C)'):
+    """every array of the flat list of a page-stage call is a DeviceArray of the form the call takes"""
+    ndim, least, most = _ENTRY_FORMS[form]
+    for a in arrays:
+        if not isinstance(a, DeviceArray) or a.ndim != ndim or not least <= a.shape[0] <= most:
+            raise ValueError(f'{who}: expected {form} device arrays, got {getattr(a, "shape", type(a))}')
+
+
+def _threshold_args(who, threshold):
+    """(mode, value) of the labelling calls for a threshold 'mean', 'mean_max' or a number"""
+    if isinstance(threshold, str):
+        if threshold not in ('mean', 'mean_max'):
+            raise ValueError(f"{who}: threshold must be 'mean', 'mean_max' or a number, got {threshold!r}")
+        return (hiplib.THRESH_MEAN if threshold == 'mean' else hiplib.THRESH_MEAN_MAX), 0.0
+    return hiplib.THRESH_VALUE, float(threshold)
+
+
+def _repeat_longer(counts, rows, caps, again):
+    """The second pass of a call that had room for caps[i] rows of item i and read back every item's true count: the items
+    that hold more are repeated in ONE call, again(their indices, their counts) -> (counts, rows), which must count what
+    the first pass counted, and their rows take the places of the cut ones in `rows`."""
+    longer = [i for i, (count, cap) in enumerate(zip(counts, caps)) if count > cap]
+    if longer:
+        recount, full = again(longer, [int(counts[i]) for i in longer])
+        assert all(recount[k] == counts[i] for k, i in enumerate(longer))
+        for k, i in enumerate(longer):
+            rows[i] = full[k]
+
+
+class _TableViews:
+    """boxes, area and center_of_mass of int64 (count, 8) tables = first pixel, area, y0, y1, x0, x1, sum of y, sum of x;
+    `_view(f)` is f of the table, or of every image's"""
+    boxes = property(lambda self: self._view(lambda t: t[:, 2:6]))
+    area = property(lambda self: self._view(lambda t: t[:, 1]))
+    center_of_mass = property(lambda self: self._view(lambda t: t[:, 6:8] / np.maximum(t[:, 1:2], 1)))
+
+
+class Components(_TableViews):
     """Result of label_components.  `.labels` stays on the device; `.count`, `.boxes`, `.area` and `.center_of_mass`
     (one entry per image) come from ONE device-to-host copy of the component table and the counts, made at the first
     access.  boxes[n] is (count, 4) = y0, y1, x0, x1, half-open as scipy's find_objects slices; center_of_mass[n] is
@@ -562,17 +603,8 @@ class Components:
         """per image: int64 (count, 8) = first pixel, area, y0, y1, x0, x1, sum of y, sum of x"""
         return self._fetch()[1]
 
-    @property
-    def boxes(self):
-        return [t[:, 2:6] for t in self.table]
-
-    @property
-    def area(self):
-        return [t[:, 1] for t in self.table]
-
-    @property
-    def center_of_mass(self):
-        return [t[:, 6:8] / np.maximum(t[:, 1:2], 1) for t in self.table]
+    def _view(self, f):
+        return [f(t) for t in self.table]
 
 
 def label_components(x, threshold='mean', max_components=4096):
@@ -581,12 +613,7 @@ def label_components(x, threshold='mean', max_components=4096):
     if x.ndim != 4 or x.shape[3] != 1:
         raise ValueError(f'label_components: expected (N, H, W, 1), got {x.shape}')
     n, h, w, _ = x.shape
-    if isinstance(threshold, str):
-        if threshold not in ('mean', 'mean_max'):
-            raise ValueError(f"label_components: threshold must be 'mean', 'mean_max' or a number, got {threshold!r}")
-        mode, value = (hiplib.THRESH_MEAN if threshold == 'mean' else hiplib.THRESH_MEAN_MAX), 0.0
-    else:
-        mode, value = hiplib.THRESH_VALUE, float(threshold)
+    mode, value = _threshold_args('label_components', threshold)
     max_components = int(max_components)
     labels = CP.empty((n, h, w), np.int32)
     table = CP.empty((n, max_components, 8), np.int64)
@@ -596,7 +623,7 @@ def label_components(x, threshold='mean', max_components=4096):
     return Components(labels, table, count, max_components)
 
 
-class EntryComponents:
+class EntryComponents(_TableViews):
     """Result of label_batch for ONE entry, on the host already: `count` (an int), `table` int64 (count, 8) = first
     pixel, area, y0, y1, x0, x1, sum of y, sum of x, and `boxes` (count, 4), `area` (count,), `center_of_mass`
     (count, 2) as Components has them per image.  `labels`: the int32 (H, W) DeviceArray, or None where none was asked
@@ -605,17 +632,8 @@ class EntryComponents:
     def __init__(self, count, table, labels=None):
         self.count, self.table, self.labels = int(count), table, labels
 
-    @property
-    def boxes(self):
-        return self.table[:, 2:6]
-
-    @property
-    def area(self):
-        return self.table[:, 1]
-
-    @property
-    def center_of_mass(self):
-        return self.table[:, 6:8] / np.maximum(self.table[:, 1:2], 1)
+    def _view(self, f):
+        return f(self.table)
 
 
 def _label_batch_call(entries, mode, value, cap, planes):
@@ -644,19 +662,13 @@ def label_batch(entries, threshold='mean', max_components=4096, cap=256, labels=
     room their counts ask for; an entry with more than max_components raises HipError.  labels=True also writes every
     entry's int32 (H, W) label plane (EntryComponents.labels).  No call for an empty list."""
     entries = [(a, int(channel)) for a, channel in entries]
+    _check_entries('label_batch', [a for a, _ in entries])
     for a, channel in entries:
-        if not isinstance(a, DeviceArray) or a.ndim != 4 or a.shape[0] != 1:
-            raise ValueError(f'label_batch: expected (1, H, W, C) device arrays, got {getattr(a, "shape", type(a))}')
         if not 0 <= channel < a.shape[3]:
             raise ValueError(f'label_batch: channel {channel} of an array of shape {a.shape}')
         if a.shape[1] < 1 or a.shape[2] < 1:
             raise ValueError(f'label_batch: an empty array, {a.shape}')
-    if isinstance(threshold, str):
-        if threshold not in ('mean', 'mean_max'):
-            raise ValueError(f"label_batch: threshold must be 'mean', 'mean_max' or a number, got {threshold!r}")
-        mode, value = (hiplib.THRESH_MEAN if threshold == 'mean' else hiplib.THRESH_MEAN_MAX), 0.0
-    else:
-        mode, value = hiplib.THRESH_VALUE, float(threshold)
+    mode, value = _threshold_args('label_batch', threshold)
     max_components, cap = int(max_components), int(cap)
     if max_components < 0 or cap < 0:
         raise ValueError(f'label_batch: max_components = {max_components}, cap = {cap}')
@@ -668,12 +680,8 @@ def label_batch(entries, threshold='mean', max_components=4096, cap=256, labels=
     counts, tables = _label_batch_call(entries, mode, value, cap, planes)
     if int(counts.max()) > max_components:
         raise HipError(f'label_batch: an entry has {int(counts.max())} components, more than max_components = {max_components}')
-    longer = [i for i, count in enumerate(counts) if count > cap]
-    if longer:
-        again, full = _label_batch_call([entries[i] for i in longer], mode, value, max(int(counts[i]) for i in longer), None)
-        assert all(again[k] == counts[i] for k, i in enumerate(longer))
-        for k, i in enumerate(longer):
-            tables[i] = full[k]
+    _repeat_longer(counts, tables, [cap] * len(entries),
+                   lambda longer, room: _label_batch_call([entries[i] for i in longer], mode, value, max(room), None))
     return [EntryComponents(count, table, planes[i] if labels else None)
             for i, (count, table) in enumerate(zip(counts, tables))]
 
@@ -756,9 +764,8 @@ def rotate_crop(entries, divisible_by=None):
                for a, comp, index, k, angle, region in entries]
     if not entries:
         return []
+    _check_entries('rotate_crop', [entry[0] for entry in entries], '(N, H, W, C)')
     for a, comp, index, k, angle, region in entries:
-        if not isinstance(a, DeviceArray) or a.ndim != 4:
-            raise ValueError(f'rotate_crop: expected (N, H, W, C) device arrays, got {getattr(a, "shape", type(a))}')
         if comp.labels.shape != a.shape[:3]:
             raise ValueError(f'rotate_crop: labels {comp.labels.shape} do not belong to an array of shape {a.shape}')
     arrays, components, index, ks, angles, _ = zip(*entries)
@@ -899,9 +906,7 @@ def char_label(lines, bits, n_chars, want_ids=False):
     empty list); labels
     have the lines' dtype.  want_ids=True: also the int32 (W,) winning class of every column, -1 where the row is zero."""
     lines = list(lines)
-    for a in lines:
-        if not isinstance(a, DeviceArray) or a.ndim != 4 or a.shape[0] != 1:
-            raise ValueError(f'char_label: expected (1, H, W, C) device arrays, got {getattr(a, "shape", type(a))}')
+    _check_entries('char_label', lines)
     if not lines:
         return ([], []) if want_ids else []
     code, c = _shared_code(lines, 'char_label', 'dtype and channel count'), lines[0].shape[3]
@@ -940,9 +945,7 @@ def pred_to_text(lines, cls):
     lines that emitted more (rows with ties) are repeated in ONE second call with the room their counts ask for.  No
     call for an empty list."""
     lines = list(lines)
-    for a in lines:
-        if not isinstance(a, DeviceArray) or a.ndim != 2 or a.shape[0] < 1:
-            raise ValueError(f'pred_to_text: expected (W, n_chars) device arrays, got {getattr(a, "shape", type(a))}')
+    _check_entries('pred_to_text', lines, '(W, n_chars)')
     if not lines:
         return []
     cls = [int(v) for v in cls]
@@ -950,12 +953,7 @@ def pred_to_text(lines, cls):
         raise ValueError(f'pred_to_text: {len(cls)} classes, but the lines are ' + ', '.join(str(a.shape) for a in lines))
     caps = [a.shape[0] for a in lines]
     counts, ids = _pred_to_text_call(lines, cls, caps)
-    longer = [i for i, (count, cap) in enumerate(zip(counts, caps)) if count > cap]
-    if longer:
-        again, full = _pred_to_text_call([lines[i] for i in longer], cls, [int(counts[i]) for i in longer])
-        assert all(again[k] == counts[i] for k, i in enumerate(longer))
-        for k, i in enumerate(longer):
-            ids[i] = full[k]
+    _repeat_longer(counts, ids, caps, lambda longer, room: _pred_to_text_call([lines[i] for i in longer], cls, room))
     return [v.tolist() for v in ids]
 
 
@@ -971,9 +969,7 @@ def text_score(preds, labels, canon, want_ids=False):
     preds, labels = list(preds), list(labels)
     if len(preds) != len(labels):
         raise ValueError(f'text_score: {len(preds)} predictions for {len(labels)} labels')
-    for a in preds + labels:
-        if not isinstance(a, DeviceArray) or a.ndim != 2 or a.shape[0] < 1:
-            raise ValueError(f'text_score: expected (W, n_chars) device arrays, got {getattr(a, "shape", type(a))}')
+    _check_entries('text_score', preds + labels, '(W, n_chars)')
     if not preds:
         return (np.zeros((0, 3), np.int32), [], []) if want_ids else np.zeros((0, 3), np.int32)
     canon = [int(v) for v in canon]
@@ -1018,9 +1014,8 @@ def line_crop(entries, zoomed_height=32, minimal_width=8):
     columns.  ONE uocr_line_crop call for all entries, whatever their sizes and channel counts (none for an empty list);
     returns the (1, zoomed_height, out_w, C) DeviceArrays in the entries' order and dtype."""
     entries = [(a, int(y0), int(x0), int(bh), int(bw), int(turns)) for a, y0, x0, bh, bw, turns in entries]
+    _check_entries('line_crop', [entry[0] for entry in entries])
     for a, y0, x0, bh, bw, turns in entries:
-        if not isinstance(a, DeviceArray) or a.ndim != 4 or a.shape[0] != 1:
-            raise ValueError(f'line_crop: expected (1, H, W, C) device arrays, got {getattr(a, "shape", type(a))}')
         if not (0 <= y0 and 0 <= x0 and bh >= 1 and bw >= 1 and y0 + bh <= a.shape[1] and x0 + bw <= a.shape[2]):
             raise ValueError(f'line_crop: the box [{y0}, {y0 + bh}) x [{x0}, {x0 + bw}) is empty or not inside {a.shape}')
         if not 0 <= turns <= 3:
@@ -1085,9 +1080,7 @@ def pack_lines(lines, strip):
     chosen = [lines[index] for index, _, _ in segments]
     if not chosen:
         raise ValueError('pack_lines: a strip without lines')
-    for a in chosen:
-        if not isinstance(a, DeviceArray) or a.ndim != 4 or a.shape[0] != 1:
-            raise ValueError(f'pack_lines: expected (1, H, W, C) device arrays, got {getattr(a, "shape", type(a))}')
+    _check_entries('pack_lines', chosen)
     code, (_, h, _, c) = _shared_code(chosen, 'pack_lines', 'a dtype'), chosen[0].shape
     if any((a.shape[1], a.shape[3]) != (h, c) for a in chosen) or any(a.shape[2] != w for a, (_, _, w) in zip(chosen, segments)):
         raise ValueError(f'pack_lines: the lines {[a.shape for a in chosen]} do not fit the segments {segments} of one strip')
