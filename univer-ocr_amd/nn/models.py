@@ -5,8 +5,10 @@ params / get_weights / set_weights, nested models flattened to 'parent/child' la
 The reference walks the DAG with memoised recursion on every call.  This executor orders the DAG
 once (`initialize`: `_plan`, the topologically ordered node names) and compiles it once, fusions
 included, into a list of steps (nn/plan.py, at the first forward after the graph or its fusion
-flags changed); forward is one loop over that list and backward one loop over it in reverse, each
-a sequence of asynchronous kernel launches on one HIP stream.  Parameters of the whole model are
+flags changed).  A step runs itself (`step.forward(inputs)`, `step.backward(grad, loss_folded)`):
+forward is one loop over that list and backward one loop over it in reverse, each a sequence of
+asynchronous kernel launches on one HIP stream; this file only routes tensors and gradients between
+the steps.  Parameters of the whole model are
 packed into one flat buffer (layers.ParamPack), which turns `clear_grads`, `regularize`,
 `update_grads`, `nan_weights` and the data-parallel gradient all-reduce into one launch each.
 
@@ -232,28 +234,14 @@ class Model(BaseModel):
         outputs = {}
         zeroed = set()                                # keep_columns: the nodes whose gap columns hold zeros
         for step in self._compiled().steps:
-            kind, layer = step.kind, step.layer
-            args = [inputs[s] if isinstance(s, int) else outputs[s] for s in step.sources]
-            if kind == plan.PLAIN:
-                out = layer.forward(args)
-            elif kind == plan.FUSED:                  # activation in the epilogue and / or folded into dx
-                out = layer.forward_fused(args, step.act) if step.act is not None else layer.forward(args)
-            elif kind == plan.ALIAS:                  # activation absorbed into its producing conv
-                out = outputs[step.alias_of]
-            elif kind == plan.PAIR:
-                out = layer.forward_pair(args[0], step.first, step.first_act, step.act)
-            elif kind == plan.UP:                     # upsample + conv on the low-res tensor
-                out = layer.forward_up(args[0], step.act)
-            elif kind == plan.WINDOWS:                # windows + flatten + dense on the conv feature map
-                out = layer.forward_windows(args[0], step.width, step.act)
-            else:                                     # ABSORBED: computed inside the kernel of its consumer
-                out = None
-            outputs[step.node] = out = out[0] if isinstance(out, list) else out
+            # (an ALIAS hands its producer's array on, an ABSORBED node has no output: None)
+            outputs[step.node] = out = step.forward([inputs[s] if isinstance(s, int) else outputs[s]
+                                                     for s in step.sources])
             if keep_columns is not None and out is not None and out.ndim == 4 and out.shape[0] == inputs[0].shape[0] \
                     and out.shape[2] == inputs[0].shape[2]:   # (the windows of a strip of 8 columns are 8 wide too, but B * 8 of them)
                 # an ALIAS shares its producer's array; LeakyReLU(+0.0) = +0.0 leaves zeroed gaps as they are
-                fresh = kind != plan.ALIAS and not (kind == plan.PLAIN and isinstance(layer, LeakyRelu)
-                                                    and step.sources[0] in zeroed)
+                fresh = step.kind != plan.ALIAS and not (step.kind == plan.PLAIN and isinstance(step.layer, LeakyRelu)
+                                                         and step.sources[0] in zeroed)
                 if fresh:
                     ops.zero_gaps(out, keep_columns)
                 zeroed.add(step.node)
@@ -296,26 +284,8 @@ class Model(BaseModel):
             return total
 
         for step in reversed(self._compiled().steps):
-            kind, layer = step.kind, step.layer
-            if kind == plan.PLAIN:
-                dx = layer.backward(incoming(step.node))
-            elif kind == plan.ALIAS:                  # its gradient is applied inside a conv's backward
-                dx = incoming(step.node)
-            elif kind == plan.PAIR:                   # dW of both convs and dX of the first in one kernel; only the
-                act = None if step.act_node in loss_folded else step.act     # loss kernel can take its Sigmoid over
-                dx = layer.backward_pair(incoming(step.node), step.first, step.first_act, act)
-            elif kind != plan.ABSORBED:               # (an absorbed node's gradient never exists)
-                grad, act = incoming(step.node), step.act
-                # the epilogue activation's derivative: here, unless a consumer's dx kernel or the loss kernel applies it
-                applied = act is not None and (step.act_folded or step.act_node in loss_folded)
-                folds = {'act_grad_applied': applied, 'input_activation': step.in_act}
-                if kind == plan.FUSED:
-                    dx = layer.backward_fused(grad, act, **folds)
-                elif kind == plan.UP:                 # dW, and dX w.r.t. the LOW-RES input, in one go
-                    dx = layer.backward_up(grad, act, **folds)
-                else:                                 # WINDOWS: dW and dX w.r.t. the conv feature map in one go
-                    dx = layer.backward_windows(grad, step.width, act, **folds)
-            if kind != plan.ABSORBED:
+            if step.kind != plan.ABSORBED:            # (an absorbed node's gradient never exists)
+                dx = step.backward(incoming(step.node), loss_folded)
                 grads_mem[step.grad_node] = make_list_if_not(dx)
             if self.bucket_hook is not None:          # data parallel: part of the gradient may be final now
                 self.bucket_hook(self, step.node)

@@ -1,42 +1,220 @@
-"""The step list a Model runs (host only; reference: none -- there every layer is its own pass, on every call).
+"""The step list a Model runs (reference: none -- there every layer is its own pass, on every call).
 
-`compile_steps` decides ONCE which layers run together and returns one `Step` per node of the model's topological
+`compile_steps` decides ONCE which layers run together and returns one step per node of the model's topological
 order; Model.forward walks the list, Model._backward_pass walks it in reverse (every node of that order is reached
-from an output, so every step has a consumer).  Each fusion kind is recognised here and nowhere else:
+from an output, so every step has a consumer).  Each fusion kind is recognised here (`find_*`) and run here (its
+class: `forward(inputs)` and `backward(grad, loss_folded)`, calls into nn/ops.py) and nowhere else:
 
   PLAIN     the layer's own forward / backward
   FUSED     Convolutional2D / FullyConnected with the activation behind it in the epilogue, and / or with the derivative
-            of the fused activation in front of it in its dx epilogue (forward_fused / backward_fused)
+            of the fused activation in front of it in its dx epilogue
   ALIAS     a fused activation: its output IS its producer's (`alias_of`), its backward hands the gradient on
-  PAIR      conv3x3(1->16) + LeakyReLU + conv3x3(16->1) [+ Sigmoid], one kernel each way (forward_pair / backward_pair)
-  UP        Upsample2D(2) + conv on the low-res tensor (forward_up / backward_up)
-  WINDOWS   windows + flatten + dense as one implicit GEMM on the conv feature map (forward_windows / backward_windows)
+  PAIR      conv3x3(1->16) + LeakyReLU + conv3x3(16->1) [+ Sigmoid], one kernel each way
+  UP        Upsample2D(2) + conv on the low-res tensor
+  WINDOWS   windows + flatten + dense as one implicit GEMM on the conv feature map
   ABSORBED  computed inside the PAIR / UP / WINDOWS step that names it in `inside`: no output (None), no launch
+
+What a step saves in its forward for its backward (`x`, its input; `y`, its output) it keeps itself and drops in its
+backward, as a layer does with `_mem`; a second forward without a backward overwrites it.  A step that launches reports
+to its layer's progress tracker under its layer's name, once each way (a PLAIN step through the layer's own methods).
 """
 import numpy as np
 
+from . import ops
+from .gpu import CP
 from .layers import (Conv2DToBatchedFixedWidthed, Convolutional2D, Flatten, FullyConnected, LeakyRelu, Sigmoid,
                      Upsample2D)
+from .progress_tracker import track_method
 
 PLAIN, FUSED, ALIAS, PAIR, UP, WINDOWS, ABSORBED = 'plain', 'fused', 'alias', 'pair', 'up', 'windows', 'absorbed'
 
 
 class Step:
-    """kind; node: whose output it defines; layer: the conv / dense layer (PLAIN: any layer); sources: where its input
-    comes from (model input numbers and node names); inside: the nodes computed within it; grad_node: the node whose
-    input gradient its backward returns (`node` itself, or the first of `inside`); act / act_node: the activation in
-    its epilogue; act_folded: a consumer applies that activation's derivative; in_act: the activation folded into its
-    dx epilogue; first / first_act: the pair's first conv and LeakyReLU; width: of the windows; alias_of: see ALIAS."""
-    __slots__ = ('kind', 'node', 'layer', 'sources', 'inside', 'grad_node', 'act', 'act_node', 'act_folded', 'in_act',
-                 'first', 'first_act', 'width', 'alias_of')
+    """node: whose output it defines; layer: the conv / dense layer (PLAIN: any layer); sources: where its input comes
+    from (model input numbers and node names).  What only some kinds have, None / empty for the others -- inside: the
+    nodes computed within it; act / act_node: the activation in its epilogue; act_folded: a consumer applies that
+    activation's derivative; in_act: the activation folded into its dx epilogue; first / first_act: the pair's first
+    conv and LeakyReLU; width: of the windows; alias_of: see ALIAS."""
+    kind = None
+    inside = ()
+    act = act_node = in_act = first = first_act = width = alias_of = None
+    act_folded = False
 
-    def __init__(self, kind, node, layer, sources=(), inside=(), **more):
-        self.kind, self.node, self.layer, self.sources, self.inside = kind, node, layer, list(sources), tuple(inside)
-        self.grad_node = inside[0] if inside else node
-        self.act = self.act_node = self.in_act = self.first = self.first_act = self.width = self.alias_of = None
-        self.act_folded = False
-        for key, value in more.items():
-            setattr(self, key, value)
+    def __init__(self, node, layer, sources=()):
+        self.node, self.layer, self.sources = node, layer, list(sources)
+
+    grad_node = property(lambda self: self.inside[0] if self.inside else self.node,
+                         doc='the node whose input gradient `backward` returns')
+    name = property(lambda self: self.layer.name)                            # (what track_method reads)
+    progress_tracker = property(lambda self: self.layer.progress_tracker)
+
+
+class Plain(Step):
+    kind = PLAIN
+
+    def forward(self, inputs):
+        out = self.layer.forward(inputs)
+        return out[0] if isinstance(out, list) else out
+
+    def backward(self, grad, loss_folded):
+        return self.layer.backward(grad)
+
+
+class Alias(Step):
+    kind = ALIAS
+
+    def __init__(self, node, layer, alias_of):
+        super().__init__(node, layer, [alias_of])
+        self.alias_of = alias_of
+
+    def forward(self, inputs):
+        return inputs[0]
+
+    def backward(self, grad, loss_folded):                # its derivative is applied inside another step's backward
+        return grad
+
+
+class Absorbed(Step):
+    """(No backward: the gradient of an absorbed node never exists.)"""
+    kind = ABSORBED
+
+    def forward(self, inputs):
+        return None
+
+
+class Pair(Step):
+    """Forward and backward of both convs as one kernel each (csrc/conv_pair.hip); the first conv's 16-channel output
+    is never stored.  `layer` is the second conv."""
+    kind = PAIR
+
+    def __init__(self, node, layer, sources, inside, first, first_act, act_node, act):
+        super().__init__(node, layer, sources)
+        self.inside, self.first, self.first_act = tuple(inside), first, first_act
+        self.act_node, self.act, self.x, self.y = act_node, act, None, None
+
+    @track_method('forward')
+    def forward(self, inputs):
+        a, b = self.first, self.layer
+        self.x = inputs[0]
+        self.y = ops.conv_pair_fwd(self.x, a.w.value, a.b.value, b.w.value, b.b.value, a.padding_value, a.bias, b.bias,
+                                   self.first_act.alpha, ops.ACT_CODES[None if self.act is None else self.act.kind])
+        return self.y
+
+    @track_method('backward')
+    def backward(self, grad, loss_folded):
+        """dW of both convs and dX of the first in one kernel, which applies the derivative of the pair's own Sigmoid:
+        only the loss kernel can take that over (nothing folds across the edge of a pair: compile_steps)."""
+        a, b = self.first, self.layer
+        x, y, self.x, self.y = self.x, self.y, None, None
+        act = None if self.act is None or self.act_node in loss_folded else self.act.kind
+        return ops.conv_pair_bwd(x, y, grad, a.w.value, a.b.value, b.w.value, a.w.grad, a.b.grad, b.w.grad, b.b.grad,
+                                 a.padding_value, a.bias, b.bias, self.first_act.alpha, ops.ACT_CODES[act],
+                                 need_dx=a.needs_input_grad, accumulate=True)
+
+
+class _Epilogue(Step):
+    """What FUSED, UP and WINDOWS share: one op forward with `act` in its epilogue, and backward the op's dW and its dx
+    with the derivative of `in_act` (whose output the step's input is) in the dx epilogue."""
+
+    def __init__(self, node, layer, sources, inside=(), act_node=None, act=None, act_folded=False, in_act=None):
+        super().__init__(node, layer, sources)
+        self.inside, self.act_node, self.act, self.act_folded = tuple(inside), act_node, act, act_folded
+        self.in_act, self.x, self.y = in_act, None, None
+
+    def epilogue(self):
+        """(kind, alpha) of `act` for the forward op."""
+        return (None, 0.0) if self.act is None else (self.act.kind, self.act.alpha)
+
+    def saved(self, grad, loss_folded):
+        """What a backward starts from, the step's hold on it dropped: the input; the gradient w.r.t. what the op
+        computed in front of `act` -- the derivative is taken from the stored output here, unless a consumer's dx
+        kernel (`act_folded`) or the loss kernel (`loss_folded`) applied it --; and (x_act, kind, alpha) for the dx op."""
+        x, y, self.x, self.y = self.x, self.y, None, None
+        if self.act is not None and not (self.act_folded or self.act_node in loss_folded):
+            grad = ops.act_bwd_from_output(self.act.kind, y, grad, self.act.alpha)
+        return x, grad, (None, None, 0.0) if self.in_act is None else (x, self.in_act.kind, self.in_act.alpha)
+
+
+class Fused(_Epilogue):
+    """The pre-activation tensor is never written."""
+    kind = FUSED
+
+    @track_method('forward')
+    def forward(self, inputs):
+        layer, x = self.layer, inputs[0]
+        if isinstance(layer, FullyConnected):
+            y = ops.dense_fwd(x, layer.w.value, *self.epilogue())
+        else:
+            assert x.shape[3] == layer.in_channels
+            y = ops.conv2d_fwd(x, layer.w.value, layer.b.value, layer.stride, layer.padding, layer.padding_value,
+                               layer.bias, *self.epilogue())
+        self.x, self.y = x, y
+        return y
+
+    @track_method('backward')
+    def backward(self, grad, loss_folded):
+        layer = self.layer
+        x, grad, (x_act, kind, alpha) = self.saved(grad, loss_folded)
+        if isinstance(layer, FullyConnected):             # (its op takes x itself as the activation's output)
+            return ops.dense_bwd(x, layer.w.value, grad, layer.w.grad, accumulate=True, x_act=kind, x_alpha=alpha)
+        ops.conv2d_bwd_weight(x, grad, layer.w.grad, layer.b.grad, layer.stride, layer.padding, layer.padding_value,
+                              layer.bias, accumulate=True)
+        if not layer.needs_input_grad:                    # Model.skip_input_grads: nobody reads dX of this layer
+            return None
+        return ops.conv2d_bwd_data(grad, layer.w.value, x.shape, layer.stride, layer.padding, x_act, kind, alpha)
+
+
+class Up(_Epilogue):
+    """The conv evaluated on the low-res tensor (csrc/conv_up.hip); backward returns the gradient w.r.t. that tensor,
+    the upsample's backward included.  float32 with 4 channels: the forward kernel leaves the per-phase weights (576
+    floats, `weff_buf`, allocated at the first forward that needs it) for the backward-data kernel of the same pass
+    (`weff`: same weights)."""
+    kind = UP
+    weff = weff_buf = None
+
+    @track_method('forward')
+    def forward(self, inputs):
+        layer, x = self.layer, inputs[0]
+        assert x.shape[3] == layer.in_channels
+        self.weff = None
+        if layer.in_channels == 4 and x.dtype == np.float32:
+            if self.weff_buf is None:
+                self.weff_buf = CP.empty((576,), np.float32)
+            self.weff = self.weff_buf
+        y = ops.upconv2x_fwd(x, layer.w.value, layer.b.value, layer.padding, layer.bias, *self.epilogue(),
+                             weff=self.weff)
+        self.x, self.y = x, y
+        return y
+
+    @track_method('backward')
+    def backward(self, grad, loss_folded):
+        layer = self.layer
+        x, grad, in_act = self.saved(grad, loss_folded)
+        weff, self.weff = self.weff, None
+        ops.upconv2x_bwd_weight(x, grad, layer.w.grad, layer.b.grad, layer.padding, layer.bias, accumulate=True)
+        return ops.upconv2x_bwd_data(grad, layer.w.value, x.shape, layer.padding, *in_act, weff=weff)
+
+
+class Windows(_Epilogue):
+    """The dense layer as an implicit GEMM on the conv feature map the windows are cut from (ops.windows_dense_*);
+    backward returns the gradient w.r.t. that feature map."""
+    kind = WINDOWS
+
+    def __init__(self, node, layer, sources, inside, width, **epilogue):
+        super().__init__(node, layer, sources, inside, **epilogue)
+        self.width = width
+
+    @track_method('forward')
+    def forward(self, inputs):
+        self.x = inputs[0]
+        self.y = ops.windows_dense_fwd(self.x, self.layer.w.value, self.width, *self.epilogue())
+        return self.y
+
+    @track_method('backward')
+    def backward(self, grad, loss_folded):
+        layer = self.layer
+        x, grad, in_act = self.saved(grad, loss_folded)
+        return ops.windows_dense_bwd(x, layer.w.value, grad, layer.w.grad, self.width, True, *in_act)
 
 
 class StepList:
@@ -177,24 +355,24 @@ def compile_steps(layers, relations, consumers, order, shape_of, outputs_count, 
         act_node = fused_conv.get(node)
         epilogue = dict(act_node=act_node, act=layers.get(act_node), act_folded=act_node in folded)
         if node in absorbed:
-            step = Step(ABSORBED, node, layer)
+            step = Absorbed(node, layer)
         elif node in pairs:                                # (its Sigmoid is never folded: see above)
             first, act_a, _ = pairs[node]
-            step = Step(PAIR, node, layer, relations[first], (first, act_a), first=layers[first],
-                        first_act=layers[act_a], **dict(epilogue, act_folded=False))
+            step = Pair(node, layer, relations[first], (first, act_a), layers[first], layers[act_a], act_node,
+                        layers.get(act_node))
         elif node in ups:
             up, act_in = ups[node]
-            step = Step(UP, node, layer, relations[up], (up,), in_act=layers.get(act_in), **epilogue)
+            step = Up(node, layer, relations[up], (up,), in_act=layers.get(act_in), **epilogue)
         elif node in wins:
             fw, flat, act_in = wins[node]
-            step = Step(WINDOWS, node, layer, relations[fw], (fw, flat), in_act=layers.get(act_in),
-                        width=layers[fw].width, **epilogue)
+            step = Windows(node, layer, relations[fw], (fw, flat), layers[fw].width, in_act=layers.get(act_in),
+                           **epilogue)
         elif node in fused_act:
-            step = Step(ALIAS, node, layer, alias_of=fused_act[node])
+            step = Alias(node, layer, fused_act[node])
         elif node in fused_conv or node in input_of:
-            step = Step(FUSED, node, layer, relations[node], in_act=layers.get(input_of.get(node)), **epilogue)
+            step = Fused(node, layer, relations[node], in_act=layers.get(input_of.get(node)), **epilogue)
         else:
-            step = Step(PLAIN, node, layer, relations[node])
+            step = Plain(node, layer, relations[node])
         steps.append(step)
 
     output_sigmoid = []
