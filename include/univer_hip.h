@@ -617,6 +617,40 @@ int uocr_text_score(uocr_ctx* ctx, int dtype, int n_lines, const void* const* pr
  * null pointer, before anything is written -- tests size their inputs from it */
 int uocr_text_score_limits(int* rows_per_block, int* lines_per_launch, int* columns_per_panel, int* max_width);
 
+/* ---- label overlap: what a mask net found of the true components (the reference's nn/metrics.py has
+ * binary_classification_metrics for 0/1 arrays, which nothing there calls; it has no score of components) ----
+ * Entry i is a pair of int32 label planes a[i], the EXPECTED labels, and b[i], the PREDICTED labels, (h[i], w[i]) each, as
+ * uocr_label_batch writes them: 0 is the background, components are 1, 2, ...  a, b, h, w are HOST arrays; a[i], b[i] are
+ * device pointers (4-byte aligned; the two planes of an entry may differ in their 16-byte alignment).
+ * bucket(l, cap) = l where 0 <= l <= cap, else cap + 1, the OVERFLOW bucket; labels are compared as unsigned, so a
+ * negative label overflows.  All outputs are DEVICE arrays:
+ * overlap: int32 [n_entries][cap_a + 2][cap_b + 2]; overlap[i][r][s] = the pixels p of entry i with bucket(a[p], cap_a)
+ *   = r and bucket(b[p], cap_b) = s.
+ * rows: int32 [n_entries][cap_a + 2][4] = {area, best, inter, other} per row r of the table: area = the sum of the row;
+ *   best = the s in 1 .. cap_b with the largest overlap[r][s] > 0, the smallest s on a tie, 0 when there is none; inter =
+ *   overlap[r][best]; other = the sum of column best; inter = other = 0 where best is 0.
+ * cols: int32 [n_entries][cap_b + 2][4]: the same of the transposed table (best is an r in 1 .. cap_a).
+ * summary: int64 [n_entries][8] = {tp, fp, fn, tn, expected, predicted, matched, overflow}: tp = the cells with r >= 1
+ *   and s >= 1, fp = row 0 without its first cell, fn = column 0 without its first cell, tn = overlap[0][0] (the overflow
+ *   buckets are foreground); expected / predicted = the r in 1 .. cap_a / the s in 1 .. cap_b with area > 0; matched = the
+ *   r in 1 .. cap_a with best > 0 and 2 * inter > area + other - inter, an intersection over union above one half, which
+ *   makes a match mutual and unique; overflow = the pixels with either bucket in the overflow.
+ * With cap_a = cap_b = 0 the table is the 2 x 2 confusion matrix of foreground against foreground.
+ * Every element of all four outputs is written by every successful call (one memset of `overlap`, then two launches per
+ * entries_per_launch entries); none may be NULL.  UOCR_ERR_ARG for null arrays, a null a[i] / b[i], a pointer off its
+ * element's alignment, h[i] or w[i] < 1, a negative cap, n_entries < 0; UOCR_ERR_UNSUPPORTED for a cap above max_cap of
+ * uocr_label_overlap_limits, h[i] * w[i] > INT32_MAX or more blocks than one grid takes.  Nothing is written on any error;
+ * n_entries = 0 is UOCR_OK and launches nothing (the other arguments are not looked at).  No workspace, no allocation,
+ * no copy, no host synchronisation: asynchronous and capturable.  Integer atomics only: results are bit-identical run to
+ * run, and no tolerance applies.  The call leaves no launch report. */
+int uocr_label_overlap(uocr_ctx* ctx, int n_entries, const int* const* a, const int* const* b, const int* h, const int* w,
+                       int cap_a, int cap_b, int* overlap, int* rows, int* cols, long long* summary);
+/* the sizes uocr_label_overlap works with, whatever the context: consecutive pixels of an entry per block of the counting
+ * kernel, the cells of the largest table a block counts in LDS before it adds to the global one (larger tables are added
+ * to directly), entries per launch pair, the largest cap.  UOCR_ERR_ARG for a null pointer, before anything is written --
+ * tests size their inputs from it */
+int uocr_label_overlap_limits(int* pixels_per_block, int* lds_cells, int* entries_per_launch, int* max_cap);
+
 /* ---- the lines of a page in one strip (the Char net over all lines in one pass; the reference runs a pass per line,
  * nn/model_system.py:150-154) ----
  * A strip is (1, h, strip_w, c) in `dtype`; its columns are cut into SEGMENTS [x0[i], x0[i] + w[i]), i < n_lines, with GAPS

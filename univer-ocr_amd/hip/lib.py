@@ -147,6 +147,8 @@ _PROTOS = {
     'uocr_text_score': [_ctx, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), _i, C.POINTER(_i), C.POINTER(_vp),
                         C.POINTER(_vp), _vp],
     'uocr_text_score_limits': [C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
+    'uocr_label_overlap': [_ctx, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _i, _i, _vp, _vp, _vp, _vp],
+    'uocr_label_overlap_limits': [C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     'uocr_pack_lines': [_ctx, _i, _i, C.POINTER(_vp), C.POINTER(_i), _i, _i, C.POINTER(_i), _vp, _i],
     'uocr_zero_gaps': [_ctx, _i, _vp, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i)],
     'uocr_ctx_last_pack_lines': [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],

@@ -61,6 +61,12 @@ the tab and rows without a maximum end a run -- and compared by the unit-cost ed
 table `canonical_ids` maps them to one id (by default the halves of a look-alike pair, whose glyphs the generator draws
 from the same pixels).  All lines of a page are ONE kernel call (nn/ops.py: text_score) and one readback of the scores
 and ids; DESIGN.md section 8 says why the score is not taken between context['text'] and the typed text.
+
+ScoreMasks has none either (nn/metrics.py: binary_classification_metrics is the pixel half of it, and nothing there calls
+it): every channel of a mask net's prediction and of its truth is thresholded by ONE rule -- the rule of the stage that
+reads the net: 'mean' for ParagraphCrop, 'mean_max' for LineCrop, a number for Monochrome --, both are labelled by the
+code the stages use (uocr_label_batch) and the overlap counts of the two label planes give the pixel numbers and how many
+of the true components the prediction found (nn/ops.py: mask_score, uocr_label_overlap).
 """
 import string
 
@@ -411,3 +417,21 @@ class ScoreText:
         text = lambda ids: ''.join(self.chars[i] for i in ids)
         return (nest_like((tuple(int(v) for v in row) for row in scores), predictions),
                 nest_like(map(text, read), predictions), nest_like(map(text, expected), predictions))
+
+
+# the rule each mask net's reader applies, and the cap of its score: Monochrome's 0.5 is foreground against foreground
+MASK_RULES = {'monochrome': (0.5, 0), 'paragraph': ('mean', 64), 'line': ('mean_max', 64)}
+
+
+class ScoreMasks:
+    def __init__(self, rules=MASK_RULES):
+        self.rules = dict(rules)
+
+    def __call__(self, net, prediction, truth):
+        """prediction, truth: (1, H, W, C) DeviceArrays of the net `net` of self.rules.  Returns [MaskScore per channel]:
+        every channel of both thresholded by the net's rule, on its own (a labelling call and an overlap call per net)."""
+        threshold, cap = self.rules[net]
+        prediction, truth = ops.as_device(prediction), ops.as_device(truth)
+        if prediction.shape != truth.shape:
+            raise ValueError(f'ScoreMasks: {net}: a prediction of shape {prediction.shape} for a truth of shape {truth.shape}')
+        return ops.mask_score([((prediction, c), (truth, c)) for c in range(prediction.shape[3])], threshold, cap=cap)

@@ -19,6 +19,7 @@ the upright crop; `rotation_search='device'` lets the device walk that search, o
 TRAIN_CHAR and TRAIN_ALL members of `Modes` are not routed through `make_model_system` and say where their systems are.
 `make_evaluate_system` puts CharLabel in front of Char and TextScore behind PredToText in either chain: what the Char
 net read, scored against the labels that travel with the crops (my_model/evaluate.py adds the lines up).
+`make_mask_evaluate_system` scores the other three nets, each on its true input: [Monochrome, Paragraph, Line, MaskScore].
 """
 from enum import Enum
 
@@ -645,3 +646,46 @@ def make_evaluate_system(input_shape, progress_tracker=None, weights=None, crops
     return _make_page_system('make_evaluate_system', crops, input_shape, None, progress_tracker, weights, char_batching,
                              find_rotation=find_rotation, rotation_search=rotation_search, line_labelling=line_labelling,
                              similar=similar)
+
+
+MASK_NETS = ('monochrome', 'paragraph', 'line')
+MASK_EVALUATE_NAMES = ['Monochrome', 'Paragraph', 'Line', 'MaskScore']
+
+
+def make_mask_score_component(progress_tracker=None, nets=MASK_NETS, target='mask_scores', rules=None):
+    """No counterpart in the reference: for every net of `nets`, context[f'{net}_pred'] is scored against
+    context[f'{net}_y'], both (1, H, W, C): context[target][net][channel] = the MaskScore of that channel (nn/ops.py),
+    prediction and truth thresholded by the rule of the stage that reads the net (my_model/crop.py: MASK_RULES, or
+    `rules`) and labelled by the code the stages use."""
+    from .crop import MASK_RULES, ScoreMasks
+    score_masks = ScoreMasks(MASK_RULES if rules is None else rules)
+
+    @track_function('MaskScore', 'forward', progress_tracker)
+    def mask_score(context):
+        context[target] = {net: score_masks(net, context[f'{net}_pred'], context[f'{net}_y']) for net in nets}
+
+    return RawFunctionComponent(mask_score, score_masks)
+
+
+def make_mask_evaluate_context_maker():
+    """the context of make_mask_evaluate_system from one page of a dataset: every mask net's true input and its truth, the
+    labels TRAIN_PAGE_CONTEXT gives them (image -> monochrome, monochrome -> paragraph, monochrome -> line)"""
+    return _context_maker({label: tag for label, tag in TRAIN_PAGE_CONTEXT.items() if not label.startswith('char')})
+
+
+def make_mask_evaluate_system(input_shape, progress_tracker=None, weights=None, rules=None):
+    """How good the three mask nets are, each on its TRUE input at page size.  Returns (model_system, models, names),
+    names = ['Monochrome', 'Paragraph', 'Line', 'MaskScore']; run it with `predict` on a context of
+    make_mask_evaluate_context_maker: context['mask_scores'][net][channel] is a MaskScore (net = 'monochrome', 'paragraph',
+    'line'; 1, 1 and 2 channels), the predictions stay at context[f'{net}_pred'].  Thresholds are the stages' own --
+    Paragraph 'mean' (ParagraphCrop), Line 'mean_max' per channel (LineCrop), Monochrome the number 0.5 with caps 0,
+    foreground against foreground -- and the truth of each net is thresholded by the rule of its prediction.  input_shape
+    is the page's, (1, H, W, 1) with H and W multiples of 16."""
+    models, components = {}, []
+    for name in MASK_EVALUATE_NAMES[:3]:
+        models[name] = _make_net(name, input_shape, None, progress_tracker, weights)
+        key = name.lower()
+        components.append(ModelComponent(name, models[name], StringSelector(f'{key}_X', None, f'{key}_pred'),
+                                         delist_result=True))
+    components.append(make_mask_score_component(progress_tracker, rules=rules))
+    return ModelSystem(components), models, list(MASK_EVALUATE_NAMES)

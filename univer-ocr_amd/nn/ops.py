@@ -6,6 +6,7 @@ get_output_shapes; arrays returned are always NEW allocations, as in the referen
 """
 import ctypes as C
 import math
+from collections import namedtuple
 
 import numpy as np
 
@@ -992,6 +993,113 @@ def text_score(preds, labels, canon, want_ids=False):
     read = [host[s:s + count].tolist() for s, count in zip(starts[:n], table[:, 2])]
     expected = [host[s:s + count].tolist() for s, count in zip(starts[n:2 * n], table[:, 1])]
     return scores, read, expected
+
+
+# ---- score of the masks: what a mask net found of the true components (nn/metrics.py: binary_classification_metrics is
+# the pixel half; the reference has no score of components) --------------------------------------------------------------
+def label_overlap(pairs, cap_a, cap_b, want_table=False):
+    """The overlap counts of pairs (a, b) of int32 (H, W) label planes, a the expected labels and b the predicted ones as
+    label_batch(labels=True) returns them, whatever the sizes of the pairs.  Labels above a cap, and negative ones, count
+    in the overflow bucket cap + 1.  Returns (summary, rows, cols): int64 (n, 8) = tp, fp, fn, tn, expected, predicted,
+    matched, overflow; int32 (n, cap_a + 2, 4) and (n, cap_b + 2, 4) = area, best, inter, other per row and per column of
+    the table (include/univer_hip.h states the rules); with want_table=True also the tables, int32 (n, cap_a + 2,
+    cap_b + 2), as a fourth item.  ONE uocr_label_overlap call and ONE device-to-host copy -- summary, rows and cols
+    share a buffer, which the tables join only when asked for -- and no call for an empty list."""
+    pairs = [(a, b) for a, b in pairs]
+    cap_a, cap_b = int(cap_a), int(cap_b)
+    if cap_a < 0 or cap_b < 0:
+        raise ValueError(f'label_overlap: cap_a = {cap_a}, cap_b = {cap_b}')
+    for a, b in pairs:
+        for plane in (a, b):
+            if not isinstance(plane, DeviceArray) or plane.ndim != 2 or plane.dtype != np.int32 or plane.size < 1:
+                raise ValueError(f'label_overlap: expected int32 (H, W) device arrays, got '
+                                 f'{getattr(plane, "shape", type(plane))} {getattr(plane, "dtype", "")}')
+        if a.shape != b.shape:
+            raise ValueError(f'label_overlap: the planes of a pair have one shape, got {a.shape} and {b.shape}')
+    n, r, s = len(pairs), cap_a + 2, cap_b + 2
+    sizes = [64 * n, 16 * n * r, 16 * n * s, 4 * n * r * s]           # summary (int64 first), rows, cols, tables
+    starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    if not pairs:
+        empty = (np.zeros((0, 8), np.int64), np.zeros((0, r, 4), np.int32), np.zeros((0, s, 4), np.int32))
+        return empty + (np.zeros((0, r, s), np.int32),) if want_table else empty
+    out = CP.empty((int(starts[4 if want_table else 3]),), np.uint8)
+    tables = None if want_table else CP.empty((n, r, s), np.int32)
+    at = lambda k: C.c_void_p(out.ptr + int(starts[k]))
+    _rt().call('uocr_label_overlap', n, _pointers([a for a, _ in pairs]), _pointers([b for _, b in pairs]),
+               _ints([a.shape[0] for a, _ in pairs]), _ints([a.shape[1] for a, _ in pairs]), cap_a, cap_b,
+               at(3) if want_table else C.c_void_p(tables.ptr), at(1), at(2), at(0))
+    host = out.numpy()
+    piece = lambda k, dtype, shape: host[starts[k]:starts[k + 1]].view(dtype).reshape(shape).copy()
+    result = (piece(0, np.int64, (n, 8)), piece(1, np.int32, (n, r, 4)), piece(2, np.int32, (n, s, 4)))
+    return result + (piece(3, np.int32, (n, r, s)),) if want_table else result
+
+
+_MASK_SCORE_FIELDS = ('tp fp fn tn expected predicted matched overflow rows precision recall f1 accuracy iou '
+                      'mean_matched_iou')
+
+
+class MaskScore(namedtuple('MaskScore', _MASK_SCORE_FIELDS)):
+    """The score of one mask: the eight ints of the summary (pixels: tp, fp, fn, tn, overflow; components: expected,
+    predicted, matched), `rows` = (area, best, inter, other) of every expected component within the cap, as a tuple of
+    tuples of ints, and the numbers derived from the ints on the host: precision, recall, f1 and accuracy by the
+    reference's formulas (nn/metrics.py:13-17), iou = tp / (tp + fp + fn), mean_matched_iou over the matched components;
+    each None where its denominator is 0."""
+    __slots__ = ()
+
+
+def mask_numbers(tp, fp, fn, tn):
+    """precision, recall, f1, accuracy, iou of four pixel counts (ints): nn/metrics.py:13-17 with f1beta = 1, and the
+    intersection over union; None where a denominator is 0"""
+    ratio = lambda numerator, denominator: numerator / denominator if denominator else None
+    precision, recall = ratio(tp, tp + fp), ratio(tp, tp + fn)
+    f1 = None if precision is None or recall is None else ratio(2 * precision * recall, precision + recall)
+    return precision, recall, f1, ratio(tp + tn, tp + tn + fp + fn), ratio(tp, tp + fp + fn)
+
+
+def mask_score_of(summary, rows):
+    """the MaskScore of one entry of label_overlap: its summary (8 ints) and its rows (cap + 2, 4)"""
+    ints = [int(v) for v in summary]
+    inner = [tuple(int(v) for v in row) for row in rows[1:-1] if row[0] > 0]
+    ious = [inter / (area + other - inter) for area, best, inter, other in inner
+            if best > 0 and 2 * inter > area + other - inter]
+    return MaskScore(*ints, tuple(inner), *mask_numbers(*ints[:4]), sum(ious) / len(ious) if ious else None)
+
+
+def mask_score(pairs, threshold, true_threshold=None, cap=64):
+    """How well masks were predicted: pairs of ((pred_array, channel), (true_array, channel)), channels of (1, H, W, C)
+    DeviceArrays as label_batch takes them, a prediction and the truth of one size.  Both sides are thresholded
+    (`threshold` the prediction, `true_threshold` the truth, by default the same rule: 'mean', 'mean_max' or a number)
+    and labelled by uocr_label_batch -- ONE call for all 2n entries where rule and dtype are the same, two otherwise --
+    and the two label planes of every pair go through label_overlap with caps `cap`.  A mask with more than `cap`
+    components is no error: its planes are complete, the excess counts in the overflow bucket (MaskScore.overflow).
+    cap=0 compares foreground with foreground alone.  Returns one MaskScore per pair."""
+    pairs = [((p, int(pc)), (t, int(tc))) for (p, pc), (t, tc) in pairs]
+    cap = int(cap)
+    if cap < 0:
+        raise ValueError(f'mask_score: cap = {cap}')
+    if not pairs:
+        return []
+    true_threshold = threshold if true_threshold is None else true_threshold
+    sides = [[pred for pred, _ in pairs], [true for _, true in pairs]]
+    for entries in sides:
+        _check_entries('mask_score', [a for a, _ in entries])
+        for a, channel in entries:
+            if not 0 <= channel < a.shape[3] or a.shape[1] < 1 or a.shape[2] < 1:
+                raise ValueError(f'mask_score: channel {channel} of an array of shape {a.shape}')
+    for (pred, _), (true, _) in pairs:
+        if pred.shape[1:3] != true.shape[1:3]:
+            raise ValueError(f'mask_score: a prediction of {pred.shape[1:3]} for a truth of {true.shape[1:3]}')
+    rules = [_threshold_args('mask_score', threshold), _threshold_args('mask_score', true_threshold)]
+    planes = [[CP.empty(a.shape[1:3], np.int32) for a, _ in entries] for entries in sides]
+    # the library itself, not label_batch: a count above the room for rows (one row each: none is wanted here) is no error
+    codes = {a.code & 0xff for entries in sides for a, _ in entries}
+    if rules[0] == rules[1] and len(codes) == 1:
+        _label_batch_call(sides[0] + sides[1], *rules[0], 1, planes[0] + planes[1])
+    else:
+        for entries, rule, side_planes in zip(sides, rules, planes):
+            _label_batch_call(entries, *rule, 1, side_planes)
+    summary, rows, _ = label_overlap(zip(planes[1], planes[0]), cap, cap)
+    return [mask_score_of(summary[i], rows[i]) for i in range(len(pairs))]
 
 
 # ---- line crops (interpreter/interpreter.py:504-523: the gather half of LineCrop) -------------------------------------
