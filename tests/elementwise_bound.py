@@ -33,6 +33,9 @@ per-image, a per-8-row-band, a per-24-column-strip and a per-channel exponent.  
 = 33.  binary16: image, band and channel 1 each, and the strips all that the normal range [2^-14, 65504] leaves (8, |e|
 <= 11, weights without a channel exponent: `fit16`); `Problem.check_ranges` asserts that every stored input and every S
 lies in that range.
+
+The weight gradients (dw, db) have a module of their own on top of this one, elementwise_wgrad.py: smaller pages (gamma
+grows with the pixels a weight gradient sums), tol = gamma(n + 8) S + u32 |init + ref|.
 """
 import copy
 import functools

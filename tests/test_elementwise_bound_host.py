@@ -25,12 +25,21 @@ tol is printed), and the wrong implementations each bound must reject -- a Sigmo
 expf clamped at |v| = 16, y (1 - y) from a y rounded once more to binary16, and for the pair's dx a dropped tap at a
 strip border, a flipped decided slope, d_a1 rounded twice and the mask read one row off.  Where rel_linf accepts a
 mutant that the bound rejects the output says so.
+
+The weight gradients (elementwise_wgrad.py) have theirs at the end: the case table reaches every kernel family of the
+weight-gradient ladder with n <= 2048 at both pages; the float32 restatement keeps to HALF of gamma(n + 8) S on every
+element of dw and db; 2^-17 of the neighbouring channel added to every element exceeds the tolerance while its rel_linf
+stays below the 2e-5 the other tests allow; the binary16 inputs with their gradient scale are normal; a contested slope
+of the pair dominates at most 5 % of dw1 / db1.
 """
 import numpy as np
 import pytest
 
 import elementwise_bound as B
+import elementwise_wgrad as W
 from conftest import rel_linf
+from test_gpu_conv_padding import WGRAD, expect_kernel
+from test_gpu_gemm_configs import expect_gemm, expect_group
 
 
 def test_gamma_and_tolerance_terms():
@@ -278,4 +287,103 @@ def test_case_has_room_is_new_and_rejects_the_mutations(index):
         for what, err in (('constant leak', l_leak), ('sliding sum', l_slide)):
             if not err <= allow:
                 failures.append(f'{name}: rel_linf rejects the {what} mutation too ({err:.2e}): nothing new shown')
+    assert not failures, '\n'.join(failures)
+
+
+# ---- weight gradients (elementwise_wgrad.py) ------------------------------------------------------------------------------
+def test_the_weight_gradient_table():
+    """Every kernel family of the weight-gradient ladder runs; every case sums at most 2048 terms; each configuration has
+    the w % 4 == 0 page and the ragged one."""
+    ids = set(W.WCASE_IDS)
+    assert len(ids) == len(W.WCASES)
+    seen = {c.kernel[1] for c in W.WCASES if c.kernel is not None and c.kernel[0] == WGRAD}
+    want = {'table_fast', 'c16_wgrad', 'wgrad_t542', 'wgrad_s2_tiled', 'h16_wgrad', 'h16_wgrad_s2', 'mfma', 'generic'}
+    assert want <= seen, sorted(want - seen)
+    for c in W.WCASES:
+        p = c.problem
+        assert p.terms() <= W.MAX_TERMS, (c.id, p.terms())
+        if isinstance(p, W.ConvWgradProblem):
+            assert c.kernel == (WGRAD, expect_kernel(WGRAD, p.dtype, p.d, p.pad_value, c.opts)), c.id
+    assert W.SHAPES[0][2] % 4 == 0 and W.SHAPES[1][2] % 4 != 0 and W.SHAPES[1][2] > 2 * 64 and W.SHAPES[1][2] % 64
+    # bands of four output rows: whole ones and, at stride 2, a short last one; short last ones at either stride
+    assert W.SHAPES[0][0] > 1 and W.SHAPES[0][1] % 4 == 0 and (W.SHAPES[0][1] // 2) % 4 and W.SHAPES[1][1] % 4
+    assert all(2 * a[2] == b[2] or 2 * a[2] == b[2] + 1 for a, b in zip(W.LOW_SHAPES, W.SHAPES))
+    pages = {}
+    for c in W.WCASES:
+        p = c.problem
+        if isinstance(p, (W.ConvWgradProblem, W.UpWgradProblem, W.PairWgradProblem)):
+            key = c.id.replace(p.name, type(p).__name__ + p.name.split('-')[0])
+            pages.setdefault(key, set()).add(p.q['x'].shape[:3])
+    assert all(len(v) == 2 for v in pages.values()), pages
+    for i in range(len(B.TABLE)):
+        for shape in W.SHAPES:
+            tag = f'{shape[0]}x{shape[1]}x{shape[2]}'
+            assert {f'32-table{i}-{tag}-dw', f'32-table{i}-{tag}-dw-t32_0-tiled0', f'16-table{i}-{tag}-dw',
+                    f'16-table{i}-{tag}-dw-h16_0'} <= ids
+    assert {'32-mfma-3x20x32-dw-mfma2', '32-generic-1x13x141-dw', '32-up4-3x10x16-dw', '16-up1-1x6x71-dw', '32-dense-dw',
+            '32-dense-dw-mfma2', f'32-dense{W.SLAB_ROWS}-dw', '32-windows-dw', '32-pair-3x20x32-dw',
+            '32-pair-1x13x141-dw-sigmoid'} <= ids
+    # the dense case that must split its depth: two or more slabs under the host rule, alone and as two of a group
+    (c,) = [c for c in W.WCASES if c.gemm is not None]
+    assert 1000 <= c.gemm[2] <= 2040 and c.problem.rows == c.gemm[2]
+    for cu in (64, 256, 304):
+        assert expect_gemm(*c.gemm, True, cu, 128 << 20, c.opts)[3] >= 2
+        assert min(expect_group([c.gemm] * 2, cu, 128 << 20, 0, c.opts['split_blocks'], c.opts['split_min'])) >= 2
+
+
+def test_weight_gradient_tolerance_terms():
+    p = W.wproblem('table', 'float32', 7, 0)
+    s, n = p.sums['dw']
+    assert n == 3 * 20 * 32 and np.array_equal(p.tolerances()['dw'], B.gamma(n + 8) * s)
+    acc = p.tolerances(True)['dw']
+    assert np.array_equal(acc, B.gamma(n + 8) * s + 2.0 ** -24 * np.abs(p.init['dw'] + p.ref['dw']))
+    r = p.init['dw'] / p.ref['dw']
+    assert np.all((np.abs(r) > 0.2499) & (np.abs(r) < 1.0001)) and (r > 0).any() and (r < 0).any()
+    assert np.array_equal(p.init['dw'].astype(np.float32).astype(np.float64), p.init['dw'])
+    off = W.wproblem('table', 'float32', 0, 0)                      # no bias: ref 0, tolerance 0, only the exact value passes
+    assert not off.bias and np.all(off.ref['db'] == 0) and np.all(off.tolerances()['db'] == 0) and np.all(off.init['db'] != 0)
+    assert W.ratio(np.zeros(16), off.ref['db'], off.tolerances()['db']).max() == 0
+    assert W.ratio(np.full(16, 1e-30), off.ref['db'], off.tolerances()['db']).max() == np.inf
+    assert W.ratio(np.full(16, np.nan), off.ref['db'], off.tolerances()['db']).max() == np.inf
+
+
+@pytest.mark.parametrize('index', range(len(W.WCASES)), ids=W.WCASE_IDS)
+def test_weight_gradient_case_has_room_and_rejects_the_leak(index):
+    """Room: the float32 NumPy restatement (the pair: through the kernel's rounding points) stays within HALF of the
+    tolerance on every element of every output.  The leak mutant: 2^-17 of the neighbouring channel's value added to every
+    element of dw (db) exceeds the tolerance somewhere, and rel_linf < 2e-5 accepts it.  binary16: x and 2^k dy lie in the
+    normal range, k > 0.  The pair: a contested slope dominates the tolerance of at most 5 % of dw1 / db1."""
+    c = W.WCASES[index]
+    p = c.problem
+    p.check_ranges()
+    tols, acc, low = p.tolerances(), p.tolerances(True), p.restated()
+    leaks, asserted = W.leak_ratios(p), W.leak_asserted(p)
+    failures = []
+    for name in p.outputs:
+        ref, tol = p.ref[name], tols[name]
+        assert tol.shape == ref.shape == acc[name].shape and np.all(tol >= 0) and np.all(acc[name] > 0)
+        assert np.all((tol > 0) | (ref == 0))
+        room = float(W.ratio(low[name], ref, tol).max())
+        with np.errstate(divide='ignore', invalid='ignore'):
+            loose = float(np.nanmax(np.where(ref != 0, tol / np.abs(ref), 0.0)))
+        line = f'{c.id} {name}: n = {p.terms()}, k = {p.gscale}, restatement / tol {room:.4f}, largest tol / |ref| {loose:.3g}'
+        if not room <= 0.5:
+            failures.append(f'{name}: the float32 restatement reaches {room:.3f} of the bound (> 0.5)')
+        if name in leaks:
+            lin = rel_linf(p.leaked(name), ref)
+            line += f'; leak {leaks[name]:.3g} of the bound, rel_linf {lin:.2e}' + ('' if name in asserted else ' (not asserted)')
+            if name in asserted and not leaks[name] > 1.0:
+                failures.append(f'{name}: the leak mutant passes the bound ({leaks[name]:.3g})')
+            if not lin < W.ALLOW_W:
+                failures.append(f'{name}: rel_linf rejects the leak mutant too ({lin:.2e}): nothing new shown')
+        else:
+            line += '; no leak mutant (a single channel, or a switched-off bias)'
+        if isinstance(p, W.PairWgradProblem) and name in ('dw1', 'db1'):
+            share = p.widened_share(name)
+            line += f'; widening above the arithmetic part on {share:.2%}, contested slopes {int(p.dx.parts["flip"].sum())}'
+            if not share <= W.WIDEN_CAP:
+                failures.append(f'{name}: a contested slope dominates {share:.2%} of the elements (> 5 %)')
+        print(line)
+    multi = any(p.leak_axis(k) is not None for k in p.outputs)
+    assert bool(asserted) == multi, (c.id, asserted)     # every case with a neighbouring channel has an asserted mutant
     assert not failures, '\n'.join(failures)

@@ -42,14 +42,30 @@ dx of the pair with every pixel judged (PAIR_DX_CASES): float32, and the binary1
 and with one band per image.  The kernel's rounding points are restated on the host; a pixel that a slope the kernel
 may take otherwise than the oracle reaches gains (1 - alpha)(|ga1| + Ega) |w1[tap]|; none is left out.
 
+Weight gradients (elementwise_wgrad.WCASES; that module derives the bound tol = gamma(n + 8) S + u32 |init + ref| and
+says why its pages are small: n = N OH OW <= 2048, at (3, 20, 32) and (1, 13, 141); upconv inputs (3, 10, 16) and (1, 6,
+71)): dw and db of the nine table configurations (float32 under the default dispatch and with t32 = 0, tiled = 0;
+binary16 with h16 = 1 and 0, dy carrying a gradient scale 2^k), of the MFMA conv and the generic conv, of upconv2x 4 -> 4
+and 1 -> 1 in both types, of dense_bwd (the generic GEMM, the MFMA GEMM, and 1 500 rows whose depth the MFMA GEMM
+splits: `Runtime.last_gemm` must report the slabs test_gpu_gemm_configs.expect_gemm / expect_group predict) and
+windows_dense_bwd, and dw1 / db1 / dw2 / db2 of the float32 conv_pair_bwd with act2 none and Sigmoid.  Every case runs
+with max_blocks 0 and 3, overwriting NaN-filled buffers and accumulating onto init = float32(ref r), with the producer's
+own finish and inside `with rt.defer_wgrad():`, where the call is issued TWICE into two sets of buffers so that the
+group kernels run two recorded finishes (GEMMs), the second at a non-zero `first_block`; both sets are judged.  Not
+covered: the binary16 pair weight gradients (elementwise_wgrad says why).
+
 The largest err / tol of every output is printed before it is judged.
 """
+import contextlib
+
 import numpy as np
 import pytest
 
 import elementwise_bound as B
+import elementwise_wgrad as W
 from conftest import rel_linf
 from test_gpu_conv_padding import DEFAULTS, DGRAD, FWD, KERNELS, KID, ctx  # noqa: F401  (ctx: the NaN-filling fixture)
+from test_gpu_gemm_configs import GEMM_DEFAULTS, WS_HALF, expect_gemm, expect_group
 
 pytestmark = pytest.mark.gpu
 
@@ -217,4 +233,106 @@ def test_pair_dx_every_pixel_within_the_bound(index, ctx):
     c = B.PAIR_DX_CASES[index]
     c = c._replace(outputs=('dx', 'dx_accumulate'))
     failures = judge(ctx, c, ((), (('pair_band', c.problem.q['x'].shape[1]),)))
+    assert not failures, '\n'.join(failures)
+
+
+# ---- weight gradients ----------------------------------------------------------------------------------------------------
+def wgrad_call(CP, c):
+    """call(buffers, accumulate): the case's weight-gradient op into `buffers` = {output: float32 DeviceArray}"""
+    from univer_ocr_amd.hip import lib as hiplib
+    from univer_ocr_amd.nn import ops
+    p = c.problem
+    dev = lambda k: CP.copy(p.device(k))
+    par = lambda k: CP.copy(p.q[k], np.float32)
+    if isinstance(p, W.PairWgradProblem):
+        x, g, yout = dev('x'), dev('g'), dev('yout')
+        w1, b1, w2 = (par(k) for k in ('w1', 'b1', 'w2'))
+        act2 = hiplib.ACT_SIGMOID if p.sig else hiplib.ACT_NONE
+        return lambda b, acc: ops.conv_pair_bwd(x, yout, g, w1, b1, w2, b['dw1'], b['db1'], b['dw2'], b['db2'], p.pad1, True,
+                                                True, B.ALPHA, act2, need_dx=True, accumulate=acc)
+    x, g = dev('x'), dev('g')
+    if p.half:
+        g.gscale = p.gscale                     # dy is stored times 2^k; the kernels divide dw / db by it
+    if isinstance(p, W.ConvWgradProblem):
+        d = p.d
+        return lambda b, acc: ops.conv2d_bwd_weight(x, g, b['dw'], b['db'], (d.sh, d.sw), (d.ph, d.pw), p.pad_value, p.bias,
+                                                    accumulate=acc)
+    if isinstance(p, W.UpWgradProblem):
+        return lambda b, acc: ops.upconv2x_bwd_weight(x, g, b['dw'], b['db'], (2, 2), True, accumulate=acc)
+    w = par('w')
+    if isinstance(p, W.DenseWgradProblem):
+        return lambda b, acc: ops.dense_bwd(x, w, g, b['dw'], accumulate=acc, need_dx=False)
+    assert isinstance(p, W.WindowsWgradProblem)
+    return lambda b, acc: ops.windows_dense_bwd(x, w, g, b['dw'], B.WIN_WIDTH, accumulate=acc)
+
+
+def judge_wgrad(CP, c):
+    """every launch form of case `c` (module docstring): last_conv, last_gemm where the case names a GEMM, and every
+    element of every output of every set of buffers; returns the misses"""
+    rt = CP.runtime()
+    p = c.problem
+    options = dict(DEFAULTS)
+    options.update(GEMM_DEFAULTS)
+    options.update(c.opts)
+    for key, value in options.items():
+        rt.set_option(key, value)
+    CP.set_dtype(p.dtype)
+    call = wgrad_call(CP, c)
+    cu = rt.device_info()['cu_count']
+    failures = []
+    try:
+        for cap in CAPS:
+            for accumulate in (False, True):
+                tols = p.tolerances(accumulate)
+                for deferred in (False, True):
+                    what = f'{c.id} max_blocks={cap} accumulate={accumulate} ' + ('deferred' if deferred else 'own finish')
+                    sets = [{k: CP.copy(p.init[k], np.float32) if accumulate else CP.empty(p.ref[k].shape, np.float32)
+                             for k in p.outputs} for _ in range(2 if deferred else 1)]
+                    rt.set_option('max_blocks', cap)
+                    try:
+                        with rt.defer_wgrad() if deferred else contextlib.nullcontext():
+                            for buffers in sets:
+                                call(buffers, accumulate)
+                                noted = rt.last_conv()
+                                if c.kernel is not None and noted != (c.kernel[0], KID[c.kernel[1]]):
+                                    failures.append(f'{what}: last_conv {noted} ({KERNELS[noted[1]]}) != {c.kernel}')
+                    finally:
+                        rt.set_option('max_blocks', 0)
+                    if c.gemm is not None:
+                        got = rt.last_gemm()
+                        if deferred:
+                            splits = expect_group([c.gemm] * len(sets), cu, WS_HALF, 0, options['split_blocks'],
+                                                  options['split_min'])
+                            want, group = (64, 0, 0, max(splits)), (len(sets), sum(s > 1 for s in splits))
+                            if rt.last_gemm_group() != group:
+                                failures.append(f'{what}: last_gemm_group {rt.last_gemm_group()} != {group}')
+                        else:
+                            want = expect_gemm(*c.gemm, True, cu, WS_HALF, options)
+                        print(f'{what}: last_gemm {got}')
+                        if got != want or want[3] < 2:
+                            failures.append(f'{what}: last_gemm {got} != host rule {want} with two or more slabs')
+                    for i, buffers in enumerate(sets):
+                        for name in p.outputs:
+                            host = CP.asnumpy(buffers[name])
+                            want, tol = p.expected(name, accumulate), tols[name]
+                            assert host.shape == want.shape and host.dtype == np.float32, (what, name, host.shape, host.dtype)
+                            r = W.ratio(host, want, tol)
+                            at = tuple(int(j) for j in np.unravel_index(np.argmax(r), r.shape))
+                            print(f'{what} set {i} {name}: largest err / tol {r.max():.3f} at {at} (rel_linf '
+                                  f'{rel_linf(np.nan_to_num(host.astype(np.float64)), want):.2e}, NaN {int(np.isnan(host).sum())})')
+                            if not r.max() <= 1.0:
+                                failures.append(f'{what} set {i} {name}: err / tol = {r.max():.3f} at {at}, '
+                                                f'{int((r > 1.0).sum())} of {r.size} elements over')
+    finally:
+        for key, value in GEMM_DEFAULTS:
+            rt.set_option(key, value)
+    return failures
+
+
+@pytest.mark.parametrize('index', range(len(W.WCASES)), ids=W.WCASE_IDS)
+def test_every_weight_gradient_element_within_the_derived_bound(index, ctx):
+    """dw / db of every weight-gradient kernel under tol = gamma(n + 8) S + u32 |init + ref| (elementwise_wgrad.py), in
+    every launch form: max_blocks 0 and 3, overwriting and accumulating, the producer's own finish and the deferred
+    group with two recorded calls."""
+    failures = judge_wgrad(ctx, W.WCASES[index])
     assert not failures, '\n'.join(failures)
