@@ -14,12 +14,13 @@ namespace {
 
 // store a gradient value: binary16 saturates at its largest finite number instead of overflowing to inf (the power-of-two
 // gradient scale of UOCR_F16 is static; a sparse channel early in training can exceed 65504 / 2^k -- an inf would
-// become NaN in dw and in the weights)
+// become NaN in dw and in the weights).  A NaN stays a NaN: fmaxf / fminf return their other operand for one, which
+// would store -65504 and hide a diverged step from Model.nan_weights
 template <typename T, typename V>
 __device__ __forceinline__ T grad_store(V v) {
     if constexpr (std::is_same<T, _Float16>::value) {
         const float f = (float)v;
-        return (T)fminf(fmaxf(f, -65504.f), 65504.f);
+        return f != f ? (T)f : (T)fminf(fmaxf(f, -65504.f), 65504.f);
     } else {
         return (T)v;
     }

@@ -98,11 +98,12 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
                 if (ox >= d.ow) continue;
                 const uint8_t* cell = mask + ((size_t)b * d.oh * d.kh + (size_t)oy * d.kh) * mrow +
                                       (size_t)ox * d.kw * d.c + ch;
-                if (!cell[(size_t)ky * mrow + (size_t)kx * d.c]) continue;
                 int cnt = 0;
                 for (int a = 0; a < d.kh; ++a)
                     for (int e = 0; e < d.kw; ++e) cnt += cell[(size_t)a * mrow + (size_t)e * d.c];
-                acc += dy[(((size_t)b * d.oh + oy) * d.ow + ox) * d.c + ch] / (T)cnt;
+                // the reference's product share * mask, not a select: a NaN or Inf in dy reaches every position of its
+                // window, and a window whose maximum is NaN (no bit set: cnt == 0) gives NaN
+                acc += dy[(((size_t)b * d.oh + oy) * d.ow + ox) * d.c + ch] / (T)cnt * (T)(int)cell[(size_t)ky * mrow + (size_t)kx * d.c];
             }
         }
         dx[idx] = acc;
@@ -152,8 +153,9 @@ __global__ __launch_bounds__(256) void maxpool2_fwd_vec(const float4* __restrict
 }
 
 __device__ __forceinline__ float4 pool_scatter4(uint32_t m, const float4& g) {
-    return make_float4((m & 0xffu) ? g.x : 0.f, (m & 0xff00u) ? g.y : 0.f, (m & 0xff0000u) ? g.z : 0.f,
-                       (m & 0xff000000u) ? g.w : 0.f);
+    // the reference's product share * mask, not a select (see maxpool_bwd_kernel)
+    return make_float4(g.x * (float)(m & 0xffu), g.y * (float)((m >> 8) & 0xffu), g.z * (float)((m >> 16) & 0xffu),
+                       g.w * (float)(m >> 24));
 }
 
 __global__ __launch_bounds__(256) void maxpool2_bwd_vec(const float4* __restrict__ dy, const uint32_t* __restrict__ mask,
@@ -167,7 +169,7 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_vec(const float4* __restrict
         const size_t rq = (size_t)2 * ow * cq;
         const size_t i00 = (row * 2) * rq + (size_t)(2 * ox) * cq + q;
         const uint32_t ma = mask[i00], mb = mask[i00 + cq], mc = mask[i00 + rq], md = mask[i00 + rq + cq];
-        const uint32_t cnt = ma + mb + mc + md;         // per byte: 1..4 set bits (the max itself is always set)
+        const uint32_t cnt = ma + mb + mc + md;         // per byte: 1..4 set bits, 0 where the maximum is NaN
         float4 g = dy[idx];
         g.x /= (float)(cnt & 0xffu);
         g.y /= (float)((cnt >> 8) & 0xffu);
