@@ -31,6 +31,12 @@ weight-gradient ladder with n <= 2048 at both pages; the float32 restatement kee
 element of dw and db; 2^-17 of the neighbouring channel added to every element exceeds the tolerance while its rel_linf
 stays below the 2e-5 the other tests allow; the binary16 inputs with their gradient scale are normal; a contested slope
 of the pair dominates at most 5 % of dw1 / db1.
+
+The binary16 pair at its kernels' own roundings (elementwise_bound.Pair16Steps) comes last: the pages reach every launch
+form of both backward kernels; the float32 restatement has room, the widening dominates at most 5 % of any output, and
+five mutants are rejected: the 2^-17 channel leak (inside the 2e-4 rel_linf of test_gpu_pair_forms.py), a halo column
+and a band's overlap row summed twice, the wave kernel with the strip kernel's slope-and-product rule and with alpha
+unrounded in d_a1.
 """
 import numpy as np
 import pytest
@@ -40,6 +46,7 @@ import elementwise_wgrad as W
 from conftest import rel_linf
 from test_gpu_conv_padding import WGRAD, expect_kernel
 from test_gpu_gemm_configs import expect_gemm, expect_group
+from test_gpu_pair_forms import TOL_SUM16, expect_pair
 
 
 def test_gamma_and_tolerance_terms():
@@ -386,4 +393,147 @@ def test_weight_gradient_case_has_room_and_rejects_the_leak(index):
         print(line)
     multi = any(p.leak_axis(k) is not None for k in p.outputs)
     assert bool(asserted) == multi, (c.id, asserted)     # every case with a neighbouring channel has an asserted mutant
+    assert not failures, '\n'.join(failures)
+
+
+# ---- the binary16 pair at its own roundings (elementwise_bound.Pair16Steps) -------------------------------------------------
+HOST_CU = 256                                   # compute units the launch rules are evaluated with here
+
+
+def test_the_binary16_pair_table():
+    """The pages are the smallest at which each launch form of the two binary16 backward kernels still runs: the
+    cooperative kernel (4) at several images, a ragged width with and without a padding value (MODE 1) and two whole
+    waves at pad1 0 (MODE 0); the wave kernel (5) at 600 columns -- ten strips, three blocks with two live strips in the
+    last, a ragged last strip -- at 560 -- nine strips, the last ends on the page -- and at three images of one row; at
+    three rows pair_band 2 gives two bands, the second with one row.  Every page sums at most 2048 terms."""
+    assert len(set(W.PAIR16_IDS)) == len(W.PAIR16_KEYS) == 2 * len(W.PAIR16_PAGES)
+    pages = {(k, s, pad) for k, s, pad in W.PAIR16_PAGES}
+    assert {('strip', (3, 20, 32), 0.25), ('strip', (1, 13, 141), 0.0), ('strip', (1, 13, 141), 0.25), ('strip', (2, 8, 128), 0.0),
+            ('wave', (1, 3, 600), 0.0), ('wave', (1, 3, 600), 0.25), ('wave', (1, 3, 560), 0.0), ('wave', (3, 1, 560), 0.25)} == pages
+    for kernel, (n, h, w), pad1 in W.PAIR16_PAGES:
+        assert n * h * w <= W.MAX_TERMS
+        for g in (4, 2):
+            form, det = expect_pair('bwd', 'float16', n, h, w, pad1, {'pair_g': g}, HOST_CU)
+            assert form[0] == (5 if kernel == 'wave' else 4), (kernel, w, form)
+            assert form[1] == (g if kernel == 'wave' else 4)
+            if kernel == 'strip':
+                assert form[2] == (0 if (w, pad1) == (128, 0.0) else 1), (w, pad1, form)
+    assert expect_pair('bwd', 'float16', 1, 3, 600, 0.0, {}, HOST_CU)[1] == dict(nstrips=10, last_live=2, last_band=3)
+    assert expect_pair('bwd', 'float16', 1, 3, 560, 0.0, {}, HOST_CU)[1]['nstrips'] == 9 and 8 * 62 + 64 == 560 < 9 * 62 + 64
+    assert 9 * 62 + 64 > 600                                                 # the tenth strip is ragged
+    form, det = expect_pair('bwd', 'float16', 1, 3, 600, 0.0, {'pair_band': 2}, HOST_CU)
+    assert form[6:] == (2, 2) and det['last_band'] == 1
+    assert expect_pair('bwd', 'float16', 3, 20, 32, 0.25, {'pair_band': 2}, HOST_CU)[0][6] > 1
+    assert {(s, pad) for s, pad, _ in B.PAIR_WAVE_DX_KEYS} == {((2, 11, 600), 0.25), ((1, 3, 560), 0.0)}
+    assert expect_pair('bwd', 'float16', 2, 11, 600, 0.25, {}, HOST_CU)[0][0] == 5
+    assert B.A16 != B.A32 and abs(B.A16 / B.ALPHA - 1) < 2.0 ** -11 and B.r16(0.25) == 0.25
+
+
+def test_the_two_kernels_rounding_rules():
+    """The restated activation of either kernel on hand-picked values: the wave kernel rounds first and reads the sign bit
+    (a z that rounds to -0 takes alpha), multiplies by alpha16; the strip kernel compares the float32 z with 0 (-0 takes
+    1), multiplies by the float32 alpha and rounds once.  An interval's endpoints enclose its nominal value."""
+    z = np.array([-1e-9, 1e-9, -0.0, -1.0, 3.0, -1.0 - 2.0 ** -12])
+    s = np.array([2.0, 2.0, 2.0, 1.0 + 2.0 ** -10, 5.0, 1.0 + 2.0 ** -10 + 2.0 ** -13])
+    a, neg = B.pair16_leaky('wave', z, np.float64)
+    assert list(neg) == [True, False, True, True, False, True] and a[0] == 0 and a[3] == -B.A16 and a[4] == 3.0
+    d = B.pair16_masked('wave', s, neg, np.float64)
+    assert d[0] == B.r16(2.0 * B.A16) and d[1] == 2.0 and d[3] == B.r16((1.0 + 2.0 ** -10) * B.A16)
+    assert d[5] == d[3] and a[5] == a[3]                              # rounded FIRST: the bits below binary16 are gone
+    a, neg = B.pair16_leaky('strip', z, np.float64)
+    assert list(neg) == [True, False, False, True, False, True] and a[3] == B.r16(-B.A32) and a[5] == B.r16((-1.0 - 2.0 ** -12) * B.A32)
+    d = B.pair16_masked('strip', s, neg, np.float64)
+    assert d[2] == 2.0 and d[5] == B.r16(s[5] * B.A32) and d[3] == B.r16(s[3] * B.A32)
+    assert B.r16(B.A16) == B.A16 and B.r16(B.A32) == B.A16 and B.A32 != B.ALPHA
+    t = B.Interval(np.array([1.0, -3.0]), np.array([1.5, -2.0]), np.array([2.0, 1.0]))
+    assert list(t.width) == [1.0, 4.0] and list(t.mag) == [2.0, 3.0]
+
+
+def _judge_pair16(st, outputs, what):
+    """room, caps and mutants of one Pair16Steps over `outputs`; returns the failures"""
+    st.check_ranges()
+    assert st.gscale > 0
+    sh = st.shares()
+    print(f'{what}: seed {st.base.seed}, k = {st.gscale}, n = {st.terms}; contested a1 {sh["a1"]:.2%}, d_a1 {sh["d_a1"]:.2%}, '
+          f'g {sh["g"]:.2%}, slopes {sh["slopes"]:.2%}')
+    failures = []
+    low, unstored = st.restated(), st.restated(store=False)
+    for name in outputs:
+        ref, (arith, widen) = st.ref[name], st.parts[name]
+        tol = st.tolerances()[name]
+        assert tol.shape == ref.shape and np.all(tol >= 0) and np.all((tol > 0) | (ref == 0))
+        if name == 'dx':
+            arith = arith + B.U16 * np.abs(ref) + B.FLOOR16      # the store is part of what every pixel is allowed
+            plain, room = st.room(unstored[name], name, store=True)
+            stored = st.room(low[name], name, store=True)[0]
+        else:
+            plain, room = st.room(low[name], name)
+            stored = plain
+        share = st.widened_share(name)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            rel = np.where(ref != 0, tol / np.abs(ref), np.nan)
+            most = float(np.nanmax(np.where(arith > 0, widen / arith, 0.0)))
+        print(f'    {name}: restatement / tol {plain:.4f} (beyond the widening {room:.4f}; stored {stored:.3f}), widening above the '
+              f'arithmetic part on {share:.2%} (largest widening / arithmetic {most:.2f}), median tol / |ref| {np.nanmedian(rel):.1e}')
+        if name != 'dx' and not plain <= 0.5:
+            failures.append(f'{name}: the float32 restatement reaches {plain:.3f} of the bound (> 0.5)')
+        if not room <= 0.5:
+            failures.append(f'{name}: beyond its widening the float32 restatement reaches {room:.3f} of the bound (> 0.5)')
+        if not stored <= 1.0:
+            failures.append(f'{name}: the float32 restatement, stored, reaches {stored:.3f} of the bound (> 1)')
+        if not share <= W.WIDEN_CAP:
+            failures.append(f'{name}: the widening exceeds the arithmetic part on {share:.2%} of the elements (> 5 %)')
+    mutants = (('halo', 'row') if 'dw1' in outputs else ()) + (B.WAVE_RULE_MUTANTS if st.kernel == 'wave' else ())
+    for m in mutants:
+        if m == 'row' and st.overlap_row() is None:
+            print('    row: the page has one row, no band overlaps another')
+            continue
+        r = {k: v for k, v in B.pair16_mutant_ratios(st, m).items() if k in outputs or k == 'dx'}
+        print(f'    {m}: ' + ', '.join(f'{k} {v:.3g}' for k, v in r.items()) + ' of the bound')
+        if not max(r.values()) > 1.0:
+            failures.append(f'the mutant "{m}" passes the bound ({max(r.values()):.3g})')
+    return failures
+
+
+@pytest.mark.parametrize('index', range(len(W.PAIR16_KEYS)), ids=W.PAIR16_IDS)
+def test_binary16_pair_case_has_room_and_rejects_the_mutants(index):
+    """dw1, db1, dw2, db2 (and the dx of the same launch) of the binary16 pair at the kernel's own roundings, shapes (3,
+    20, 32), (1, 13, 141), (2, 8, 128) for the cooperative kernel and (1, 3, 600), (1, 3, 560), (3, 1, 560) for the wave
+    kernel: the float32 restatement stays within room <= 0.5 of the tolerance; the elements whose widening exceeds the
+    arithmetic part stay within WIDEN_CAP (5 %); k > 0 and every rounded quantity is in range.  Mutants: the 2^-17
+    neighbouring-channel leak reaches VISIBLE tolerances on dw1 and dw2 while its rel_linf stays inside the 2e-4 that
+    test_gpu_pair_forms.py allows (the gap this closes; db1 is printed, no seed shows it reliably); one halo column summed
+    twice into all four outputs; the overlap row between two bands summed twice; and for the wave kernel its restatement
+    fed the strip kernel's slope-and-product rule, and alpha unrounded in d_a1 -- these two show on dx (elementwise_bound,
+    "Seeds", says why no weight gradient can show them)."""
+    p = W.pair16_problem(*W.PAIR16_KEYS[index])
+    assert '16-' + p.name == W.PAIR16_IDS[index] and p.terms() <= W.MAX_TERMS
+    failures = _judge_pair16(p.steps, p.outputs + ('dx',), W.PAIR16_IDS[index])
+    low = p.restated()
+    acc = p.tolerances(True)
+    leaks = W.leak_ratios(p)
+    assert set(leaks) == {'dw1', 'db1', 'dw2'} and W.leak_asserted(p) == ('dw1', 'dw2')
+    for name in p.outputs:
+        assert np.array_equal(low[name], p.steps.restated()[name]) and np.all(acc[name] >= p.tolerances()[name])
+        if name in leaks:
+            lin = rel_linf(p.leaked(name), p.ref[name])
+            print(f'    leak {name}: {leaks[name]:.3g} of the bound, rel_linf {lin:.2e}' + ('' if name != 'db1' else ' (not asserted)'))
+            if name != 'db1' and not leaks[name] >= W.VISIBLE:
+                failures.append(f'{name}: the leak mutant reaches {leaks[name]:.3g} tolerances (< {W.VISIBLE})')
+            if not lin < TOL_SUM16:
+                failures.append(f'{name}: rel_linf rejects the leak mutant too ({lin:.2e}): nothing new shown')
+    assert not failures, '\n'.join(failures)
+
+
+@pytest.mark.parametrize('index', range(len(B.PAIR_WAVE_DX_KEYS)), ids=B.PAIR_WAVE_DX_IDS)
+def test_pair_wave_dx_case_has_room_and_rejects_the_mutants(index):
+    """dx of pair_wave_bwd_h_kernel at (2, 11, 600) and (1, 3, 560), every pixel judged at the kernel's own roundings:
+    beyond what its contested roundings explain the float32 restatement uses at most half of the tolerance, stored it
+    keeps to the whole; at most 5 % of the pixels have a widening above their arithmetic and store terms; the strip
+    kernel's slope-and-product rule and an unrounded alpha each exceed the tolerance."""
+    c = B.pair_wave_dx_case(index)
+    failures = _judge_pair16(c.problem.steps, ('dx',), c.id)
+    p = c.problem
+    assert np.array_equal(p.ref['dx'], p.steps.ref['dx']) and np.array_equal(p.tolerances()['dx'], p.steps.tolerances()['dx'])
+    assert p.device('g').max() <= B.F16_MAX and np.array_equal(p.device('g'), p.q['g'] * 2.0 ** p.gscale)
     assert not failures, '\n'.join(failures)

@@ -51,8 +51,14 @@ splits: `Runtime.last_gemm` must report the slabs test_gpu_gemm_configs.expect_g
 windows_dense_bwd, and dw1 / db1 / dw2 / db2 of the float32 conv_pair_bwd with act2 none and Sigmoid.  Every case runs
 with max_blocks 0 and 3, overwriting NaN-filled buffers and accumulating onto init = float32(ref r), with the producer's
 own finish and inside `with rt.defer_wgrad():`, where the call is issued TWICE into two sets of buffers so that the
-group kernels run two recorded finishes (GEMMs), the second at a non-zero `first_block`; both sets are judged.  Not
-covered: the binary16 pair weight gradients (elementwise_wgrad says why).
+group kernels run two recorded finishes (GEMMs), the second at a non-zero `first_block`; both sets are judged.
+
+The binary16 pair at its own roundings (elementwise_wgrad.PAIR16_KEYS, elementwise_bound.PAIR_WAVE_DX_KEYS): dw1 / db1 / dw2
+/ db2 of pair_strip_bwd_h_kernel at (3, 20, 32), (1, 13, 141), (2, 8, 128) and of pair_wave_bwd_h_kernel at (1, 3, 600), (1, 3,
+560), (3, 1, 560), and the dx of the wave kernel at (2, 11, 600) and (1, 3, 560), pad1 0 and 0.25, act2 none and Sigmoid,
+against the kernel's rounding points restated in float64 with every binary16 rounding of a float32 value as an interval;
+pair_band 0 and 2, pair_g 4 and 2, need_dx True and False, overwriting and accumulating, own finish and deferred twice;
+`Runtime.last_pair` after every launch.  Measured: dw1 <= 0.021, db1 <= 0.015, dw2 <= 0.048, db2 < 0.0005, dx <= 0.958.
 
 The largest err / tol of every output is printed before it is judged.
 """
@@ -66,11 +72,12 @@ import elementwise_wgrad as W
 from conftest import rel_linf
 from test_gpu_conv_padding import DEFAULTS, DGRAD, FWD, KERNELS, KID, ctx  # noqa: F401  (ctx: the NaN-filling fixture)
 from test_gpu_gemm_configs import GEMM_DEFAULTS, WS_HALF, expect_gemm, expect_group
+from test_gpu_pair_forms import expect_pair
 
 pytestmark = pytest.mark.gpu
 
 CAPS = (0, 3)
-EXTRA_DEFAULTS = dict(act_dispatch=1, pair_band=0)       # options a test sets on top of a case's own, and their defaults
+EXTRA_DEFAULTS = dict(act_dispatch=1, pair_band=0, pair_g=4)       # options a test sets on top of a case's own, and their defaults
 
 
 def launches(CP, c):
@@ -335,4 +342,131 @@ def test_every_weight_gradient_element_within_the_derived_bound(index, ctx):
     every launch form: max_blocks 0 and 3, overwriting and accumulating, the producer's own finish and the deferred
     group with two recorded calls."""
     failures = judge_wgrad(ctx, W.WCASES[index])
+    assert not failures, '\n'.join(failures)
+
+
+# ---- the binary16 pair at its own roundings ----------------------------------------------------------------------------------
+def pair16_launch(CP, st):
+    """bwd(buffers, accumulate, need_dx) -> dx or None: conv_pair_bwd on the device operands of Pair16Steps `st`"""
+    from univer_ocr_amd.hip import lib as hiplib
+    from univer_ocr_amd.nn import ops
+    q = st.base.q
+    x, yout, g = CP.copy(q['x']), CP.copy(st.yout), CP.copy(st.g_dev)
+    g.gscale = st.gscale                        # dy is stored times 2^k; the kernels divide dw / db by it, dx keeps it
+    w1, b1, w2 = (CP.copy(q[k], np.float32) for k in ('w1', 'b1', 'w2'))
+    act2 = hiplib.ACT_SIGMOID if st.sig else hiplib.ACT_NONE
+    return lambda b, acc, need_dx: ops.conv_pair_bwd(x, yout, g, w1, b1, w2, b['dw1'], b['db1'], b['dw2'], b['db2'], st.pad1,
+                                                     True, True, B.ALPHA, act2, need_dx=need_dx, accumulate=acc)
+
+
+def pair16_forms(st):
+    """the option sets of a case: pair_band 0 and 2 (three rows: two bands, the second with one row), and for the wave
+    kernel pair_g 4 and 2"""
+    return [dict(pair_band=band, pair_g=g) for band in (0, 2) for g in ((4, 2) if st.kernel == 'wave' else (4,))]
+
+
+def judge_dx16(CP, st, dx, what, failures):
+    host = CP.asnumpy(dx)
+    ref, tol = st.ref['dx'], st.tolerances()['dx']
+    assert host.shape == ref.shape and host.dtype == np.float16 and dx.gscale == st.gscale, (what, host.shape, host.dtype)
+    r = W.ratio(host, ref, tol)
+    at = tuple(int(j) for j in np.unravel_index(np.argmax(r), r.shape))
+    print(f'{what} dx: largest err / tol {r.max():.3f} at {at} (rel_linf '
+          f'{rel_linf(np.nan_to_num(host.astype(np.float64)), ref):.2e}, NaN {int(np.isnan(host).sum())})')
+    if not r.max() <= 1.0:
+        failures.append(f'{what} dx: err / tol = {r.max():.3f} at {at}, {int((r > 1.0).sum())} of {r.size} pixels over')
+
+
+def set_pair_options(rt, opts):
+    for key in ('pair_band', 'pair_g'):
+        rt.set_option(key, opts.get(key, EXTRA_DEFAULTS[key]))
+
+
+@pytest.mark.parametrize('index', range(len(W.PAIR16_KEYS)), ids=W.PAIR16_IDS)
+def test_binary16_pair_weight_gradients_within_the_bound_at_their_roundings(index, ctx):
+    """dw1, db1, dw2, db2 of pair_strip_bwd_h_kernel and pair_wave_bwd_h_kernel element by element against the kernel's own
+    rounding points restated in float64, every binary16 rounding of a float32 value an interval (elementwise_wgrad.
+    PairWgrad16Problem): pair_band 0 and 2, pair_g 4 and 2 (wave kernel), need_dx True and False (with dx judged as
+    stored), overwriting NaN-filled buffers and accumulating onto init = float32(ref r), with the producer's finish and
+    inside `rt.defer_wgrad()` issued twice; after each launch `Runtime.last_pair` must be what
+    test_gpu_pair_forms.expect_pair predicts (kernel 5: wave, 4: cooperative)."""
+    p = W.pair16_problem(*W.PAIR16_KEYS[index])
+    st, rt = p.steps, ctx.runtime()
+    for key, value in DEFAULTS:
+        rt.set_option(key, value)
+    ctx.set_dtype('float16')
+    call = pair16_launch(ctx, st)
+    cu = rt.device_info()['cu_count']
+    n, h, w = st.base.shape
+    failures, worst = [], {}
+    try:
+        for opts in pair16_forms(st):
+            set_pair_options(rt, opts)
+            want = expect_pair('bwd', 'float16', n, h, w, st.pad1, opts, cu)[0]
+            assert want[0] == (5 if st.kernel == 'wave' else 4), want
+            for need_dx in (True, False):
+                for accumulate in (False, True):
+                    tols = p.tolerances(accumulate)
+                    for deferred in (False, True):
+                        what = f'{W.PAIR16_IDS[index]} {opts} need_dx={need_dx} accumulate={accumulate} ' + \
+                            ('deferred' if deferred else 'own finish')
+                        sets = [{k: ctx.copy(p.init[k], np.float32) if accumulate else ctx.empty(p.ref[k].shape, np.float32)
+                                 for k in p.outputs} for _ in range(2 if deferred else 1)]
+                        dxs = []
+                        with rt.defer_wgrad() if deferred else contextlib.nullcontext():
+                            for buffers in sets:
+                                dxs.append(call(buffers, accumulate, need_dx))
+                                if rt.last_pair() != want:
+                                    failures.append(f'{what}: last_pair {rt.last_pair()} != host rule {want}')
+                        for i, (buffers, dx) in enumerate(zip(sets, dxs)):
+                            if need_dx:
+                                judge_dx16(ctx, st, dx, f'{what} set {i}', failures)
+                            else:
+                                assert dx is None
+                            for name in p.outputs:
+                                host = ctx.asnumpy(buffers[name])
+                                expect, tol = p.expected(name, accumulate), tols[name]
+                                assert host.shape == expect.shape and host.dtype == np.float32, (what, name, host.shape, host.dtype)
+                                r = W.ratio(host, expect, tol)
+                                at = tuple(int(j) for j in np.unravel_index(np.argmax(r), r.shape))
+                                worst[name] = max(worst.get(name, 0.0), float(r.max()))
+                                print(f'{what} set {i} {name}: largest err / tol {r.max():.3f} at {at} (rel_linf '
+                                      f'{rel_linf(np.nan_to_num(host.astype(np.float64)), expect):.2e}, NaN {int(np.isnan(host).sum())})')
+                                if not r.max() <= 1.0:
+                                    failures.append(f'{what} set {i} {name}: err / tol = {r.max():.3f} at {at}, '
+                                                    f'{int((r > 1.0).sum())} of {r.size} elements over')
+    finally:
+        set_pair_options(rt, {})
+    print(f'{W.PAIR16_IDS[index]}: largest err / tol over all forms ' + ', '.join(f'{k} {v:.3f}' for k, v in worst.items()))
+    assert not failures, '\n'.join(failures)
+
+
+@pytest.mark.parametrize('index', range(len(B.PAIR_WAVE_DX_KEYS)), ids=B.PAIR_WAVE_DX_IDS)
+def test_pair_wave_dx_every_pixel_within_the_bound_at_its_roundings(index, ctx):
+    """dx of pair_wave_bwd_h_kernel (pages wider than 512 columns) with every pixel judged at the kernel's own roundings
+    (elementwise_bound.PairWaveDxProblem), with and without accumulation of the weight gradients, in the default bands,
+    with one band per image and with pair_g 2; `Runtime.last_pair` must report kernel 5 in the form the host rules give."""
+    c = B.pair_wave_dx_case(index)
+    p, st, rt = c.problem, c.problem.steps, ctx.runtime()
+    for key, value in DEFAULTS:
+        rt.set_option(key, value)
+    ctx.set_dtype('float16')
+    call = pair16_launch(ctx, st)
+    cu = rt.device_info()['cu_count']
+    n, h, w = st.base.shape
+    failures = []
+    try:
+        for opts in ({}, {'pair_band': h}, {'pair_g': 2}):
+            set_pair_options(rt, opts)
+            want = expect_pair('bwd', 'float16', n, h, w, st.pad1, opts, cu)[0]
+            assert want[0] == 5, want
+            for accumulate in (False, True):
+                grads = {k: ctx.full(st.ref[k].shape, 0.0, np.float32) for k in ('dw1', 'db1', 'dw2', 'db2')}
+                dx = call(grads, accumulate, True)
+                what = f'{c.id} {opts} accumulate={accumulate}'
+                if rt.last_pair() != want:
+                    failures.append(f'{what}: last_pair {rt.last_pair()} != host rule {want}')
+                judge_dx16(ctx, st, dx, what, failures)
+    finally:
+        set_pair_options(rt, {})
     assert not failures, '\n'.join(failures)
